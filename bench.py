@@ -1,9 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the geometry hot path on MI355X -- prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up (inputs, outputs, the one-time K1 autotune), W warm-up steps,
+K timed steps, the outputs of the last timed step if ``--dump-outputs DIR`` is given, and the result line (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = wall milliseconds per timed step, ``roofline``
+from the timed steps' own HIP events).  Everything else described below -- the check of the timed buffers, the
+library-default re-timing, the buffer fill rate, BASELINE configs 2, 3 and 5, the allocation lottery, the CPU baseline
+and, at N > 1, the row-sharded config 4 section -- runs only with ``--full`` (the ``--no-*`` options switch single
+parts of it off).
+
+``--dump-outputs DIR`` (rank 0) writes, after the timed region, a fixed seeded sample of what the last timed step
+computed: ``DIR/dist.npy`` (DUMP_BLOCKS x A x A float32 distance blocks), ``DIR/dist_mask.npy`` (the same blocks of
+the pair mask as float32 0 / 1) and ``DIR/sample_bij.npy`` (the (b, i, j) of each block, float64); about 30 MB.
+The inputs are seeded, so two builds run with the same arguments can be compared file for file.
 
 Both forms work for N > 1.  The control plane (barriers, max over ranks, verdict exchange) is a gloo group; only the
 all-gather of the row-shard section runs on RCCL (its own group), so the headline line does not depend on RCCL.  Started WITHOUT a launcher (WORLD_SIZE unset), ``bench.py --gpus N`` is its own launcher:
@@ -35,7 +48,7 @@ outputs are resident in HBM before the timed region.
   checks take well under a minute); the self-launcher gives the whole run 570 s,
   inside the driver's 600 s.
 
-After the timed region the buffers that were just timed are CHECKED (sampled
+With ``--full``, after the timed region the buffers that were just timed are CHECKED (sampled
 blocks against the fp32 formula, exact mask checksum per structure, symmetry of
 one structure); a failed check prints no result line and exits non-zero.
 
@@ -76,6 +89,7 @@ BYTES_PER_PAIR = N_ATOM * N_ATOM * 4 + N_ATOM * N_ATOM  # 900 + 225
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip table)
 XGMI_LINK_GBPS = 153.0  # per xGMI link and direction (MI355X_MICROARCH.md); a GPU has 7 links
 C4_B, C4_N = 32, 2048   # BASELINE config 4
+DUMP_BLOCKS, DUMP_SEED = 16384, 2024   # --dump-outputs: residue-pair blocks sampled from the (B, N, N, A, A) outputs
 
 
 def synth(seed, b=B, n=N_RES, a=N_ATOM):
@@ -200,6 +214,21 @@ def check_outputs(xyz, mask, out_d, out_m, n_blocks=64, seed=7):
     if torch.isnan(out_d[bsym]).any():
         fails.append(f"structure {bsym} holds NaN")
     return fails
+
+
+def dump_outputs(out_dir, out_d, out_m, n_blocks=DUMP_BLOCKS, seed=DUMP_SEED):
+    """Write a fixed seeded sample of (b, i, j) blocks of the two output buffers as .npy files (see the module doc)."""
+    import numpy as np
+
+    b_, n_ = out_d.shape[:2]
+    g = torch.Generator().manual_seed(seed)
+    bij = torch.stack([torch.randint(0, b_, (n_blocks,), generator=g), torch.randint(0, n_, (n_blocks,), generator=g),
+                       torch.randint(0, n_, (n_blocks,), generator=g)], 1)
+    bs, i_s, js = bij.to(out_d.device).unbind(1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "dist.npy"), out_d[bs, i_s, js].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "dist_mask.npy"), out_m[bs, i_s, js].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "sample_bij.npy"), bij.double().numpy())
 
 
 def all_ranks_early(dist, world, obj):
@@ -777,6 +806,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a fixed seeded sample of the last timed step's outputs to DIR/*.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the check and every informational section (see the module doc); "
+                         "a plain run does only the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rowshard", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the post-run verification of the timed buffers")
@@ -896,8 +930,14 @@ def main():
         dist.all_gather_object(per_rank_kernel_ms, kernel_ms)
     elapsed, kernel_ms_max = max_over_ranks([elapsed, kernel_ms])
 
+    # ---- what the last timed step wrote, before anything below touches the buffers ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_d, out_m)
+
     # ---- verification of the timed buffers (outside the timed region) ----
-    if args.no_check:
+    if not args.full:
+        check = "skipped (plain run; --full checks the timed buffers)"
+    elif args.no_check:
         check = "skipped (--no-check)"
     else:
         fails = check_outputs(xyz, mask, out_d, out_m)
@@ -918,7 +958,7 @@ def main():
     default_cfg = dict(ops._K1_CANDIDATE_PATTERN[0])
     tuned_cfg = {f: _lib.get_tuning("k1_" + f, dev) for f in default_cfg}
     default_kernel_ms = kernel_ms
-    if tuned_cfg != default_cfg:
+    if args.full and tuned_cfg != default_cfg:
         try:
             for f, v in default_cfg.items():
                 _lib.set_tuning("k1_" + f, v, dev)
@@ -937,13 +977,14 @@ def main():
         finally:
             for f, v in tuned_cfg.items():
                 _lib.set_tuning("k1_" + f, v, dev)
-    default_kernel_ms = max_over_ranks([default_kernel_ms])[0]
+    if args.full:
+        default_kernel_ms = max_over_ranks([default_kernel_ms])[0]
 
-    # ---- which class of allocation did this run draw?  fill rate of the very buffers that were timed (they have been
-    # checked; their contents are no longer needed) ----
-    fill_GBps = fill_rate_GBps(out_d, out_m)
-    fill_all = max_over_ranks([-fill_GBps])
-    fill_GBps_min = -fill_all[0]      # the slowest rank's buffers, like kernel_ms_max
+        # ---- which class of allocation did this run draw?  fill rate of the very buffers that were timed (they have
+        # been checked; their contents are no longer needed) ----
+        fill_GBps = fill_rate_GBps(out_d, out_m)
+        fill_all = max_over_ranks([-fill_GBps])
+        fill_GBps_min = -fill_all[0]      # the slowest rank's buffers, like kernel_ms_max
     plan = _lib.k1_plan(B, N_RES, N_ATOM, dist_misalign=out_d.data_ptr() % 16, mask_misalign=out_m.data_ptr() % 16,
                         has_atom_mask=True, device=dev)
 
@@ -957,10 +998,6 @@ def main():
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "check": check,
-        "check_what": "64 sampled (b,i,j) blocks of the timed buffers vs the fp32 formula <= 1e-5 and their mask blocks "
-                      "exactly; exact mask checksum of every structure; bitwise symmetry of one whole structure; the "
-                      "buffers were NaN/False-filled and then warmed up on a decoy input (doubled coordinates, inverted mask): "
-                      "anything the timed launches had not overwritten would fail these checks",
         "config": {"workload": "pairwise_distance_matrix B=64 N_res=512 N_atom=15 (dist fp32 + bool mask), per GPU",
                    "global_batch": B * world, "n_res": N_RES, "n_atom": N_ATOM,
                    "parallelism": "replicas-of-batch" if world > 1 else "single-gpu",
@@ -983,18 +1020,26 @@ def main():
                      "kernel_ms_min_max_this_rank": [min(per_step_ms), max(per_step_ms)],
                      "kernel_ms_per_step_this_rank": [round(t, 4) for t in per_step_ms],
                      "wall_minus_kernel_ms_per_step": elapsed / args.steps * 1e3 - kernel_ms_max,
-                     "algorithmic_bytes_per_launch": B * N_RES * N_RES * BYTES_PER_PAIR,
-                     "buffer_fill_GBps": fill_GBps_min, "frac_of_buffer_fill": achieved / fill_GBps_min,
-                     "buffer_fill_what": "torch.fill_ on the two timed output buffers, HIP events, mean of 5 after one "
-                                         "warm-up, measured after the timed region and the check"},
+                     "algorithmic_bytes_per_launch": B * N_RES * N_RES * BYTES_PER_PAIR},
         "pct_hbm_roofline": 100.0 * achieved / HBM_PEAK_GBPS,
-        # the timed launches ran `config.k1_autotune`'s pick; these three say what the library default does on the same buffers
-        "default_config": ops._cand_label(default_cfg) + (" (= the tuner's pick: the headline IS the default launch)"
-                                                           if tuned_cfg == default_cfg else ""),
-        "default_config_kernel_ms": default_kernel_ms,
-        "default_config_frac_of_hbm_peak": B * N_RES * N_RES * BYTES_PER_PAIR / (default_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-        "tuner_gain": default_kernel_ms / kernel_ms_max,
     }
+    if check == "ok":
+        result["check_what"] = ("64 sampled (b,i,j) blocks of the timed buffers vs the fp32 formula <= 1e-5 and their mask "
+                                "blocks exactly; exact mask checksum of every structure; bitwise symmetry of one whole "
+                                "structure; the buffers were NaN/False-filled and then warmed up on a decoy input (doubled "
+                                "coordinates, inverted mask): anything the timed launches had not overwritten would fail these checks")
+    if args.full:
+        result["roofline"].update({
+            "buffer_fill_GBps": fill_GBps_min, "frac_of_buffer_fill": achieved / fill_GBps_min,
+            "buffer_fill_what": "torch.fill_ on the two timed output buffers, HIP events, mean of 5 after one "
+                                "warm-up, measured after the timed region and the check"})
+        result.update({
+            # the timed launches ran `config.k1_autotune`'s pick; these three say what the library default does on the same buffers
+            "default_config": ops._cand_label(default_cfg) + (" (= the tuner's pick: the headline IS the default launch)"
+                                                               if tuned_cfg == default_cfg else ""),
+            "default_config_kernel_ms": default_kernel_ms,
+            "default_config_frac_of_hbm_peak": B * N_RES * N_RES * BYTES_PER_PAIR / (default_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+            "tuner_gain": default_kernel_ms / kernel_ms_max})
     if dist:
         result["rccl_ranks"] = world if args.backend == "nccl" else 0
         result["dist_backend"] = args.backend
@@ -1013,7 +1058,7 @@ def main():
             os.dup2(saved_stdout_fd, 1)
             print(json.dumps(result), flush=True)
 
-    if world == 1:
+    if world == 1 and args.full:
         # The headline is complete and checked.  What follows at N = 1 is informational (allocation lottery: 4 x 18.9 GB of
         # allocations and ~60 launches; the CPU baseline: ~20 s of host work): a hang or a hard fault in it must not lose the
         # result line -- the watchdog prints it and ends the process with a non-zero code, like the N > 1 path below.
@@ -1027,11 +1072,11 @@ def main():
 
         threading.Thread(target=watchdog_n1, daemon=True).start()
 
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and args.full and not args.no_other_configs:
         # BASELINE configs 2, 3 and 5, timed and checked on this GPU (informational; `value` is the headline's)
         result["other_configs"] = other_configs(dev, args.steps)
 
-    if world == 1 and not args.no_lottery and shop_report is None:
+    if world == 1 and args.full and not args.no_lottery and shop_report is None:
         # Informational, AFTER the measurement above and not part of it: the same kernel timed on four fresh output
         # allocations of this process.  MI355X allocations come in a faster and a slower class; the line
         # above reports whatever torch.empty handed out, this shows the spread a caller can choose from with
@@ -1067,13 +1112,13 @@ def main():
         except Exception as exc:  # noqa: BLE001 -- informational only
             result["roofline"]["allocation_lottery"] = {"error": f"{type(exc).__name__}: {exc}"}
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(xyz_cpu, mask_cpu)
         result["gpu_over_cpu"] = value / result["cpu_baseline"]["value"]
         result["gpu_over_cpu_single_thread"] = value / result["cpu_baseline"]["single_thread"]["value"]
 
     exit_code = 0
-    if (world > 1 or force_dist) and not args.no_rowshard:
+    if (world > 1 or force_dist) and args.full and not args.no_rowshard:
         # A stalled collective or hung kernel must not look like success: the watchdog prints the main line (the
         # headline measurement above is complete and valid) and then ends EVERY rank with a non-zero code.
         def watchdog():

@@ -46,3 +46,25 @@ def test_host_cpu_info_fields():
     info = _bench().host_cpu_info()
     assert set(info) == {"host_cpu", "host_logical_cpus", "host_physical_cores", "host_sockets"}
     assert info["host_logical_cpus"] >= 1
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_buffers(tmp_path):
+    """``--dump-outputs``: float32 blocks of both buffers at seeded (b, i, j), the same sample on every call, and at the
+    headline shape well under 64 MB in all."""
+    import numpy as np
+
+    bench = _bench()
+    xyz, mask = bench.synth(0, b=3, n=12)
+    d, m = O.pairwise_distance_matrix(xyz, mask)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), d, m, n_blocks=300)
+    files = ("dist.npy", "dist_mask.npy", "sample_bij.npy")
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.array_equal(a[f], np.load(tmp_path / "b" / f)), f
+    bij = a["sample_bij.npy"].astype(np.int64)
+    assert a["dist.npy"].dtype == np.float32 and a["dist_mask.npy"].dtype == np.float32
+    assert np.array_equal(a["dist.npy"], d[bij[:, 0], bij[:, 1], bij[:, 2]].numpy())
+    assert np.array_equal(a["dist_mask.npy"], m[bij[:, 0], bij[:, 1], bij[:, 2]].float().numpy())
+    a_ = bench.N_ATOM
+    assert bench.DUMP_BLOCKS * (2 * a_ * a_ * 4 + 3 * 8) < 64 << 20

@@ -54,10 +54,10 @@ def test_one_rank_rccl_native_gather():
 
 
 def test_bench_gpus2_self_launch_as_the_driver_invokes_it():
-    """``python3 bench.py --gpus 2 --backend gloo --steps 2 --warmup 1 --no-cpu-baseline`` with no launcher around it
-    (the command form the driver uses for N > 1): the parent starts two rank processes of itself, relays ONE JSON line
-    and exits 0; the headline check and the check after the gather are both ok and the strong-scaling keys are
-    top-level."""
+    """``python3 bench.py --gpus 2 --backend gloo --steps 2 --warmup 1 --no-cpu-baseline --full`` with no launcher around
+    it (the command form for N > 1; --full runs the check and the row-shard section): the parent starts two rank
+    processes of itself, relays ONE JSON line and exits 0; the headline check and the check after the gather are both
+    ok and the strong-scaling keys are top-level."""
     code, log = conftest.wait_rehearsal("bench_gpus2", 750)
     out = open(conftest.REHEARSALS["bench_gpus2"]["stdout"]).read()
     lines = [ln for ln in out.splitlines() if ln.strip()]

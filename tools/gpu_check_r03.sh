@@ -6,7 +6,7 @@ mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; rc=$?; tail -3 $O/pytest.log
 [ $rc -eq 0 ] || exit $rc
 for k in 1 2; do
-  timeout -k 10 240 python bench.py --no-cpu-baseline > $O/bench_$k.json 2> $O/bench_$k.err || exit 1
+  timeout -k 10 240 python bench.py --full --no-cpu-baseline > $O/bench_$k.json 2> $O/bench_$k.err || exit 1
 done
 python3 - $O <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.build(); g.smoke(); 
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 900 python -m pytest tests -q -m gpu > $O/pytest.log 2>&1; rc=$?; tail -3 $O/pytest.log | cut -c1-300
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 560 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?; tail -2 $O/bench.err | cut -c1-300
+timeout -k 10 560 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?; tail -2 $O/bench.err | cut -c1-300
 python3 - $O/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,5 +1,5 @@
 # Round-5 measurement set (run on the GPU box: bash tools/gpu_profile_r05.sh [outdir-name]):
-#   * bench.py plain (the line as the driver sees it, with other_configs);
+#   * bench.py --full (the whole line, with other_configs);
 #   * bench.py --no-cpu-baseline under rocprofv3 --kernel-trace --stats TWICE in one lease (two processes): each trace is cut
 #     at the K1 dispatch ordinals the line reports -- the timed region AND the allocation lottery's kept pair -- so profiles/
 #     holds a kernel-trace mean for a fast-class pair next to whatever the default allocation drew;
@@ -9,14 +9,14 @@ set -o pipefail
 O=gpurun_out/${1:-r05fin}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
-timeout -k 10 400 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
 for k in 1 2; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace$k -o b -- python3 bench.py --no-cpu-baseline --no-other-configs > $O/bench_traced_$k.json 2> $O/bench_traced_$k.err; echo "trace $k rc=$?"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace$k -o b -- python3 bench.py --full --no-cpu-baseline --no-other-configs > $O/bench_traced_$k.json 2> $O/bench_traced_$k.err; echo "trace $k rc=$?"
   python3 tools/summarize_rocprof.py ranges $O/trace$k $O/bench_kernel_trace_ranges_$k.json $O/bench_traced_$k.json
 done
 python3 tools/summarize_rocprof.py stats $O/trace1 $O/bench_kernel_stats.csv
-timeout -k 10 240 rocprofv3 --output-format csv --pmc WRITE_SIZE -d $O/pmcw -o b -- python3 bench.py --no-cpu-baseline --no-other-configs --no-lottery --steps 3 > $O/bench_pmcw.json 2> $O/bench_pmcw.err; echo "pmcw rc=$?"
-timeout -k 10 240 rocprofv3 --output-format csv --pmc FETCH_SIZE -d $O/pmcf -o b -- python3 bench.py --no-cpu-baseline --no-other-configs --no-lottery --steps 3 > $O/bench_pmcf.json 2> $O/bench_pmcf.err; echo "pmcf rc=$?"
+timeout -k 10 240 rocprofv3 --output-format csv --pmc WRITE_SIZE -d $O/pmcw -o b -- python3 bench.py --full --no-cpu-baseline --no-other-configs --no-lottery --steps 3 > $O/bench_pmcw.json 2> $O/bench_pmcw.err; echo "pmcw rc=$?"
+timeout -k 10 240 rocprofv3 --output-format csv --pmc FETCH_SIZE -d $O/pmcf -o b -- python3 bench.py --full --no-cpu-baseline --no-other-configs --no-lottery --steps 3 > $O/bench_pmcf.json 2> $O/bench_pmcf.err; echo "pmcf rc=$?"
 python3 tools/summarize_rocprof.py pmc $O/pmcw $O/bench_pmc_w.json 0
 python3 tools/summarize_rocprof.py pmc $O/pmcf $O/bench_pmc_f.json 0
 python3 tools/make_k1_traffic.py $O/bench_pmc_w.json $O/bench_pmc_f.json $O/k1_traffic.json 5 > /dev/null; echo "traffic rc=$?"

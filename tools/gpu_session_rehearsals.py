@@ -8,8 +8,9 @@ keeps the number of processes on the card bounded by running in two phases:
   phase A (in parallel):  gloo_world2  tools/rehearse_rowshard.py --world 2 --backend gloo          (2 ranks)
                           rccl_world1  tools/rehearse_rowshard.py --world 1 --backend nccl --quick  (1 rank)
                           c_abi_demo   examples/c_abi_demo.c, compiled with gcc and run             (1 process)
-  phase B (after A):      bench_gpus2  python3 bench.py --gpus 2 --backend gloo --steps 2 --warmup 1 --no-cpu-baseline
-                                       -- the exact command form the driver uses for N > 1, self-launching (2 ranks)
+  phase B (after A):      bench_gpus2  python3 bench.py --gpus 2 --backend gloo --steps 2 --warmup 1 --no-cpu-baseline --full
+                                       -- the command form for N > 1, self-launching (2 ranks), with the check and the
+                                       row-sharded section that only --full runs
 
 For every name it writes ``<outdir>/<name>.log`` (stdout + stderr; bench_gpus2: stderr only, stdout goes to
 ``<name>.stdout``) and, when the rehearsal has ended, ``<outdir>/<name>.exit`` holding its exit code.
@@ -41,7 +42,7 @@ def main():
     }
     phase_b = {
         "bench_gpus2": [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"],
+                        "--warmup", "1", "--no-cpu-baseline", "--full"],
     }
 
     def run_phase(cmds, timeout):

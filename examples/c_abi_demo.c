@@ -7,8 +7,8 @@
  *
  * Allocates with hipMalloc, calls ps_pairwise_distance_f32 / ps_pairwise_distance_cfg_f32 / ps_frames_f32 /
  * ps_diffuse_f32 on a stream of its own (the last two also captured into a hipGraph and replayed), and checks the
- * results on the host: distances against the float formula
- * sqrtf((dx*dx + dy*dy) + dz*dz) -- within 1 ulp with the default hardware square root, bit for bit with
+ * results on the host: distances against the reference's torch.norm,
+ * sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx*dx))) -- within 1 ulp with the default hardware square root, bit for bit with
  * ps_k1_config.exact_sqrt = 1 -- the pair mask exactly, frames for orthonormality.  Exit code 0 = all checks passed.
  * (Replaces, for a C host, what StructureBatch.pairwise_distance_matrix does in the reference: protstruc.py:455-484.)
  */
@@ -95,8 +95,7 @@ int main(void) {
                             const float* p = xyz + (((size_t)b * N + i) * A + a) * 3;
                             const float* q = xyz + (((size_t)b * N + j) * A + c) * 3;
                             const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
-                            const float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-                            const float want = sqrtf((sx + sy) + sz);
+                            const float want = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
                             const size_t o = ((((size_t)b * N + i) * N + j) * A + a) * A + c;
                             const uint32_t gb = bits_of(dist[o]), wb = bits_of(want);
                             const uint32_t ulps = gb > wb ? gb - wb : wb - gb;

@@ -68,7 +68,8 @@ const char* ps_error_string(int code);
  */
 typedef struct ps_k1_config {
     int struct_size;      /* = sizeof(ps_k1_config); a launcher refuses any other value (caller built against another header) */
-    int exact_sqrt;       /* 0: hardware v_sqrt_f32 (exact for 85 % of inputs, 1 ulp off otherwise); 1: correctly rounded */
+    int exact_sqrt;       /* 0: hardware v_sqrt_f32 (exact for 85 % of inputs, 1 ulp off otherwise); 1: correctly rounded,
+                             the reference's torch.norm bit for bit */
     int variant;          /* [diagnostic] 0: fast kernels (pattern / flat pattern / row-tile / row-phase / fixed-A flat); 1: the simple
                              kernels everywhere (slot-decode kernel for A = 15, element-per-lane kernel otherwise) */
     int flat;             /* 0: none of the fast kernels for A != 15 and no flat kernel for A = 15; 1 (default): every kernel
@@ -121,9 +122,10 @@ void ps_k1_config_default(ps_k1_config* cfg);
  * and row-phase kernels (the latter also N * A * A <= 2^28); B <= 65535 only for the two simple kernels that put the
  * structure on grid.z (A = 15 on unaligned planes or with variant = 1; A > 64; unaligned planes).  K2 / K3 run on 1-D grids:
  * any batch size up to 2^31 workgroups per launch.
- * Arithmetic: sqrt((dx*dx + dy*dy) + dz*dz) in fp32 without contraction; the square
- * root is the hardware instruction (exact for 85 % of inputs, 1 ulp off otherwise)
- * unless ps_k1_config.exact_sqrt selects the correctly rounded routine.
+ * Arithmetic: sqrt(fma(dz, dz, fma(dy, dy, dx*dx))) in fp32, the squared length of the
+ * reference's torch.norm; the square root is the hardware instruction (exact for 85 % of
+ * inputs, 1 ulp off otherwise) unless ps_k1_config.exact_sqrt selects the correctly rounded
+ * routine, which gives the reference's bits.
  */
 int ps_pairwise_distance_f32(const float* xyz, const uint8_t* atom_mask,
                              float* dist, uint8_t* dist_mask,

@@ -78,19 +78,17 @@ struct run16 {
     }
 };
 
+// The squared length is the reference's torch.norm form, fma(dz, dz, fma(dy, dy, dx * dx)) (norm_sq3), in both modes.
 // EXACT = false: the hardware square root (v_sqrt_f32: exact for 84.95 % of all inputs, 1 ulp off for the rest,
-// never more -- tools/microbench/sqrt_check.hip; the reference's own torch.norm is 1 ulp away from this formula on
-// ~11 % of entries).  EXACT = true: correctly rounded (sqrt_rn_mk), 22 more VALU instructions per 16-byte slot, which
-// on the devices that can store at 7 TB/s costs 10-16 % of K1's speed (profiles/r01_k1_ab_sqrt_mk.log).
-// The subtractions and squares of x and y are one packed operation each (v_pk_add_f32 / v_pk_mul_f32 on the even-aligned
-// (x, y) half of the float4 a ds_read_b128 delivers: two lanes of work per issue slot).  Every operation rounds exactly as
-// its scalar twin and the sum keeps the reference's order (sx + sy) + sz, so the values are those of the scalar formula.
+// never more -- tools/microbench/sqrt_check.hip), so at most 1 ulp from the reference.  EXACT = true: correctly rounded
+// (sqrt_rn_mk), the reference's bits; 22 more VALU instructions per 16-byte slot, which on the devices that can store
+// at 7 TB/s costs 10-16 % of K1's speed (profiles/r01_k1_ab_sqrt_mk.log).
+// The x and y subtractions are one packed operation (v_pk_add_f32 on the even-aligned (x, y) half of the float4 a
+// ds_read_b128 delivers).  Every operation rounds exactly as its scalar twin, so the values are those of dist3_t.
 template <bool EXACT>
 __device__ __forceinline__ float dist_pp(float4 p, float4 q) {
     const f32x2 dxy = f32x2{p.x, p.y} - f32x2{q.x, q.y};
-    const f32x2 sxy = dxy * dxy;
-    const float dz = p.z - q.z, sz = dz * dz;
-    const float x = (sxy.x + sxy.y) + sz;
+    const float x = norm_sq3(dxy.x, dxy.y, p.z - q.z);
     return EXACT ? sqrt_rn_mk(x) : __builtin_amdgcn_sqrtf(x);
 }
 
@@ -335,9 +333,7 @@ template <int MATH>
 __device__ __forceinline__ float dist_pp_m(float4 p, float4 q) {
 #ifdef PS_EXPERIMENTS
     if (MATH == 3) {
-        float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-        float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-        return sqrt_rn_pos((sx + sy) + sz);
+        return sqrt_rn_pos(norm_sq3(p.x - q.x, p.y - q.y, p.z - q.z));
     }
 #else
     static_assert(MATH == 0 || MATH == 1, "experiment modes are compiled only with -DPS_EXPERIMENTS");
@@ -1642,9 +1638,7 @@ __global__ __launch_bounds__(256) void k1_pairdist_generic(const float* __restri
         const float* xj = xyz + (((size_t)b * N + j) * A + c) * 3;
         const float* xa = xi + a * 3;
         if (dist) {
-            float dx = xa[0] - xj[0], dy = xa[1] - xj[1], dz = xa[2] - xj[2];
-            float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-            const float x = (sx + sy) + sz;
+            const float x = norm_sq3(xa[0] - xj[0], xa[1] - xj[1], xa[2] - xj[2]);
             dist[obase + e] = EXACT ? sqrt_rn_mk(x) : __builtin_amdgcn_sqrtf(x);
         }
         if (dmask) {

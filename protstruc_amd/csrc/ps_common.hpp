@@ -72,25 +72,39 @@ __device__ __forceinline__ float sqrt_rn_mk(float x) {
     return __builtin_amdgcn_classf(x, 0x2F0) ? x : g;   // +-0, +-subnormal, +inf
 }
 
-// |a - b| exactly as K1 evaluates it (protstruc.py:477-479): differences, squares, two adds, sqrt
+// The squared length as the reference's torch.norm(v, dim=-1) evaluates it (protstruc.py:477-479, geometry.py:29-31):
+// fma(z, z, fma(y, y, x * x)) -- ATen's CPU norm accumulates with fused multiply-adds (pinned bit for bit against
+// ATen by tests/test_reference_arithmetic.py).  Written with explicit fmas: -ffp-contract=off still holds everywhere else.
+__device__ __forceinline__ float norm_sq3(float x, float y, float z) {
+    return __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x));
+}
+
+// |a - b| exactly as the reference evaluates it: differences, then norm_sq3, then a correctly rounded sqrt
 __device__ __forceinline__ float dist3(f3 a, f3 b) {
-    float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-    return sqrt_rn_mk((sx + sy) + sz);
+    return sqrt_rn_mk(norm_sq3(a.x - b.x, a.y - b.y, a.z - b.z));
 }
 
 // the same with K1's choice of square root (ps_k1_config.exact_sqrt): hardware v_sqrt_f32 or correctly rounded
 template <bool EXACT>
 __device__ __forceinline__ float dist3_t(f3 a, f3 b) {
-    float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-    const float x = (sx + sy) + sz;
+    const float x = norm_sq3(a.x - b.x, a.y - b.y, a.z - b.z);
     return EXACT ? sqrt_rn_mk(x) : __builtin_amdgcn_sqrtf(x);
 }
 
 // x.norm(dim=-1) (geometry.py:29-31); correctly rounded sqrt in half the instructions of the library routine
-// (identical result unless the squared norm is subnormal, i.e. |a| < 1e-19)
-__device__ __forceinline__ float norm3(f3 a) { return sqrt_rn_mk(dot3(a, a)); }
+// (identical result unless the squared norm is below 2.0e-31, i.e. |a| < 4.5e-16)
+__device__ __forceinline__ float norm3(f3 a) { return sqrt_rn_mk(norm_sq3(a.x, a.y, a.z)); }
+
+// torch.linalg.cross (the reference's frames, geometry.py:437): one rounded product, then a fused multiply-add per
+// component, fma(u_i, v_j, -(u_j * v_i)) -- pinned against ATen like norm_sq3.  Not for dihedrals: those use np.cross
+// (cross3 below), whose exact cancellation on coincident arms the +0 diagonal of pairwise_dihedrals depends on.
+__device__ __forceinline__ f3 cross3_fused(f3 u, f3 v) {
+    f3 r;
+    r.x = __builtin_fmaf(u.y, v.z, -(u.z * v.y));
+    r.y = __builtin_fmaf(u.z, v.x, -(u.x * v.z));
+    r.z = __builtin_fmaf(u.x, v.y, -(u.y * v.x));
+    return r;
+}
 
 // np.cross component order: u1*v2 - u2*v1, ... two products then one subtract
 __device__ __forceinline__ f3 cross3(f3 u, f3 v) {
@@ -547,10 +561,11 @@ __device__ __forceinline__ f32x2 sqrt_rn_mk_v(f32x2 x) {
 }
 
 // dist3 / angle3 for two problems per lane (same operations in the same order as the scalar functions below / above)
+__device__ __forceinline__ f32x2 norm_sq3v(f32x2 x, f32x2 y, f32x2 z) {
+    return __builtin_elementwise_fma(z, z, __builtin_elementwise_fma(y, y, x * x));
+}
 __device__ __forceinline__ f32x2 dist3v(f3v a, f3v b) {
-    const f32x2 dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    const f32x2 sx = dx * dx, sy = dy * dy, sz = dz * dz;
-    return sqrt_rn_mk_v((sx + sy) + sz);
+    return sqrt_rn_mk_v(norm_sq3v(a.x - b.x, a.y - b.y, a.z - b.z));
 }
 
 // geometry.angle (geometry.py:64-71): no clamp before acos.  The reference divides the dot product by the product of
@@ -561,9 +576,7 @@ __device__ __forceinline__ f32x2 dist3v(f3v a, f3v b) {
 // zero-length arm (the diagonal of pairwise_planar_angles) is 0 * rsq(0) = 0 * inf = NaN like the reference's 0 / 0.
 template <bool EXACT>
 __device__ __forceinline__ f32x2 dist3v_t(f3v a, f3v b) {
-    const f32x2 dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    const f32x2 sx = dx * dx, sy = dy * dy, sz = dz * dz;
-    const f32x2 x = (sx + sy) + sz;
+    const f32x2 x = norm_sq3v(a.x - b.x, a.y - b.y, a.z - b.z);
     if (EXACT) return sqrt_rn_mk_v(x);
     return f32x2{__builtin_amdgcn_sqrtf(x.x), __builtin_amdgcn_sqrtf(x.y)};
 }
@@ -736,7 +749,7 @@ __device__ __forceinline__ void dihedral4v_ref_n(const f3v (&a)[NC], const f3v (
         const f3v m = cross3v(n1, n2);
         x[q] = dot3v_f(n1, n2);
         y0[q] = dot3v_f(m, b1);
-        nb[q] = sqrt_rn_mk_v((b1.x * b1.x + b1.y * b1.y) + b1.z * b1.z);   // squares are never -0: dot3's leading `0 +` changes no bit
+        nb[q] = sqrt_rn_mk_v(norm_sq3v(b1.x, b1.y, b1.z));
     }
     div_ieee_vn<NC>(y0, nb, y);
     atan2_lib_vn<NC>(y, x, out);
@@ -750,13 +763,13 @@ __device__ __forceinline__ void angle3v_ref_n(const f3v (&a)[NC], const f3v (&b)
     for (int q = 0; q < NC; ++q) {
         const f3v ba = sub3v(a[q], b[q]), bc = sub3v(c[q], b[q]);
         num[q] = dot3v_f(ba, bc);
-        den[q] = sqrt_rn_mk_v((ba.x * ba.x + ba.y * ba.y) + ba.z * ba.z) * sqrt_rn_mk_v((bc.x * bc.x + bc.y * bc.y) + bc.z * bc.z);
+        den[q] = sqrt_rn_mk_v(norm_sq3v(ba.x, ba.y, ba.z)) * sqrt_rn_mk_v(norm_sq3v(bc.x, bc.y, bc.z));
     }
     div_ieee_vn<NC>(num, den, cs);
     acos_lib_vn<NC>(cs, out);
 }
 
-// geometry.gram_schmidt (geometry.py:428-439); e3 uses the last-axis cross
+// geometry.gram_schmidt (geometry.py:428-439); e3 uses the last-axis cross, torch.linalg.cross's fused form
 __device__ __forceinline__ void gram_schmidt3(f3 a, f3 b, f3 c, f3& e1, f3& e2, f3& e3) {
     f3 v1 = sub3(c, b);
     e1 = div3(v1, norm3(v1));
@@ -764,7 +777,7 @@ __device__ __forceinline__ void gram_schmidt3(f3 a, f3 b, f3 c, f3& e1, f3& e2, 
     float p = dot3(e1, v2);
     f3 u2 = sub3(v2, scale3(e1, p));
     e2 = div3(u2, norm3(u2));
-    e3 = cross3(e1, e2);
+    e3 = cross3_fused(e1, e2);
 }
 
 __device__ __forceinline__ f3 load3(const float* __restrict__ p) { return f3{p[0], p[1], p[2]}; }

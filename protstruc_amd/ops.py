@@ -255,8 +255,10 @@ def _autotune_k1(device, args, n_pairs: int, N: int, A: int, force: bool = False
 
 
 def set_exact_sqrt(flag: bool, device=None) -> None:
-    """K1 arithmetic on ``device`` (default: the current one): False (default) = hardware square root, exact for
-    85 % of inputs and 1 ulp off for the rest; True = correctly rounded square root (slower on fast allocations).
+    """K1 arithmetic on ``device`` (default: the current one).  Both modes take the squared length as the reference's
+    torch.norm does, fma(dz, dz, fma(dy, dy, dx * dx)).  False (default) = hardware square root, exact for 85 % of inputs
+    and 1 ulp off for the rest, so within 1 ulp of the reference; True = correctly rounded square root, the reference's
+    bits (slower on fast allocations).
     ``PROTSTRUC_AMD_EXACT_SQRT=1`` in the environment makes True the default of every device."""
     _lib.set_tuning("k1_exact_sqrt", 1 if flag else 0, device)
 
@@ -269,8 +271,9 @@ def set_exact_angles(flag: bool, device=None) -> None:
     """K3 / featuriser arithmetic on ``device`` (default: the current one).  False (default): the fast forms -- exact
     where the reference is exact, otherwise within the conditioning gates (3.8e-6 of off-diagonal dihedrals more than
     1e-5 from the reference at unit scale).  True: geometry.dihedral / geometry.angle in the reference's order of
-    operations (three cross products, division by |b1|, library atan2 / acos): no entry beyond 1e-5 on well-conditioned
-    inputs, on the same per-CU sweep kernels as the fast forms (DESIGN.md section 4 has both modes' times).  ``PROTSTRUC_AMD_EXACT_ANGLES=1`` makes True the default of every device."""
+    operations (three np.cross-form cross products, torch.norm's fused squared length, IEEE division by |b1|, library
+    atan2 / acos): everything up to the atan2 / acos argument is the reference's bits, and no entry is beyond 1e-5, on
+    the same per-CU sweep kernels as the fast forms (DESIGN.md section 4 has both modes' times).  ``PROTSTRUC_AMD_EXACT_ANGLES=1`` makes True the default of every device."""
     _lib.set_exact_angles(flag, device)
 
 

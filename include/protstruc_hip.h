@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 5
+#define PS_ABI_VERSION 6
 int ps_abi_version(void);
 
 /* 0 for the product library.  1 for builds made with -DPS_EXPERIMENTS (tools/ only), which contain timing
@@ -271,7 +271,10 @@ int ps_frames_f32(const float* xyz, float* rot, float* trans,
  * Point-wise geometry primitives -- replace the free functions geometry.angle,
  * geometry.dihedral and geometry.gram_schmidt (geometry.py:39-124, :413-439) on
  * (n,3) point arrays:  mode 0: out[n] = angle(a,b,c);  mode 1: out[n] =
- * dihedral(a,b,c,d);  mode 2: out[n][3][3] = gram_schmidt(a,b,c).  Radians.
+ * dihedral(a,b,c,d);  mode 2: out[n][3][3] = gram_schmidt(a,b,c);  mode 3 (ABI 6):
+ * out[n][3] = place_fourth_atom(a,b,c, d[n][0], d[n][1], d[n][2]) (geometry.py:127-168)
+ * with d packed (length, planar, dihedral): |X-c| = length, angle(X,c,b) = planar,
+ * dihedral(a,b,c,X) = dihedral.  Radians.
  */
 int ps_pointwise_f32(int mode, const float* a, const float* b, const float* c, const float* d,
                      float* out, long long n, void* stream);
@@ -388,6 +391,26 @@ int ps_center_of_mass_f32(const float* xyz, float* com, int B, int N, int A, int
  */
 int ps_frames_to_backbone_f32(const float* rot, const float* trans, const float* ideal, int n_ideal,
                               float* xyz, int B, int N, int A, void* stream);
+
+/*
+ * K7 (ABI 6) -- backbone coordinates from dihedral angles: the inverse of ps_backbone_dihedrals, behind
+ * StructureBatch.from_backbone_dihedrals (the reference's from_dihedrals is a TODO, protstruc.py:321-339).
+ *   dihedrals[b][i]    = (phi_i, psi_i, omega_i) in ps_backbone_dihedrals_f32's layout;
+ *   bond_angles[b][i]  = (N_i-CA_i-C_i, CA_i-C_i-N_i+1, C_i-N_i+1-CA_i+1), radians  (NULL: 1.937, 116.2 deg, 121.7 deg);
+ *   bond_lengths[b][i] = (|N_i-CA_i|, |CA_i-C_i|, |C_i-N_i+1|), Angstrom          (NULL: 1.458, 1.523, 1.329);
+ *   chain_idx (B,N) fp32 and residue_mask (B,N) bytes are optional (NULL: one chain, every residue present).
+ * A segment starts at i = 0, where chain_idx changes (NaN != NaN) and after a residue whose mask is 0; each segment's
+ * first residue sits at the ideal position (CA at the origin, C on +x, N in the xy-plane with y > 0), and
+ *   N_i+1 = place(N_i, CA_i, C_i, |C-N|, CA-C-N, psi_i),  CA_i+1 = place(CA_i, C_i, N_i+1, |N-CA|, C-N-CA, omega_i),
+ *   C_i+1 = place(C_i, N_i+1, CA_i+1, |CA-C|, N-CA-C, phi_i+1)   (place = mode 3 of ps_pointwise_f32).
+ * phi at a segment's first residue and psi / omega at its last are never read into the result.  Evaluated as a
+ * segmented prefix scan of per-residue rigid transforms (error growing with log N, not N).  Writes every byte of
+ * xyz (B,N,A,3) -- slots 0/1/2 = N/CA/C, slot 4 = CB when include_cb (A >= 5), zeros elsewhere and for masked
+ * residues -- and atom_mask (B,N,A) fp32 1 / 0.  Deterministic (no atomics).
+ */
+int ps_backbone_from_dihedrals_f32(const float* dihedrals, const float* bond_angles, const float* bond_lengths,
+                                   const float* chain_idx, const uint8_t* residue_mask, float* xyz, float* atom_mask,
+                                   int include_cb, int B, int N, int A, void* stream);
 
 /*
  * Batched Kabsch fit -- replaces the per-structure loop of StructureBatch.align and

@@ -9,6 +9,7 @@
 // 3: ps_k1_plan_f32 (which kernel a K1 launch takes; host-only query); ps_inter_residue_geometry_f32 takes exact_sqrt.
 // 4: ps_pairwise_angles_f32 and ps_inter_residue_geometry_f32 take exact_angles (0: fast arithmetic, 1: the reference's
 //    order of operations).
+// 6: ps_backbone_from_dihedrals_f32 (K7); ps_pointwise_f32 mode 3 (place_fourth_atom).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void k4_frames(const float* __restrict__ xyz, 
 // (reference geometry.py:39-124, :413-439): a, b, c(, d) are (n,3) arrays.
 //   mode 0: out[n]   = angle(a, b, c)        mode 1: out[n] = dihedral(a, b, c, d)
 //   mode 2: out[n*9] = gram_schmidt(a, b, c) (3x3 row-major, basis vectors as columns)
+//   mode 3: out[n*3] = place_fourth_atom(a, b, c, d[n][0], d[n][1], d[n][2])  (d packed [length, planar, dihedral])
 __global__ __launch_bounds__(256) void k_pointwise(const float* __restrict__ a, const float* __restrict__ b,
                                                    const float* __restrict__ c, const float* __restrict__ d,
                                                    float* __restrict__ out, size_t n, int mode) {
@@ -42,13 +43,17 @@ __global__ __launch_bounds__(256) void k_pointwise(const float* __restrict__ a, 
         out[i] = angle3(pa, pb, pc);
     } else if (mode == 1) {
         out[i] = dihedral4(pa, pb, pc, load3(d + i * 3));
-    } else {
+    } else if (mode == 2) {
         f3 e1, e2, e3;
         gram_schmidt3(pa, pb, pc, e1, e2, e3);
         float* o = out + i * 9;
         o[0] = e1.x; o[1] = e2.x; o[2] = e3.x;
         o[3] = e1.y; o[4] = e2.y; o[5] = e3.y;
         o[6] = e1.z; o[7] = e2.z; o[8] = e3.z;
+    } else {
+        const f3 x = place4(pa, pb, pc, d[i * 3], d[i * 3 + 1], d[i * 3 + 2]);
+        float* o = out + i * 3;
+        o[0] = x.x; o[1] = x.y; o[2] = x.z;
     }
 }
 
@@ -56,7 +61,8 @@ __global__ __launch_bounds__(256) void k_pointwise(const float* __restrict__ a, 
 
 extern "C" int ps_pointwise_f32(int mode, const float* a, const float* b, const float* c, const float* d, float* out,
                                 long long n, void* stream) {
-    if (mode < 0 || mode > 2 || !a || !b || !c || !out || n < 0 || (mode == 1 && !d)) return (int)hipErrorInvalidValue;
+    if (mode < 0 || mode > 3 || !a || !b || !c || !out || n < 0 || ((mode == 1 || mode == 3) && !d))
+        return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
     return ps_launch(k_pointwise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), a, b, c, d, out, (size_t)n, mode);

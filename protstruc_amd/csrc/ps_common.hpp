@@ -780,6 +780,25 @@ __device__ __forceinline__ void gram_schmidt3(f3 a, f3 b, f3 c, f3& e1, f3& e2, 
     e3 = cross3_fused(e1, e2);
 }
 
+// geometry.place_fourth_atom (geometry.py:127-168), op for op: the X with |X - c| = length, angle(X, c, b) = planar and
+// dihedral(a, b, c, X) = dihedral.  The sines and cosines are the library's accurate sincosf, not __sinf / v_sin_f32: the
+// backbone builder (nerf.hip) chains thousands of these, and an angle error d at one residue moves every later atom by up
+// to (distance) * d.  What ps_pointwise_f32 mode 3 and the builder both evaluate, so the two cannot drift apart.
+__device__ __forceinline__ f3 place4(f3 a, f3 b, f3 c, float length, float planar, float dihedral) {
+    f3 bc = sub3(b, c);
+    bc = div3(bc, norm3(bc));
+    f3 n = cross3(sub3(b, a), bc);
+    n = div3(n, norm3(n));
+    const f3 m = cross3(n, bc);
+    float sp, cp, sd, cd;
+    sincosf(planar, &sp, &cp);
+    sincosf(dihedral, &sd, &cd);
+    const float m0 = length * cp, m1 = length * sp * cd, m2 = -length * sp * sd;
+    // c + sum([m0 * bc, m1 * m, m2 * n]): Python's sum starts from 0
+    return f3{c.x + (((0.0f + m0 * bc.x) + m1 * m.x) + m2 * n.x), c.y + (((0.0f + m0 * bc.y) + m1 * m.y) + m2 * n.y),
+              c.z + (((0.0f + m0 * bc.z) + m1 * m.z) + m2 * n.z)};
+}
+
 __device__ __forceinline__ f3 load3(const float* __restrict__ p) { return f3{p[0], p[1], p[2]}; }
 
 // Launch `kernel` and return THIS launch's status.  hipLaunchKernel reports the result of the launch it performs;

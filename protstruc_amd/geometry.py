@@ -1,6 +1,6 @@
 """Free-function geometry API of the reference (``protstruc.geometry``), on the GPU.
 
-``angle``, ``dihedral`` and ``gram_schmidt`` evaluate in the same HIP device
+``angle``, ``dihedral``, ``gram_schmidt`` and ``place_fourth_atom`` evaluate in the same HIP device
 functions the batch kernels use (csrc/ps_common.hpp) through a point-wise
 launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
 Type polymorphism follows the reference's ``with_tensor`` decorator
@@ -10,6 +10,8 @@ moved to) the GPU; there is no CPU evaluation path.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -18,6 +20,11 @@ from . import ops
 
 # ideal backbone geometry (reference constants/ideal.py:2-36): bond lengths in Angstrom, angles in radians
 IDEAL_NA, IDEAL_AC, IDEAL_NAC = 1.458, 1.523, 1.937
+# the peptide bond, for StructureBatch.from_backbone_dihedrals: |C-N| from the reference (ideal.C_N); the two angles
+# around it, which the reference has no constant for, from Engh & Huber (CA-C-N 116.2 deg, C-N-CA 121.7 deg).
+# The builder kernel (csrc/nerf.hip) rounds the same doubles to float32.
+IDEAL_C_N = 1.329
+IDEAL_CACN, IDEAL_CNCA = math.radians(116.2), math.radians(121.7)
 
 
 def ideal_backbone_coordinates(size, include_cb: bool = False) -> torch.Tensor:
@@ -95,6 +102,24 @@ def gram_schmidt(a, b, c):
     """Orthonormal basis of the plane through (c-b) and (a-b), basis vectors as columns (reference geometry.py:413-439)."""
     (a, b, c), ft = _prep([a, b, c])
     return _finish(ops.pointwise(2, a, b, c), ft)
+
+
+def place_fourth_atom(a, b, c, length, planar, dihedral):
+    """The atom X with |X - c| = ``length``, angle(X, c, b) = ``planar`` and dihedral(a, b, c, X) = ``dihedral``
+    (reference geometry.py:127-168).  ``a``, ``b``, ``c`` are (n,3) points, the three parameters (n,1) or anything that
+    broadcasts as a trailing size-1 axis against them (scalars included).  Evaluated by the same device function as
+    StructureBatch.from_backbone_dihedrals (ps_pointwise_f32 mode 3)."""
+    params = [np.asarray(p, dtype=np.float32) if isinstance(p, (int, float)) else p for p in (length, planar, dihedral)]
+    (a, b, c, length, planar, dihedral), ft = _prep([a, b, c] + params)
+    length, planar, dihedral = (p.reshape(1) if p.ndim == 0 else p for p in (length, planar, dihedral))
+    if any(p.shape[-1] != 1 for p in (length, planar, dihedral)):
+        raise ValueError("length, planar and dihedral must have a trailing axis of size 1, e.g. (n, 1)")
+    full = torch.broadcast_shapes(a.shape, b.shape, c.shape, length.shape, planar.shape, dihedral.shape)
+    if full[-1] != 3:
+        raise ValueError("points must have a trailing axis of size 3")
+    lead = tuple(full[:-1]) + (1,)
+    d = torch.cat([p.float().expand(lead) for p in (length, planar, dihedral)], dim=-1)
+    return _finish(ops.pointwise(3, a, b, c, d), ft)
 
 
 def kabsch(a, b):

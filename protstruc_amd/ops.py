@@ -485,7 +485,8 @@ def inter_residue_geometry(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor] 
 
 
 def pointwise(mode: int, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, d: Optional[torch.Tensor] = None):
-    """angle (mode 0) / dihedral (1) / gram_schmidt (2) over broadcast (*,3) point tensors."""
+    """angle (mode 0) / dihedral (1) / gram_schmidt (2) / place_fourth_atom (3, ``d`` packed [length, planar, dihedral])
+    over broadcast (*,3) tensors."""
     pts = [a, b, c] + ([d] if d is not None else [])
     pts = torch.broadcast_tensors(*[_f32c(p, "points") for p in pts])
     shape = pts[0].shape[:-1]
@@ -495,13 +496,57 @@ def pointwise(mode: int, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, d: O
     n = flat[0].shape[0]
     dev = flat[0].device
     with _on(dev):
-        out = torch.empty((n, 9) if mode == 2 else (n,), dtype=torch.float32, device=dev)
+        out = torch.empty({2: (n, 9), 3: (n, 3)}.get(mode, (n,)), dtype=torch.float32, device=dev)
         rc = 0
         if not (n == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
             rc = _lib.load().ps_pointwise_f32(mode, _ptr(flat[0]), _ptr(flat[1]), _ptr(flat[2]),
-                                              _ptr(flat[3]) if mode == 1 else None, _ptr(out), n, _stream(flat[0]))
+                                              _ptr(flat[3]) if mode in (1, 3) else None, _ptr(out), n, _stream(flat[0]))
     _lib.check(rc, "ps_pointwise_f32")
-    return out.reshape(*shape, 3, 3) if mode == 2 else out.reshape(shape)
+    if mode == 2:
+        return out.reshape(*shape, 3, 3)
+    return out.reshape(*shape, 3) if mode == 3 else out.reshape(shape)
+
+
+def check_backbone_from_dihedrals_shapes(dihedrals, chain_idx=None, residue_mask=None, bond_angles=None,
+                                         bond_lengths=None) -> None:
+    """Shape rules of ``backbone_from_dihedrals``, on shapes only (no device, no launch): ValueError on a mismatch."""
+    shape = tuple(dihedrals.shape)
+    if len(shape) != 3 or shape[-1] != 3:
+        raise ValueError(f"dihedrals must have shape (batch, residues, 3) [phi, psi, omega], got {shape}")
+    for name, t, want in (("chain_idx", chain_idx, shape[:2]), ("residue_mask", residue_mask, shape[:2]),
+                          ("bond_angles", bond_angles, shape), ("bond_lengths", bond_lengths, shape)):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{name} must have shape {want} to match dihedrals {shape}, got {tuple(t.shape)}")
+
+
+def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.Tensor] = None,
+                            residue_mask: Optional[torch.Tensor] = None, bond_angles: Optional[torch.Tensor] = None,
+                            bond_lengths: Optional[torch.Tensor] = None, include_cb: bool = False, n_slots: int = 15):
+    """K7.  Backbone coordinates from (B,N,3) [phi, psi, omega]: returns xyz (B,N,n_slots,3) with N / CA / C in slots
+    0-2 (and CB in slot 4 when ``include_cb``), zeros elsewhere, and atom_mask (B,N,n_slots) float32 1 / 0.  Optional
+    per-residue (B,N) chain_idx / residue_mask start new segments; optional (B,N,3) bond_angles / bond_lengths override
+    the ideal geometry (include/protstruc_hip.h)."""
+    check_backbone_from_dihedrals_shapes(dihedrals, chain_idx, residue_mask, bond_angles, bond_lengths)
+    if n_slots < (5 if include_cb else 3):
+        raise ValueError(f"n_slots = {n_slots} leaves no room for {'N, CA, C and CB' if include_cb else 'N, CA, C'}")
+    dih = _f32c(dihedrals, "dihedrals")
+    _same_device(dih, chain_idx=chain_idx, residue_mask=residue_mask, bond_angles=bond_angles, bond_lengths=bond_lengths)
+    chain = None if chain_idx is None else _f32c(chain_idx, "chain_idx")
+    rmask = _u8c(residue_mask, "residue_mask")
+    ang = None if bond_angles is None else _f32c(bond_angles, "bond_angles")
+    lens = None if bond_lengths is None else _f32c(bond_lengths, "bond_lengths")
+    B, N = dih.shape[:2]
+    dev = dih.device
+    with _on(dev):
+        xyz = torch.empty(B, N, n_slots, 3, dtype=torch.float32, device=dev)
+        atom_mask = torch.empty(B, N, n_slots, dtype=torch.float32, device=dev)
+        rc = 0
+        if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            rc = _lib.load().ps_backbone_from_dihedrals_f32(
+                _ptr(dih), _ptr(ang), _ptr(lens), _ptr(chain), _ptr(rmask), _ptr(xyz), _ptr(atom_mask), int(bool(include_cb)),
+                B, N, n_slots, _stream(dih))
+    _lib.check(rc, "ps_backbone_from_dihedrals_f32")
+    return xyz, atom_mask
 
 
 def frames(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *, want_rot: bool = True,

@@ -156,8 +156,50 @@ class StructureBatch:
                                   "StructureBatch.from_pdb(path) instead")
 
     @classmethod
+    def from_backbone_dihedrals(
+        cls,
+        dihedrals: Union[np.ndarray, torch.Tensor],
+        chain_idx: Union[np.ndarray, torch.Tensor] = None,
+        chain_ids: List[List[str]] = None,
+        seq: List[Dict[str, str]] = None,
+        residue_idx: Union[np.ndarray, torch.Tensor] = None,
+        residue_mask: Union[np.ndarray, torch.Tensor] = None,
+        bond_angles: Union[np.ndarray, torch.Tensor] = None,
+        bond_lengths: Union[np.ndarray, torch.Tensor] = None,
+        include_cb: bool = False,
+        **kwargs,
+    ) -> "StructureBatch":
+        """Backbone (N, CA, C[, CB]) built from ``dihedrals`` (B, N, 3) = [phi, psi, omega] in radians, the layout
+        :meth:`backbone_dihedrals` returns -- its inverse (what the reference's ``from_dihedrals`` documents).
+
+        A segment starts at the first residue, where ``chain_idx`` changes (NaN counts as a change) and after a residue
+        whose ``residue_mask`` is False; each segment's first residue sits at the ideal position (CA at the origin, C on
+        +x, N in the xy-plane) and the others follow by ``geometry.place_fourth_atom``.  phi at a segment's first residue
+        and psi / omega at its last are never used.  ``bond_angles`` / ``bond_lengths`` (B, N, 3) override the ideal
+        [N-CA-C, CA-C-N(next), C-N(next)-CA(next)] and [|N-CA|, |CA-C|, |C-N(next)|] (defaults: ``geometry.IDEAL_*``).
+        Masked residues get zero coordinates and a zero mask; the atom mask is float32 ones / zeros.  Computed in float32
+        by one HIP launch (a segmented prefix scan of per-residue rigid transforms), on ``device=`` or the current GPU."""
+        from .general import MAX_N_ATOMS_PER_RESIDUE
+
+        if (chain_idx is not None and chain_ids is None) or (chain_idx is None and chain_ids is not None):
+            raise ValueError("Both `chain_idx` and `chain_ids` should be provided or None.")
+        dihedrals, chain_idx, residue_idx, residue_mask, bond_angles, bond_lengths = (
+            _always_tensor(x) for x in (dihedrals, chain_idx, residue_idx, residue_mask, bond_angles, bond_lengths))
+        ops.check_backbone_from_dihedrals_shapes(dihedrals, chain_idx, residue_mask, bond_angles, bond_lengths)
+        dev = kwargs.get("device") or (dihedrals.device if dihedrals.is_cuda else _default_device())
+
+        def on_dev(t):
+            return None if t is None else t.to(dev)
+
+        xyz, atom_mask = ops.backbone_from_dihedrals(
+            on_dev(dihedrals), on_dev(chain_idx), on_dev(residue_mask), on_dev(bond_angles), on_dev(bond_lengths),
+            include_cb=include_cb, n_slots=MAX_N_ATOMS_PER_RESIDUE)
+        return cls(xyz, atom_mask, chain_idx, chain_ids, seq, residue_idx, **kwargs)
+
+    @classmethod
     def from_dihedrals(cls, dihedrals, chain_idx=None, chain_ids=None, **kwargs):
-        """Unimplemented in the reference as well (`# TODO`, protstruc.py:321-339)."""
+        """Unimplemented in the reference as well (`# TODO`, protstruc.py:321-339); kept as the reference has it.
+        :meth:`from_backbone_dihedrals` builds a batch from backbone dihedral angles."""
         raise NotImplementedError("from_dihedrals is a TODO stub in the reference (protstruc.py:321-339)")
 
     # ------------------------------------------------------------------ getters (protstruc.py:341-433)

@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 6
+#define PS_ABI_VERSION 7
 int ps_abi_version(void);
 
 /* 0 for the product library.  1 for builds made with -DPS_EXPERIMENTS (tools/ only), which contain timing
@@ -411,6 +411,46 @@ int ps_frames_to_backbone_f32(const float* rot, const float* trans, const float*
 int ps_backbone_from_dihedrals_f32(const float* dihedrals, const float* bond_angles, const float* bond_lengths,
                                    const float* chain_idx, const uint8_t* residue_mask, float* xyz, float* atom_mask,
                                    int include_cb, int B, int N, int A, void* stream);
+
+/*
+ * K8 / K9 (ABI 7) -- backbone N / CA / C distance matrices from inter-residue geometry (trRosetta), behind
+ * geometry.reconstruct_backbone_distmat_from_interresidue_geometry (reference geometry.py:229-347).  Three steps,
+ * launched in this order on one stream:
+ *
+ * ps_backbone_distmat_init_f32 (K8): d_cb, omega, theta, phi (B,L,L) fp32 -> out (B,3,3,L,L) fp32, planes (a, b) with
+ * atom order N, CA, C.  x = the reference's ideal_local_frame() (N, CA, C, CB).  Per pair i != j, in residue i's frame:
+ *   CB' = place(N, CA, CB, d_cb[i,j], phi[i,j], theta[i,j]),   CA' = place(CA, CB, CB', |CB-CA|, phi[j,i], omega[i,j]),
+ *   N'  = place(CB, CB', CA', |CA-N|, CB-CA-N, theta[j,i]),    C'  = place(CB', CA', N', |N-C|, CA-N-C, CB-CA-N-C)
+ * (place = mode 3 of ps_pointwise_f32), out[a][b][i][j] = |x_a - y_b|.  omega is the trRosetta dihedral
+ * (CA_i, CB_i, CB_j, CA_j), theta[i,j] = dihedral(N_i, CA_i, CB_i, CB_j), phi[i,j] = angle(CA_i, CB_i, CB_j).  Then:
+ * the diagonal i = j is 0 for a = b and the ideal intra-residue distance otherwise; [C][N][i][i+1] = [N][C][i+1][i] =
+ * 1.329 (the peptide bond), or MASK = 12345679 where chain_breaks[b][i] != 0; all nine planes are MASK where
+ * mask[b][i][j] == 0; NaN becomes MASK and +-inf +-FLT_MAX (torch.nan_to_num).  chain_breaks (B,L) bytes ("chain ends
+ * after residue i"), mask (B,L,L) bytes and lengths (B) int32 are optional (NULL: no break, every pair, L).  A residue
+ * i >= lengths[b] is an inert node: 0 on its own diagonal planes (a = b, i = j), MASK everywhere else.
+ *
+ * ps_floyd_warshall_f32 (K9): in place on D (B,G,G,L,L) fp32 with node (g, i) = g * L + i, n = G L nodes (G = 3: the
+ * distance-matrix layout above; G = 1: a plain (B,L,L) matrix), for k = 0 .. n-1 in order:
+ *   D[r][c] = min(D[r][c], D[k][r] + D[k][c])     (the reference's rule, geometry.py:327-330; it reads row k only).
+ * Blocked in 64-pivot panels; equal to that sequential float32 loop bit for bit when every entry is >= 0 and not NaN
+ * (what K8 writes).  workspace: device memory of at least ps_floyd_warshall_workspace_bytes(B, G, L) bytes, 4-byte
+ * aligned, overwritten.  Requires (G L)^2 < 2^31.
+ *
+ * ps_backbone_distmat_finish_f32: in place on out (B,3,3,L,L): D = (D + D^T) / 2 over the 3L nodes, then the bonds
+ * again -- [N][CA][i][i] = [CA][N][i][i] = 1.458, [CA][C][i][i] = [C][CA][i][i] = 1.523, [C][N][i][i+1] =
+ * [N][C][i+1][i] = 1.329 except where chain_breaks[b][i] != 0 (the reference re-bonds chain breaks here; this does not)
+ * -- and NaN in every entry of a residue i >= lengths[b].
+ *
+ * Requires B <= 65535 and 9 L^2 < 2^31.  Deterministic (no atomics).
+ */
+int ps_backbone_distmat_init_f32(const float* d_cb, const float* omega, const float* theta, const float* phi,
+                                 const uint8_t* mask, const uint8_t* chain_breaks, const int* lengths, float* out,
+                                 int B, int L, void* stream);
+/* Host-only query: the workspace ps_floyd_warshall_f32 needs, in bytes (-1 for invalid arguments). */
+long long ps_floyd_warshall_workspace_bytes(int B, int G, int L);
+int ps_floyd_warshall_f32(float* D, int B, int G, int L, void* workspace, long long workspace_bytes, void* stream);
+int ps_backbone_distmat_finish_f32(float* D, const uint8_t* chain_breaks, const int* lengths, int B, int L,
+                                   void* stream);
 
 /*
  * Batched Kabsch fit -- replaces the per-structure loop of StructureBatch.align and

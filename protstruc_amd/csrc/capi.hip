@@ -10,6 +10,8 @@
 // 4: ps_pairwise_angles_f32 and ps_inter_residue_geometry_f32 take exact_angles (0: fast arithmetic, 1: the reference's
 //    order of operations).
 // 6: ps_backbone_from_dihedrals_f32 (K7); ps_pointwise_f32 mode 3 (place_fourth_atom).
+// 7: ps_backbone_distmat_init_f32 (K8), ps_floyd_warshall_f32 / ps_floyd_warshall_workspace_bytes (K9),
+//    ps_backbone_distmat_finish_f32.
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

@@ -3,6 +3,7 @@
 ``angle``, ``dihedral``, ``gram_schmidt`` and ``place_fourth_atom`` evaluate in the same HIP device
 functions the batch kernels use (csrc/ps_common.hpp) through a point-wise
 launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
+``reconstruct_backbone_distmat_from_interresidue_geometry`` runs the distance-matrix kernels (csrc/distmat.hip).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -25,6 +26,9 @@ IDEAL_NA, IDEAL_AC, IDEAL_NAC = 1.458, 1.523, 1.937
 # The builder kernel (csrc/nerf.hip) rounds the same doubles to float32.
 IDEAL_C_N = 1.329
 IDEAL_CACN, IDEAL_CNCA = math.radians(116.2), math.radians(121.7)
+# the placeholder of unknown distances in reconstruct_backbone_distmat_from_interresidue_geometry (reference
+# geometry.py:21); exact in float32
+MASK = 12345679
 
 
 def ideal_backbone_coordinates(size, include_cb: bool = False) -> torch.Tensor:
@@ -129,3 +133,88 @@ def kabsch(a, b):
     mask = torch.ones(1, a.shape[0], dtype=torch.bool, device=a.device)
     R, t = ops.kabsch(a.reshape(1, -1, 1, 3).contiguous(), b.reshape(1, -1, 1, 3).contiguous(), mask)
     return _finish(R[0], ft), _finish(t[0], ft)
+
+
+def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):
+    """chain_breaks as a (B, L) bool array / tensor ("the chain ends after residue i"), or None.  Accepts a list of
+    residue indices (every structure), a list of B such lists, or a (B, L) ((L,) unbatched) boolean array / tensor."""
+    if chain_breaks is None:
+        return None
+    if isinstance(chain_breaks, (torch.Tensor, np.ndarray)):
+        want = (B, L) if batched else (L,)
+        if tuple(chain_breaks.shape) != want:
+            raise ValueError(f"a chain_breaks array must have shape {want}, got {tuple(chain_breaks.shape)}")
+        return chain_breaks.reshape(B, L) if isinstance(chain_breaks, torch.Tensor) else np.asarray(chain_breaks).reshape(B, L)
+    items = list(chain_breaks)
+    per_structure = len(items) > 0 and all(isinstance(x, (list, tuple, np.ndarray)) for x in items)
+    if per_structure and len(items) != B:
+        raise ValueError(f"chain_breaks holds {len(items)} lists for {B} structures")
+    lists = items if per_structure else [items] * B
+    out = np.zeros((B, L), dtype=bool)
+    for b, idx in enumerate(lists):
+        for i in idx:
+            if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)):
+                raise ValueError(f"chain_breaks entries must be residue indices (int), got {i!r}")
+            if not 0 <= int(i) < L:
+                raise ValueError(f"chain break after residue {int(i)} is outside 0 .. {L - 1}")
+            out[b, int(i)] = True
+    return out
+
+
+def reconstruct_backbone_distmat_from_interresidue_geometry(d_cb, omega, theta, phi, mask=None, chain_breaks=None,
+                                                            lengths=None):
+    """The N / CA / C distance matrix implied by trRosetta inter-residue geometry (reference geometry.py:229-347).
+
+    ``d_cb`` (CB-CB distance), ``omega``, ``theta`` and ``phi`` are (L, L) -> (3, 3, L, L), or (B, L, L) ->
+    (B, 3, 3, L, L); plane [a, b] holds |atom a of residue i - atom b of residue j| for atoms N, CA, C.
+    ``omega`` is the trRosetta dihedral (CA_i, CB_i, CB_j, CA_j) -- ``StructureBatch.pairwise_dihedrals(["CA", "CB"],
+    ["CB", "CA"])``, not ``inter_residue_geometry()["omega"]`` (which is dihedral(CA_i, CB_i, CA_j, CB_j), following the
+    reference's featuriser): the placement of CA_j below is only consistent with the former.  ``theta[i, j]`` =
+    dihedral(N_i, CA_i, CB_i, CB_j), ``phi[i, j]`` = angle(CA_i, CB_i, CB_j).
+
+    Residue j's atoms are placed in residue i's ideal frame (``place_fourth_atom`` four times), the diagonal and the
+    bonds take ideal values, ``chain_breaks`` (a list of residue indices i -- the chain ends after i -- for every
+    structure, a list of B such lists, or a (B, L) boolean array) remove the peptide bond, ``mask`` (pair mask, (L, L)
+    or (B, L, L)) False and NaN entries become ``MASK``, and the Floyd-Warshall pass of the reference replaces them by
+    shortest-path distances over the 3 L atoms; the result is symmetrised and the bonds are set again.  Unlike the
+    reference, that last step does not put a peptide bond back across a chain break.  ``lengths`` (B,) pads a ragged
+    batch: residues at or beyond a structure's length do not take part, and their entries are NaN.
+
+    numpy in -> numpy out, tensor in -> tensor out (on the GPU); evaluated in float32 by the K8 / K9 kernels."""
+    for name, t in (("d_cb", d_cb), ("omega", omega), ("theta", theta), ("phi", phi)):
+        if not isinstance(t, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{name} must be a tensor or an ndarray")
+    shape = tuple(d_cb.shape)
+    if len(shape) not in (2, 3) or shape[-1] != shape[-2]:
+        raise ValueError(f"d_cb must have shape (L, L) or (B, L, L), got {shape}")
+    for name, t in (("omega", omega), ("theta", theta), ("phi", phi)):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have the shape of d_cb {shape}, got {tuple(t.shape)}")
+    batched = len(shape) == 3
+    B, L = (shape[0] if batched else 1), shape[-1]
+    if mask is not None and tuple(mask.shape) != shape:
+        raise ValueError(f"mask must have the shape of d_cb {shape}, got {tuple(mask.shape)}")
+    breaks = _chain_break_matrix(chain_breaks, B, L, batched)
+    if lengths is not None:
+        if isinstance(lengths, (int, np.integer)):
+            lengths = [int(lengths)]
+        if not isinstance(lengths, torch.Tensor):
+            lengths = np.asarray(lengths, dtype=np.int64)
+            if lengths.shape != (B,) or (lengths < 0).any() or (lengths > L).any():
+                raise ValueError(f"lengths must be {B} integers in 0 .. {L}, got {lengths.tolist()}")
+            lengths = lengths.astype(np.int32)
+        elif tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    ops.check_distmat_size(B, L)
+
+    args = [d_cb, omega, theta, phi] + [t for t in (mask, breaks, lengths) if t is not None]
+    prepped, ft = _prep(args)
+    d_cb, omega, theta, phi = (t.reshape(B, L, L) for t in prepped[:4])
+    rest = iter(prepped[4:])
+    mask = None if mask is None else next(rest).reshape(B, L, L)
+    breaks = None if breaks is None else next(rest).reshape(B, L)
+    lengths = None if lengths is None else next(rest)
+    out = ops.backbone_distmat_init(d_cb, omega, theta, phi, mask, breaks, lengths)
+    ops.floyd_warshall_(out, G=3)
+    ops.backbone_distmat_finish_(out, breaks, lengths)
+    return _finish(out if batched else out[0], ft)

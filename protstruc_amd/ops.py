@@ -549,6 +549,118 @@ def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.T
     return xyz, atom_mask
 
 
+
+def check_distmat_shapes(d_cb, omega, theta, phi, mask=None, chain_breaks=None, lengths=None) -> None:
+    """Shape rules of ``backbone_distmat_init`` on (B,L,L) inputs, on shapes only (no device, no launch): ValueError."""
+    shape = tuple(d_cb.shape)
+    if len(shape) != 3 or shape[1] != shape[2]:
+        raise ValueError(f"d_cb must have shape (batch, L, L), got {shape}")
+    for name, t, want in (("omega", omega, shape), ("theta", theta, shape), ("phi", phi, shape), ("mask", mask, shape),
+                          ("chain_breaks", chain_breaks, shape[:2]), ("lengths", lengths, shape[:1])):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{name} must have shape {want} to match d_cb {shape}, got {tuple(t.shape)}")
+    check_distmat_size(shape[0], shape[1])
+
+
+def check_distmat_size(B: int, L: int) -> None:
+    """The size limits of the K8 / K9 launches (a grid dimension per structure, 32-bit offsets in a structure)."""
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if 9 * L ** 2 >= 2 ** 31:
+        raise ValueError(f"L = {L} is too long (9 L^2 must stay below 2^31)")
+
+
+def _i32c(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _require_device(t, name)
+    return t.to(torch.int32).contiguous()
+
+
+def backbone_distmat_init(d_cb: torch.Tensor, omega: torch.Tensor, theta: torch.Tensor, phi: torch.Tensor,
+                          mask: Optional[torch.Tensor] = None, chain_breaks: Optional[torch.Tensor] = None,
+                          lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K8.  Steps 1-6 of the distance-matrix reconstruction: (B,L,L) d_cb / omega (trRosetta) / theta / phi, optional
+    (B,L,L) pair ``mask``, (B,L) ``chain_breaks`` (chain ends after residue i) and (B,) ``lengths`` -> the (B,3,3,L,L)
+    N / CA / C distance planes with MASK for unknown entries (include/protstruc_hip.h)."""
+    check_distmat_shapes(d_cb, omega, theta, phi, mask, chain_breaks, lengths)
+    d = _f32c(d_cb, "d_cb")
+    _same_device(d, omega=omega, theta=theta, phi=phi, mask=mask, chain_breaks=chain_breaks, lengths=lengths)
+    om, th, ph = _f32c(omega, "omega"), _f32c(theta, "theta"), _f32c(phi, "phi")
+    m, brk, lens = _u8c(mask, "mask"), _u8c(chain_breaks, "chain_breaks"), _i32c(lengths, "lengths")
+    B, L = d.shape[:2]
+    dev = d.device
+    with _on(dev):
+        out = torch.empty(B, 3, 3, L, L, dtype=torch.float32, device=dev)
+        rc = 0
+        if not (B == 0 or L == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            rc = _lib.load().ps_backbone_distmat_init_f32(_ptr(d), _ptr(om), _ptr(th), _ptr(ph), _ptr(m), _ptr(brk),
+                                                          _ptr(lens), _ptr(out), B, L, _stream(d))
+    _lib.check(rc, "ps_backbone_distmat_init_f32")
+    return out
+
+
+def check_floyd_warshall_shape(D, G: int = 1) -> Tuple[int, int]:
+    """(B, L) of a Floyd-Warshall operand: (B,L,L) for G = 1, (B,G,G,L,L) for any G; ValueError otherwise."""
+    shape = tuple(D.shape)
+    if G < 1:
+        raise ValueError(f"G must be >= 1, got {G}")
+    if len(shape) == 5 and shape[1] == shape[2] == G and shape[3] == shape[4]:
+        B, L = shape[0], shape[3]
+    elif G == 1 and len(shape) == 3 and shape[1] == shape[2]:
+        B, L = shape[0], shape[1]
+    else:
+        raise ValueError(f"D must have shape (batch, {G}, {G}, L, L)" + (" or (batch, L, L)" if G == 1 else "") +
+                         f", got {shape}")
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if (G * L) ** 2 >= 2 ** 31:
+        raise ValueError(f"{G * L} nodes are too many ((G L)^2 must stay below 2^31)")
+    return B, L
+
+
+def floyd_warshall_(D: torch.Tensor, G: int = 1) -> torch.Tensor:
+    """K9.  All-pairs shortest paths in place, by the reference's rule D[r][c] = min(D[r][c], D[k][r] + D[k][c]) for
+    k = 0 .. n-1 over the n = G L nodes (g, i) = g L + i of a contiguous float32 (B,G,G,L,L) tensor ((B,L,L) for G = 1).
+    Bit for bit the sequential float32 loop when every entry is >= 0 and not NaN.  The workspace comes from torch's
+    allocator on the current stream, so the call can be captured in a graph."""
+    B, L = check_floyd_warshall_shape(D, G)
+    _require_device(D, "D")
+    if D.dtype != torch.float32 or not D.is_contiguous():
+        raise ValueError("D must be a contiguous float32 tensor (it is updated in place)")
+    lib = _lib.load()
+    dev = D.device
+    with _on(dev):
+        rc = 0
+        if not (B == 0 or L == 0):
+            nbytes = lib.ps_floyd_warshall_workspace_bytes(B, G, L)
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            rc = lib.ps_floyd_warshall_f32(_ptr(D), B, G, L, _ptr(ws), nbytes, _stream(D))
+    _lib.check(rc, "ps_floyd_warshall_f32")
+    return D
+
+
+def backbone_distmat_finish_(D: torch.Tensor, chain_breaks: Optional[torch.Tensor] = None,
+                             lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Steps 8-9 in place on a (B,3,3,L,L) float32 tensor: (D + D^T) / 2 over the 3 L nodes, the bonds again (none
+    across a chain break) and NaN for residues at or beyond ``lengths``."""
+    B, L = check_floyd_warshall_shape(D, 3)
+    for name, t, want in (("chain_breaks", chain_breaks, (B, L)), ("lengths", lengths, (B,))):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
+    _require_device(D, "D")
+    if D.dtype != torch.float32 or not D.is_contiguous():
+        raise ValueError("D must be a contiguous float32 tensor (it is updated in place)")
+    _same_device(D, chain_breaks=chain_breaks, lengths=lengths)
+    brk, lens = _u8c(chain_breaks, "chain_breaks"), _i32c(lengths, "lengths")
+    dev = D.device
+    with _on(dev):
+        rc = 0
+        if not (B == 0 or L == 0):
+            rc = _lib.load().ps_backbone_distmat_finish_f32(_ptr(D), _ptr(brk), _ptr(lens), B, L, _stream(D))
+    _lib.check(rc, "ps_backbone_distmat_finish_f32")
+    return D
+
 def frames(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *, want_rot: bool = True,
            want_trans: bool = True):
     """K4.  Returns (rot (B,N,3,3) or None, trans (B,N,3) or None)."""

@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 7
+#define PS_ABI_VERSION 8
 int ps_abi_version(void);
 
 /* 0 for the product library.  1 for builds made with -DPS_EXPERIMENTS (tools/ only), which contain timing
@@ -451,6 +451,38 @@ long long ps_floyd_warshall_workspace_bytes(int B, int G, int L);
 int ps_floyd_warshall_f32(float* D, int B, int G, int L, void* workspace, long long workspace_bytes, void* stream);
 int ps_backbone_distmat_finish_f32(float* D, const uint8_t* chain_breaks, const int* lengths, int B, int L,
                                    void* stream);
+
+/*
+ * K10 / K11 (ABI 8) -- backbone coordinates from a distance matrix, behind geometry.initialize_backbone_with_mds
+ * (reference geometry.py:350-410).
+ *
+ * ps_smacof_f32 (K10): metric SMACOF (sklearn 1.7's smacof) on D (B,G,G,L,L) fp32, node (g, i) = g * L + i as in
+ * ps_floyd_warshall_f32 (G = 3: a reconstructed distance matrix; G = 1: a plain (B,L,L) matrix), read in place.  With
+ * lengths (B) int32 (NULL: L) only nodes with i < lengths[b] take part: n = G lengths[b].  K starts per structure,
+ * init (B,K,G L,3) fp32 (entries of padded nodes are not read).  Per start, for t = 0, 1, ...:
+ *   d~_ij = |x_i - x_j| (1e-5 where exactly 0),  x_i <- (1/n) sum_j (D_ij / d~_ij)(x_i - x_j)  (the Guttman transform),
+ *   sigma_{t+1} = 1/2 sum_ij (d_ij - D_ij)^2,  S_{t+1} = sum_ij d_ij^2  (of the new x; float64 sums),
+ * stopping after X^{t+1} when t >= 1 and (sigma_t - sigma_{t+1}) / (S_{t+1} / 2) < eps, or at t + 1 = max_iter.  The
+ * start with the smallest final sigma wins (the lowest index on ties; a NaN stress never replaces an earlier start):
+ * X_out (B,G L,3) fp32 (NaN for padded nodes), stress_out (B) float64, n_iter_out (B) int32.  A structure of length 0
+ * gives stress 0, n_iter 0.  Issues max_iter + 2 launches on `stream` whatever the convergence (the ones after it are
+ * no-ops): capturable, bitwise deterministic.  workspace: at least ps_smacof_workspace_bytes(B, K, G, L) bytes of device
+ * memory, 8-byte aligned, overwritten.  Requires B <= 65535, K >= 1, max_iter >= 1, eps >= 0, (G L)^2 < 2^31 and
+ * B K G L 3 < 2^31.
+ *
+ * ps_mds_backbone_finish_f32 (K11): X (B,3,L,3) fp32 (N, CA, C) -> out (B,n_atoms_out,L,3), n_atoms_out = 3 (N, CA, C)
+ * or 5 (N, CA, C, O, CB).  mirror_mode 1: z is negated iff the mean of phi_i = dihedral(C_{i-1}, N_i, CA_i, C_i) over
+ * i = 1 .. len-1 is positive (the reference's documented intent; its code mirrors unconditionally); 0: never.  Then
+ * CB = place(C, N, CA, 1.522, 1.927, -2.143) and O = place(N_{(i+1) mod len}, CA, C, 1.231, 2.108, -3.142) (place = mode 3
+ * of ps_pointwise_f32; the wrap at the last residue is the reference's np.roll).  Residues i >= lengths[b] are NaN; a
+ * NaN anywhere in a structure's first lengths[b] residues makes that structure's whole output NaN.
+ */
+long long ps_smacof_workspace_bytes(int B, int K, int G, int L);
+int ps_smacof_f32(const float* D, int B, int G, int L, const int* lengths, const float* init, int K, int max_iter,
+                  double eps, float* X_out, double* stress_out, int* n_iter_out, void* workspace, long long workspace_bytes,
+                  void* stream);
+int ps_mds_backbone_finish_f32(const float* X, const int* lengths, int B, int L, int mirror_mode, int n_atoms_out,
+                               float* out, void* stream);
 
 /*
  * Batched Kabsch fit -- replaces the per-structure loop of StructureBatch.align and

@@ -10,7 +10,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROTSTRUC_AMD_LIB selects another build of the same sources (tools/ use the -DPS_EXPERIMENTS one)
 LIB_PATH = os.environ.get("PROTSTRUC_AMD_LIB") or os.path.join(_HERE, "lib", "libprotstruc_hip.so")
-EXPECTED_ABI = 7  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
+EXPECTED_ABI = 8  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
 
 
 class K1Config(ctypes.Structure):
@@ -81,6 +81,10 @@ SIGNATURES = {
     "ps_floyd_warshall_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "ps_floyd_warshall_f32": (_c_int, [_c_f32p, _c_int, _c_int, _c_int, ctypes.c_void_p, ctypes.c_longlong, _c_stream]),
     "ps_backbone_distmat_finish_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, _c_int, _c_int, _c_stream]),
+    "ps_smacof_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int, _c_int]),
+    "ps_smacof_f32": (_c_int, [_c_f32p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_f32p, _c_int, _c_int, ctypes.c_double,
+                               _c_f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, _c_stream]),
+    "ps_mds_backbone_finish_f32": (_c_int, [_c_f32p, ctypes.c_void_p, _c_int, _c_int, _c_int, _c_int, _c_f32p, _c_stream]),
     "ps_kabsch_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_min_dist_to_points_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_standardize_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),

@@ -3,7 +3,8 @@
 ``angle``, ``dihedral``, ``gram_schmidt`` and ``place_fourth_atom`` evaluate in the same HIP device
 functions the batch kernels use (csrc/ps_common.hpp) through a point-wise
 launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
-``reconstruct_backbone_distmat_from_interresidue_geometry`` runs the distance-matrix kernels (csrc/distmat.hip).
+``reconstruct_backbone_distmat_from_interresidue_geometry`` runs the distance-matrix kernels (csrc/distmat.hip);
+``initialize_backbone_with_mds`` and ``fix_chirality`` the SMACOF and finishing kernels (csrc/mds.hip).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -217,4 +218,77 @@ def reconstruct_backbone_distmat_from_interresidue_geometry(d_cb, omega, theta, 
     out = ops.backbone_distmat_init(d_cb, omega, theta, phi, mask, breaks, lengths)
     ops.floyd_warshall_(out, G=3)
     ops.backbone_distmat_finish_(out, breaks, lengths)
+    return _finish(out if batched else out[0], ft)
+
+
+def _lengths_array(lengths, B: int, L: int):
+    if lengths is None:
+        return None
+    if isinstance(lengths, (int, np.integer)):
+        lengths = [int(lengths)]
+    if isinstance(lengths, torch.Tensor):
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+        lengths = lengths.cpu().numpy()
+    lengths = np.asarray(lengths, dtype=np.int64)
+    if lengths.shape != (B,) or (lengths < 0).any() or (lengths > L).any():
+        raise ValueError(f"lengths must be {B} integers in 0 .. {L}, got {lengths.tolist()}")
+    return lengths
+
+
+def initialize_backbone_with_mds(dist_mat, max_iter: int = 500, *, n_init: int = 4, eps: float = 1e-6,
+                                 random_state=None, init=None, lengths=None):
+    """Backbone coordinates from an N / CA / C distance matrix by metric MDS (reference geometry.py:350-386).
+
+    ``dist_mat`` (3, 3, L, L) -> (5, L, 3), or (B, 3, 3, L, L) -> (B, 5, L, 3), atoms N, CA, C, O, CB.  SMACOF as
+    sklearn 1.7's ``MDS(3, max_iter=max_iter, dissimilarity="precomputed")`` runs it (``n_init`` = 4 random starts,
+    ``eps`` = 1e-6) over the 3 L atoms; the starts are sklearn's draws from ``random_state`` (None: numpy's global
+    state, as in the reference, so ``np.random.seed(s)`` before the call reproduces its starts).  ``init`` ((K, 3 L, 3)
+    or (B, K, 3 L, 3), node g L + i = atom g of residue i) gives K explicit starts instead -- an extension: sklearn runs
+    a single start when given one.  The best start is mirrored (z negated) iff its mean backbone phi is positive -- the
+    reference's documented intent; its code mirrors unconditionally, which returns the wrong hand about half the time
+    -- and CB and O are placed at ideal geometry; O of the last residue is placed from N of the first residue (the
+    reference's np.roll).  ``lengths`` (B,) pads a ragged batch: residues at or beyond a structure's length do not take
+    part and come back NaN.  A NaN distance inside a structure makes that structure's result all NaN.
+
+    numpy in -> numpy out, tensor in -> tensor out (on the GPU); float32 coordinates, float64 stress sums."""
+    if not isinstance(dist_mat, (torch.Tensor, np.ndarray)):
+        raise TypeError("dist_mat must be a tensor or an ndarray")
+    shape = tuple(dist_mat.shape)
+    if len(shape) not in (4, 5) or shape[-4:-2] != (3, 3) or shape[-1] != shape[-2]:
+        raise ValueError(f"dist_mat must have shape (3, 3, L, L) or (B, 3, 3, L, L), got {shape}")
+    batched = len(shape) == 5
+    B, L = (shape[0] if batched else 1), shape[-1]
+    lens = _lengths_array(lengths, B, L)
+    args = [dist_mat] + ([init] if init is not None else [])
+    prepped, ft = _prep(args)
+    D = prepped[0].reshape(B, 3, 3, L, L)
+    x0 = None
+    if init is not None:
+        x0 = prepped[1]
+        if not batched:
+            x0 = x0.unsqueeze(0)
+    lens_t = None if lens is None else torch.from_numpy(lens.astype(np.int32)).to(D.device)
+    X, _, _ = ops.smacof(D, 3, n_init=None if init is not None else n_init, max_iter=max_iter, eps=eps, init=x0,
+                         random_state=random_state, lengths=lens)
+    out = ops.mds_backbone_finish(X.reshape(B, 3, L, 3), lens_t, mirror=True, place_o_cb=True)
+    return _finish(out if batched else out[0], ft)
+
+
+def fix_chirality(coords, lengths=None):
+    """N / CA / C coordinates (3, L, 3) or (B, 3, L, 3), mirrored (z negated) iff the mean of the backbone phi
+    dihedrals (C_{i-1}, N_i, CA_i, C_i), i = 1 .. L-1, is positive (reference geometry.py:389-410, as its docstring and
+    commented-out test intend; its code mirrors unconditionally).  Evaluated by the same kernel as
+    ``initialize_backbone_with_mds``; an unmirrored structure comes back bit for bit.  numpy in -> numpy out."""
+    if not isinstance(coords, (torch.Tensor, np.ndarray)):
+        raise TypeError("coords must be a tensor or an ndarray")
+    shape = tuple(coords.shape)
+    if len(shape) not in (3, 4) or shape[-3] != 3 or shape[-1] != 3:
+        raise ValueError(f"coords must have shape (3, L, 3) or (B, 3, L, 3), got {shape}")
+    batched = len(shape) == 4
+    B, L = (shape[0] if batched else 1), shape[-2]
+    lens = _lengths_array(lengths, B, L)
+    (x,), ft = _prep([coords])
+    lens_t = None if lens is None else torch.from_numpy(lens.astype(np.int32)).to(x.device)
+    out = ops.mds_backbone_finish(x.reshape(B, 3, L, 3), lens_t, mirror=True, place_o_cb=False)
     return _finish(out if batched else out[0], ft)

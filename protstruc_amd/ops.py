@@ -13,6 +13,7 @@ import threading
 import time
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -660,6 +661,143 @@ def backbone_distmat_finish_(D: torch.Tensor, chain_breaks: Optional[torch.Tenso
             rc = _lib.load().ps_backbone_distmat_finish_f32(_ptr(D), _ptr(brk), _ptr(lens), B, L, _stream(D))
     _lib.check(rc, "ps_backbone_distmat_finish_f32")
     return D
+
+def check_smacof_shapes(D, G: int = 1, n_init: Optional[int] = None, max_iter: int = 300, eps: float = 1e-6, init=None,
+                        lengths=None) -> Tuple[int, int, int]:
+    """Argument rules of ``smacof`` on shapes and values only (no device, no launch): (B, L, K) or ValueError."""
+    B, L = check_floyd_warshall_shape(D, G)
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError(f"max_iter must be an integer >= 1, got {max_iter!r}")
+    if not eps >= 0:
+        raise ValueError(f"eps must be >= 0, got {eps!r}")
+    if n_init is not None and (isinstance(n_init, bool) or not isinstance(n_init, int) or n_init < 1):
+        raise ValueError(f"n_init must be an integer >= 1, got {n_init!r}")
+    if init is not None:
+        shape = tuple(init.shape)
+        if len(shape) != 4 or shape[0] != B or shape[2] != G * L or shape[3] != 3:
+            raise ValueError(f"init must have shape ({B}, n_init, {G * L}, 3), got {shape}")
+        if n_init is not None and shape[1] != n_init:
+            raise ValueError(f"init holds {shape[1]} starts, n_init = {n_init}")
+        K = shape[1]
+        if K < 1:
+            raise ValueError("init must hold at least one start")
+    else:
+        K = 4 if n_init is None else n_init
+    if lengths is not None:
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+        if isinstance(lengths, np.ndarray) and lengths.size and (lengths.min() < 0 or lengths.max() > L):
+            raise ValueError(f"lengths must lie in 0 .. {L}, got {lengths.tolist()}")
+    if K > 65535 or B * K * G * L * 3 >= 2 ** 31:
+        raise ValueError(f"{B} x {K} starts of {G * L} nodes are too many for one call")
+    return B, L, K
+
+
+def _check_random_state(random_state):
+    """sklearn.utils.check_random_state: None -> numpy's global RandomState, an int -> a new RandomState(seed), a
+    RandomState -> itself."""
+    if random_state is None or random_state is np.random:
+        return np.random.mtrand._rand
+    if isinstance(random_state, (int, np.integer)) and not isinstance(random_state, bool):
+        return np.random.RandomState(random_state)
+    if isinstance(random_state, np.random.RandomState):
+        return random_state
+    raise ValueError(f"{random_state!r} cannot be used to seed a numpy.random.RandomState instance")
+
+
+def smacof_random_starts(B: int, K: int, G: int, L: int, lengths=None, random_state=None) -> np.ndarray:
+    """sklearn's random SMACOF starts: for structure b = 0 .. B-1 and start k = 0 .. K-1 in turn,
+    ``random_state.uniform(size=3 n)`` with n = G lengths[b], as (n, 3) rows, placed at nodes (g, i) = g L + i with
+    i < lengths[b].  Returns (B, K, G L, 3) float64 (0 at padded nodes); host work only."""
+    rs = _check_random_state(random_state)
+    out = np.zeros((B, K, G, L, 3), dtype=np.float64)
+    for b in range(B):
+        ln = L if lengths is None else int(lengths[b])
+        for k in range(K):
+            out[b, k, :, :ln] = rs.uniform(size=3 * G * ln).reshape(G, ln, 3)
+    return out.reshape(B, K, G * L, 3)
+
+
+def smacof(D: torch.Tensor, G: int = 1, *, n_init: Optional[int] = None, max_iter: int = 300, eps: float = 1e-6,
+           init: Optional[torch.Tensor] = None, random_state=None, lengths=None):
+    """K10.  Metric SMACOF (sklearn 1.7's ``smacof``) on the n = G L nodes (g, i) = g L + i of a float32 (B,G,G,L,L)
+    dissimilarity tensor ((B,L,L) for G = 1) on the GPU: returns (X (B, G L, 3) float32, stress (B,) float64, n_iter (B,)
+    int32) of the best of K starts (include/protstruc_hip.h).
+
+    Starts: ``init`` (B, K, G L, 3) on D's device -- K explicit starts, an extension (sklearn runs one start when given
+    ``init``) -- or K = ``n_init`` (default 4) random ones drawn on the host exactly as sklearn draws them from
+    ``random_state`` (None: numpy's global state; see ``smacof_random_starts``).  ``lengths`` (B,) restricts structure
+    b to the nodes i < lengths[b]; padded rows of X are NaN.  Without ``random_state`` draws the call is capturable."""
+    if lengths is not None and not isinstance(lengths, torch.Tensor):
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    B, L, K = check_smacof_shapes(D, G, n_init, max_iter, eps, init, lengths)
+    if random_state is not None and init is not None:
+        raise ValueError("random_state draws starts; it cannot be combined with an explicit init")
+    _require_device(D, "D")
+    dev = D.device
+    d = _f32c(D, "D")
+    if init is None:
+        lens_host = None if lengths is None else (lengths.cpu().numpy() if isinstance(lengths, torch.Tensor) else lengths)
+        if lens_host is not None and lens_host.size and (lens_host.min() < 0 or lens_host.max() > L):
+            raise ValueError(f"lengths must lie in 0 .. {L}, got {lens_host.tolist()}")
+        starts = smacof_random_starts(B, K, G, L, lens_host, random_state)
+        x0 = torch.from_numpy(starts.astype(np.float32)).to(dev)
+    else:
+        _same_device(d, init=init)
+        x0 = _f32c(init, "init")
+    if lengths is not None:
+        lens = _i32c(lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(lengths).to(dev), "lengths")
+        _same_device(d, lengths=lens)
+    else:
+        lens = None
+    lib = _lib.load()
+    with _on(dev):
+        X = torch.empty(B, G * L, 3, dtype=torch.float32, device=dev)
+        stress = torch.empty(B, dtype=torch.float64, device=dev)
+        n_iter = torch.empty(B, dtype=torch.int32, device=dev)
+        rc = 0
+        if B > 0:
+            nbytes = lib.ps_smacof_workspace_bytes(B, K, G, L)
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+            rc = lib.ps_smacof_f32(_ptr(d), B, G, L, _ptr(lens), _ptr(x0), K, max_iter, float(eps), _ptr(X),
+                                   _ptr(stress), _ptr(n_iter), _ptr(ws), ws.numel() * 8, _stream(d))
+    _lib.check(rc, "ps_smacof_f32")
+    return X, stress, n_iter
+
+
+def check_backbone_coords_shape(X, n_atoms: int = 3) -> Tuple[int, int]:
+    """(B, L) of (B, n_atoms, L, 3) backbone coordinates; ValueError otherwise."""
+    shape = tuple(X.shape)
+    if len(shape) != 4 or shape[1] != n_atoms or shape[3] != 3:
+        raise ValueError(f"coordinates must have shape (batch, {n_atoms}, L, 3), got {shape}")
+    if shape[0] > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {shape[0]}")
+    return shape[0], shape[2]
+
+
+def mds_backbone_finish(X: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, mirror: bool = True,
+                        place_o_cb: bool = True) -> torch.Tensor:
+    """K11.  (B,3,L,3) N / CA / C coordinates (an MDS result reshaped) -> (B,5,L,3) N, CA, C, O, CB (``place_o_cb``) or
+    (B,3,L,3) N, CA, C.  With ``mirror`` z is negated where the mean backbone phi is positive (the hand a protein does
+    not have); ``mirror=False`` never mirrors.  O of the last residue is placed from N of the first (the reference's
+    np.roll).  Padded residues (``lengths``) are NaN; a NaN in a structure makes its whole output NaN."""
+    B, L = check_backbone_coords_shape(X, 3)
+    if lengths is not None and tuple(lengths.shape) != (B,):
+        raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    x = _f32c(X, "X")
+    _same_device(x, lengths=lengths)
+    lens = _i32c(lengths, "lengths")
+    A = 5 if place_o_cb else 3
+    dev = x.device
+    with _on(dev):
+        out = torch.empty(B, A, L, 3, dtype=torch.float32, device=dev)
+        rc = 0
+        if not (B == 0 or L == 0):
+            rc = _lib.load().ps_mds_backbone_finish_f32(_ptr(x), _ptr(lens), B, L, 1 if mirror else 0, A, _ptr(out),
+                                                       _stream(x))
+    _lib.check(rc, "ps_mds_backbone_finish_f32")
+    return out
+
 
 def frames(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *, want_rot: bool = True,
            want_trans: bool = True):

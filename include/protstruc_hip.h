@@ -40,8 +40,8 @@ extern "C" {
 #define PS_ABI_VERSION 8
 int ps_abi_version(void);
 
-/* 0 for the product library.  1 for builds made with -DPS_EXPERIMENTS (tools/ only), which contain timing
- * experiments that can write wrong values; those are unreachable -- not compiled -- in the product build. */
+/* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
+ * with experiments that could write wrong values, which returned 1.) */
 int ps_has_experiments(void);
 
 /* Human-readable text for a code returned by any ps_* function. */
@@ -63,8 +63,8 @@ const char* ps_error_string(int code);
  *   them and the defaults (0) are the product:
  *       variant = 1 (the simple kernels everywhere: the cross-check of the parity tests), flat = 0 / 2 / 4 and
  *       rowphase = 1 / 2 (force or forbid a kernel family; + 16: an A/B switch of the row-phase kernel), store_nt = 1 (non-temporal stores: slower),
- *       flat_fl_log2 = 4 / 5 (the small granules of round 3's bounded A/B), experiment (must be 0: refused by the
- *       product library).
+ *       flat_fl_log2 = 4 / 5 (the small granules of round 3's bounded A/B).
+ *   RESERVED -- experiment: must be 0, any other value is refused.
  */
 typedef struct ps_k1_config {
     int struct_size;      /* = sizeof(ps_k1_config); a launcher refuses any other value (caller built against another header) */
@@ -94,9 +94,8 @@ typedef struct ps_k1_config {
                              residues; 2 <= A <= 16 up to 7..64 residues; full matrices): they take the two flat kernels; 1 also for A = 14, 15, 16, 24, 32 and
                              for those CA traces (A/B runs); 2 never (fixed-A flat / element kernels instead).  Bits 4..7 (value / 16) are A/B
                              switches of that kernel: 16 = the A = 1 seam slots written element-wise from both rows (round 3) */
-    int experiment;       /* [diagnostic] must be 0 in the product library; timing experiments exist only in builds made with
-                             -DPS_EXPERIMENTS (tools/), where 1 = first correctly rounded sqrt routine, 2 = store-only
-                             run that writes WRONG values, +16 = fully unrolled group loop */
+    int experiment;       /* [reserved] must be 0; a launcher refuses any other value (the field selected timing experiments in a
+                             tools-only build that no longer exists, and keeps its place for the layout) */
 } ps_k1_config;
 
 /* Fills *cfg with the defaults listed above (struct_size included). */

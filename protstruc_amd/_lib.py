@@ -8,7 +8,7 @@ import os
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# PROTSTRUC_AMD_LIB selects another build of the same sources (tools/ use the -DPS_EXPERIMENTS one)
+# PROTSTRUC_AMD_LIB selects another build of the library: the same-process A/B of two builds (tools/k1_ab_libs.py)
 LIB_PATH = os.environ.get("PROTSTRUC_AMD_LIB") or os.path.join(_HERE, "lib", "libprotstruc_hip.so")
 EXPECTED_ABI = 8  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
 
@@ -302,8 +302,7 @@ def set_tuning(key, value, device=None):
             or (key == "k1_flat_fl_log2" and value in (1, 2, 3)) or (key == "k1_flat" and value == 3):
         raise HipLibraryError(f"tuning value {key}={value} outside its range")
     if key == "k1_experiment" and value and not load().ps_has_experiments():
-        raise HipLibraryError("timing experiments are not compiled into the product library "
-                              "(build with `python -m protstruc_amd.build --experiments` and set PROTSTRUC_AMD_LIB)")
+        raise HipLibraryError("k1_experiment is reserved and must be 0: the product library contains no timing experiments")
     with _k1_lock:
         idx = _device_index(device)
         _k1_entry(idx)[field] = value

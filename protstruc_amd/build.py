@@ -16,9 +16,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_hip.so")
-# tools/ only: the same sources with -DPS_EXPERIMENTS (store-only and other timing modes that can write wrong
-# values).  Never loaded by the package unless PROTSTRUC_AMD_LIB points at it explicitly.
-EXPERIMENTS_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_hip_experiments.so")
 # the multi-GPU exchange step lives in its own library so that libprotstruc_hip.so has no RCCL dependency
 RCCL_SRC_DIR = os.path.join(HERE, "csrc_rccl")
 RCCL_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_rccl.so")
@@ -36,9 +33,9 @@ def _deps():
         [os.path.join(HERE, "..", "include", "protstruc_hip.h")]
 
 
-def source_hash(experiments=False):
+def source_hash():
     """Digest of everything the library is compiled from (file names, contents, flags)."""
-    h = hashlib.sha256((" ".join(FLAGS) + (" -DPS_EXPERIMENTS" if experiments else "")).encode())
+    h = hashlib.sha256(" ".join(FLAGS).encode())
     for d in _deps():
         h.update(os.path.basename(d).encode())
         with open(d, "rb") as f:
@@ -58,20 +55,20 @@ def is_stale(path=None):
             recorded = f.read().strip()
     except OSError:
         return True
-    return recorded != source_hash(experiments=(os.path.abspath(path) == os.path.abspath(EXPERIMENTS_LIB_PATH)))
+    return recorded != source_hash()
 
 
-def build(force=False, verbose=True, experiments=False):
-    out = EXPERIMENTS_LIB_PATH if experiments else LIB_PATH
+def build(force=False, verbose=True):
+    out = LIB_PATH
     if not force and not is_stale(out):
         return out
     os.makedirs(LIB_DIR, exist_ok=True)
     tmp = f"{out}.{os.getpid()}.tmp"  # build aside and rename: concurrent builders (one per rank) cannot corrupt the .so
-    cmd = [HIPCC] + FLAGS + (["-DPS_EXPERIMENTS"] if experiments else []) + ["-o", tmp] + sources()
+    cmd = [HIPCC] + FLAGS + ["-o", tmp] + sources()
     if verbose:
         print("[protstruc_amd.build]", " ".join(cmd), flush=True)
     try:
-        digest = source_hash(experiments)
+        digest = source_hash()
         subprocess.run(cmd, check=True)
         os.replace(tmp, out)
         with open(out + ".srchash", "w") as f:
@@ -149,6 +146,6 @@ def build_c_example(verbose=True):
 
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    print(build(force=force, experiments="--experiments" in sys.argv))
+    print(build(force=force))
     print(build_rccl(force=force))
     print(build_c_example())

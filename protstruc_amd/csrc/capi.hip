@@ -17,12 +17,6 @@ extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }
 
-// 1 when the library was built with -DPS_EXPERIMENTS (timing experiments that can write wrong values); the product
-// build returns 0 and refuses any ps_k1_config with experiment != 0.
-extern "C" int ps_has_experiments(void) {
-#ifdef PS_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
+// Always 0: the library contains no timing experiments (the builds that had them are retired; the symbol stays for the ABI)
+// and refuses any ps_k1_config with experiment != 0.
+extern "C" int ps_has_experiments(void) { return 0; }

@@ -29,7 +29,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <type_traits>
@@ -98,14 +97,6 @@ constexpr bool K3_FAITHFUL_NC4(int, int) { return true; }
 // threads of a full-width sweep workgroup: four waves per SIMD with 128 VGPRs each -- two with 256 for the faithful chains at
 // four columns per lane (the library-order chains keep ~2x the values live)
 constexpr int k3_sweep_threads(int NC, bool FAITHFUL) { return FAITHFUL && NC == 4 ? 512 : 1024; }
-#ifdef PS_K3_AB
-// tools only (tools/k3f_probe.py): 2 = every K3 / featuriser kernel computes but stores out of range (the arithmetic and the store
-// issue alone); 1 = k3_featurise_tiles stores constants instead of computing (the store pattern alone)
-__device__ int k3f_probe;
-#define K3_PROBE_RECORDS(n) (k3f_probe == 2 ? 0u : (unsigned)(n))
-#else
-#define K3_PROBE_RECORDS(n) (n)
-#endif
 constexpr size_t K3_LDS_MAX = 160 * 1024 - 256;   // the most dynamic LDS a workgroup of the sweep kernels asks for
 constexpr size_t K3_LDS_ONE_PER_CU = 80 * 1024;   // with its few static bytes on top, two such workgroups do not fit a CU
 constexpr size_t K3_LDS_TWO_PER_CU = 80 * 1024 - 256;   // exactly two such workgroups fit a CU (three would need 240 KB)
@@ -313,7 +304,7 @@ __global__ __launch_bounds__(1024) void k3_flat(const float* __restrict__ xyz, f
             const k3_f32x4* slot = k3_flatbuf + (size_t)(b - bs) * slot_vec4;
             const k3_f32x4* rowp = slot + col_vec4;
             float* obase = out + ((size_t)b * out_rows + (size_t)(row_begin - out_row_origin)) * N;
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, (int)K3_PROBE_RECORDS(rows * N * 4), 0x00020000u);   // this structure's rows, exactly
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, (int)(rows * N * 4), 0x00020000u);   // this structure's rows, exactly
             // the lane's tile: two row pairs x two adjacent columns (four chains) -- or, where a row of FOUR columns is one aligned
             // 16-byte store (vec == 4: N % 4 == 0), two such halves that share the index arithmetic and the row-side points
             // (N = 64 .. 220: 58-65 / 60-66 / 43-50 us per 2^25 pairs against 62-73 / 68-79 / 48-59; without the wide store the
@@ -494,19 +485,6 @@ _Pragma("unroll")                                                               
                 }                                                                                                        \
             }                                                                                                            \
     }
-#ifdef PS_K3_AB
-// tools only (-DPS_K3_AB): per wave of the last k3_sweep launch, the 100 MHz wall clock at entry, after the first staging
-// barrier, after the wave's first task, after its last task (tools/k3_stamps.py; DESIGN.md section 4, "where K3's time goes")
-__device__ unsigned long long k3_stamps[512 * 16 * 4];
-#define K3_STAMP(slot) if (lane == 0 && blockIdx.x < 512) k3_stamps[((size_t)blockIdx.x * 16 + wave) * 4 + (slot)] = wall_clock64()
-// ... and of the last k3_featurise_tiles launch: entry, then per staging pass (the first five): pass begun (after the top
-// barrier), rows staged (after the second barrier), this wave's last task of the pass done (tools/k3f_stamps.py)
-__device__ unsigned long long k3f_stamps[512 * 8 * 16];
-#define K3F_STAMP(slot) if (lane == 0 && blockIdx.x < 512 && (slot) < 16) k3f_stamps[((size_t)blockIdx.x * 8 + wave) * 16 + (slot)] = wall_clock64()
-#else
-#define K3_STAMP(slot)
-#define K3F_STAMP(slot)
-#endif
 
 template <int NP, int SRC, int NC, bool VEC, bool FAITHFUL = false>
 __global__ __launch_bounds__(k3_sweep_threads(NC, FAITHFUL)) void k3_sweep(const float* __restrict__ xyz, float* __restrict__ out, int N, int A,
@@ -523,7 +501,6 @@ __global__ __launch_bounds__(k3_sweep_threads(NC, FAITHFUL)) void k3_sweep(const
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int n_waves = (int)(blockDim.x >> 6);
     const unsigned t0 = blockIdx.x * tasks_per_wg, t1 = min(t0 + tasks_per_wg, n_tasks);
-    K3_STAMP(0);
     if (t0 >= t1) return;                         // whole workgroup
     int amap[NPIq];
     {
@@ -573,10 +550,9 @@ __global__ __launch_bounds__(k3_sweep_threads(NC, FAITHFUL)) void k3_sweep(const
         }
         if (threadIdx.x == 0) next_task = (unsigned)(c_lo + n_waves);   // the first n_waves tasks are pre-assigned
         __syncthreads();
-        K3_STAMP(1);
         // the segment's rows as one buffer: uniform base, the lane's constant byte offset, the row's byte offset as a scalar
         float* obase = out + ((size_t)b * out_rows + (size_t)(r_lo - out_row_origin)) * N;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, K3_PROBE_RECORDS(0xFFFFFFFFu), 0x00020000u);
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, 0xFFFFFFFFu, 0x00020000u);
         const int lane_off = j0 * 4;
         auto rows = [&](int r, f3v (&p)[NP]) {                    // r = row pair index inside the segment
             int q = 0;
@@ -607,14 +583,10 @@ __global__ __launch_bounds__(k3_sweep_threads(NC, FAITHFUL)) void k3_sweep(const
                 else if (NC == 4 && ncl == 2) K3_SWEEP_ROWS((NC == 4 ? 2 : 1))
                 else K3_SWEEP_ROWS(1)
             }
-#ifdef PS_K3_AB
-            if (c == c_lo + wave) { K3_STAMP(2); }
-#endif
             unsigned nx = 0;
             if (lane == 0) nx = atomicAdd(&next_task, 1u);
             c = __builtin_amdgcn_readfirstlane((int)nx);
         }
-        K3_STAMP(3);
     }
 }
 
@@ -850,7 +822,7 @@ __global__ __launch_bounds__((NC == 4 || FAITHFUL) ? 512 : 1024) void k3_featuri
             constexpr int r_lo = 0;
             const int r_hi = N;
             const size_t seg = (size_t)b * N * N, sbase = seg;
-            auto rs = [&](void* base) { return __builtin_amdgcn_make_buffer_rsrc(base, 0, K3_PROBE_RECORDS(0xFFFFFFFFu), 0x00020000u); };
+            auto rs = [&](void* base) { return __builtin_amdgcn_make_buffer_rsrc(base, 0, 0xFFFFFFFFu, 0x00020000u); };
             const __amdgpu_buffer_rsrc_t r_dca = rs(d_ca + seg), r_dcb = rs(d_cb + seg), r_dno = rs(d_no + seg), r_om = rs(omega + seg),
                                          r_th = rs(theta + seg), r_ph = rs(phi + seg);
             const __amdgpu_buffer_rsrc_t r_mca = rs(m_ca + sbase), r_mcb = rs(m_cb + sbase), r_mno = rs(m_no + sbase);
@@ -1138,12 +1110,9 @@ __global__ __launch_bounds__(512) void k3_featurise_tiles(
     const bool wide = vecf == 4;                  // (uniform)
     const unsigned TC = wide ? (unsigned)N >> 2 : (unsigned)(N + 1) >> 1, TR = (unsigned)(n_rp + 1) >> 1, FT = TR * TC;
     const unsigned b_first = t0 / tps, b_last = (t1 - 1u) / tps;
-    K3F_STAMP(0);
-    [[maybe_unused]] int pass = 0;
-    for (unsigned bs = b_first; bs <= b_last; bs += (unsigned)KS, ++pass) {
+    for (unsigned bs = b_first; bs <= b_last; bs += (unsigned)KS) {
         const unsigned ks = min((unsigned)KS, b_last - bs + 1u);
         __syncthreads();                                          // the previous pass's readers are done
-        K3F_STAMP(1 + 3 * pass);
         for (unsigned it = threadIdx.x; it < ks * (unsigned)N; it += blockDim.x) {   // one residue of one structure per thread
             unsigned sidx = __umulhi(it, rcpN), r = it - sidx * (unsigned)N;
             if (r >= (unsigned)N) ++sidx, r -= (unsigned)N;
@@ -1168,7 +1137,6 @@ __global__ __launch_bounds__(512) void k3_featurise_tiles(
         const unsigned seg_t0 = max(t0, bs * tps), seg_t1 = min(t1, (bs + ks) * tps);
         if (threadIdx.x == 0) next_task = seg_t0 + n_waves;       // the first n_waves tasks are pre-assigned
         __syncthreads();
-        K3F_STAMP(2 + 3 * pass);
         unsigned t = seg_t0 + (unsigned)wave;
         while (t < seg_t1) {
             const unsigned b = t / tps, chunk = t - b * tps;      // (uniform)
@@ -1182,11 +1150,7 @@ __global__ __launch_bounds__(512) void k3_featurise_tiles(
                                          r_om = rs(omega + sbase, fbytes), r_th = rs(theta + sbase, fbytes), r_ph = rs(phi + sbase, fbytes);
             const __amdgpu_buffer_rsrc_t r_mca = rs(m_ca + sbase, mbytes), r_mcb = rs(m_cb + sbase, mbytes), r_mno = rs(m_no + sbase, mbytes);
             const unsigned ti = chunk * 64u + (unsigned)lane;
-#ifdef PS_K3_AB
-            const bool lt = ti < FT && k3f_probe != 2;
-#else
             const bool lt = ti < FT;
-#endif
             const unsigned tcl = min(ti, FT - 1u);
             unsigned tr = __umulhi(tcl, rcpTC), tc = tcl - tr * TC;
             if (tc >= TC) ++tr, tc -= TC;
@@ -1288,13 +1252,6 @@ __global__ __launch_bounds__(512) void k3_featurise_tiles(
                 plane(r_mno, 0u, 2u);      // N_i & O_j
             }
             f32x2 v[4], w[4];
-#ifdef PS_K3_AB
-            const int probe = k3f_probe;
-            if (probe == 1) {
-                for (int c = 0; c < 4; ++c) v[c] = w[c] = f32x2{(float)lane, (float)c};
-                emit(r_dca, v, w); emit(r_dcb, v, w); emit(r_dno, v, w); emit(r_ph, v, w); emit(r_om, v, w); emit(r_th, v, w);
-            } else {
-#endif
             // each plane: the first half's four chains, the second half's (four-column tiles), the stores
 #define K3F_TILE_PLANE(RSRC, EXPR0, EXPR1)      \
             { EXPR0; if (wide) { EXPR1; } emit(RSRC, v, w); }
@@ -1313,14 +1270,10 @@ __global__ __launch_bounds__(512) void k3_featurise_tiles(
             }
 #undef K3F_DIST
 #undef K3F_TILE_PLANE
-#ifdef PS_K3_AB
-            }
-#endif
             unsigned nx = 0;
             if (lane == 0) nx = atomicAdd(&next_task, 1u);
             t = (unsigned)__builtin_amdgcn_readfirstlane((int)nx);
         }
-        K3F_STAMP(3 + 3 * pass);
     }
 }
 
@@ -1329,10 +1282,6 @@ __global__ __launch_bounds__(512) void k3_featurise_tiles(
 // `rows` rows gets about 64 tasks (N = 512: 8 rows per task, 256: 4, 128: 2; with one task per wave a 128-residue segment
 // ended when its slowest wave did: 61 -> 5x us at 2^25 pairs, profiles/r04_k3_shapes.log).  A task costs one LDS atomic.
 inline int k3_rows_per_task(int rows, int min_rows) {
-#ifdef PS_K3_AB
-    static const int forced = getenv("PS_K3_CH") ? atoi(getenv("PS_K3_CH")) : 0;
-    if (forced > 0) return forced;
-#endif
     const int ch = (rows / 64) & ~1;
     return std::min(8, std::max(min_rows, ch));
 }
@@ -1344,6 +1293,17 @@ struct K3Go {
     hipStream_t s;
     ps_k3_plan* plan;   // non-null: record only, launch nothing, make no HIP call
     int cus;            // compute units of the device the launch is for
+};
+
+// The arguments of one K3 call (a plan query leaves the pointers NULL; out_misalign: the low four address bits of `out`)
+struct K3Call {
+    const float* xyz;
+    float* out;
+    int B, N, A;
+    AtomSel sel;
+    int row_begin, row_end, out_rows, out_row_origin;
+    unsigned out_misalign;
+    int rows() const { return row_end - row_begin; }
 };
 
 struct K3Shape {        // what the plan reports besides the kernel's name and launch geometry
@@ -1372,22 +1332,21 @@ inline int k3_go(const K3Go& go, const char* family, const char* name, const K3S
 }
 
 template <int NP, int SRC, int NC, bool VEC, bool FAITHFUL>
-int launch_sweep(const float* xyz, float* out, int B, int N, int A, const AtomSel& sel, int row_begin, int row_end,
-                 int out_rows, int out_row_origin, const K3Go& go) {
+int launch_sweep(const K3Call& c, const K3Go& go) {
     constexpr int NPI = NP - __builtin_popcount(SRC & ((1 << NP) - 1));
     constexpr int THREADS = k3_sweep_threads(NC, FAITHFUL);
-    const int rows = row_end - row_begin, cus = go.cus;
+    const int N = c.N, rows = c.rows(), cus = go.cus;
     const int n_strips = (N + 64 * NC - 1) / (64 * NC);
     const int CH = k3_rows_per_task(rows, 2);
     const int n_chunks = (rows + CH - 1) / CH;
-    const unsigned long long n_tasks = (unsigned long long)n_strips * n_chunks * B;
+    const unsigned long long n_tasks = (unsigned long long)n_strips * n_chunks * c.B;
     if (n_tasks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const size_t need = (size_t)((rows + 2) / 2) * (NPI > 0 ? NPI : 1) * 3 * 8;   // one segment's rows, pair-interleaved
     // Every CU one full-width workgroup -- or, when a workgroup would walk four or more (structure, strip) segments (chains
     // of ~128 residues in large batches), TWO of half the width: a segment's set-up (two barriers, the global-load latency
     // of its rows and column points) idles all of a workgroup's waves for ~1.8 us, and a second workgroup on the CU computes
     // meanwhile.  Their LDS requests admit exactly two per CU.  Short lists: at least 4 tasks per workgroup.
-    const unsigned long long segs = (unsigned long long)n_strips * B;
+    const unsigned long long segs = (unsigned long long)n_strips * c.B;
     const bool two = segs >= 4ull * cus * 2 && need <= K3_LDS_TWO_PER_CU;
     const unsigned slots = (unsigned)cus * (two ? 2u : 1u);
     const unsigned tasks_per_wg = (unsigned)std::max<unsigned long long>((n_tasks + slots - 1) / slots, 4ull);
@@ -1400,62 +1359,54 @@ int launch_sweep(const float* xyz, float* out, int B, int N, int A, const AtomSe
     sh.nc = NC; sh.vec = VEC; sh.skips = !VEC; sh.faithful = FAITHFUL; sh.rows_per_task = CH;
     sh.wgs_per_cu = two ? 2 : 1; sh.structs_per_segment = 1; sh.n_tasks = (unsigned)n_tasks; sh.tasks_per_wg = tasks_per_wg;
     return k3_go(go, "sweep", name, sh, k3_sweep<NP, SRC, NC, VEC, FAITHFUL>, &prepared, dim3(grid), dim3(THREADS >> (two ? 1 : 0)), dyn, 4u,
-                 xyz, out, N, A, sel, row_begin, row_end, out_rows, out_row_origin, CH, n_strips, n_chunks, (unsigned)n_tasks, tasks_per_wg);
+                 c.xyz, c.out, N, c.A, c.sel, c.row_begin, c.row_end, c.out_rows, c.out_row_origin, CH, n_strips, n_chunks, (unsigned)n_tasks,
+                 tasks_per_wg);
 }
 
-// LDS the flat kernel stages its structures in (one workgroup per CU: the request keeps a second one off the CU)
-constexpr size_t K3_FLAT_LDS = 128 * 1024;
+// Tiles of two row pairs x FOUR columns (a row of the tile is one 16-byte store) save ~10 % of the instructions of the
+// two-column tiles, which must not go to idle lanes: a structure's tiles fill whole tasks of 64, and the wide tiles are taken
+// unless they idle > 8 % more lanes of the last task (K3, N = 36: 81 tiles in 2 tasks against 162 in 3: 113 against 105 us;
+// N = 48: 144 in 3 against 288 in 5: level).  TR: the structure's tile rows.  Shared by k3_flat and k3_featurise_tiles.
+inline bool k3_wide_tiles_pay(unsigned TR, int N) {
+    const unsigned ft_w = TR * ((unsigned)N / 4), ft_n = TR * ((unsigned)N / 2);
+    const unsigned long long lanes_w = 64ull * ((ft_w + 63) / 64) * 2, lanes_n = 64ull * ((ft_n + 63) / 64);   // in narrow-tile units
+    return lanes_w * 100 <= lanes_n * 108;
+}
 
 template <int NP, int SRC, bool FAITHFUL>
-int launch_flat(const float* xyz, float* out, int B, int N, int A, const AtomSel& sel, int row_begin, int row_end, int out_rows,
-                int out_row_origin, unsigned out_misalign_bytes, const K3Go& go) {
+int launch_flat(const K3Call& c, const K3Go& go) {
     constexpr int NPI = NP - __builtin_popcount(SRC & ((1 << NP) - 1)), NPJ = NP - NPI;
-    const int rows = row_end - row_begin, rp = (rows + 1) / 2;
+    const int N = c.N, rows = c.rows(), rp = (rows + 1) / 2;
     // a row of the tile as one 16-byte store (then the tile is four columns wide), or as one 8-byte store, where the chain length
     // and the rows' alignment allow it
-    const unsigned mis = out_misalign_bytes + (unsigned)(((long long)row_begin - out_row_origin) * N * 4);
+    const unsigned mis = c.out_misalign + (unsigned)(((long long)c.row_begin - c.out_row_origin) * N * 4);
     int vec = (N % 4 == 0 && (mis & 15u) == 0) ? 4 : (N % 2 == 0 && (mis & 7u) == 0) ? 2 : 0;
     const unsigned TR = (unsigned)(rp + 1) / 2;
-    if (vec == 4) {
-        // a structure's tiles fill whole tasks of 64: the wide tile's instruction saving (~10 %) must not go to idle lanes of the
-        // last task (N = 36: 81 tiles in 2 tasks against 162 in 3: 113 against 105 us; N = 48: 144 in 3 against 288 in 5: level)
-        const unsigned ft_w = TR * ((unsigned)N / 4), ft_n = TR * ((unsigned)N / 2);
-        const unsigned long long lanes_w = 64ull * ((ft_w + 63) / 64) * 2, lanes_n = 64ull * ((ft_n + 63) / 64);   // in narrow-tile units
-        if (lanes_w * 100 > lanes_n * 108) vec = 2;
-    }
+    if (vec == 4 && !k3_wide_tiles_pay(TR, N)) vec = 2;
     const unsigned TC = vec == 4 ? (unsigned)N / 4 : (unsigned)(N + 1) / 2;       // tiles of two row pairs x four / two columns
     const unsigned tps = (TR * TC + 63u) / 64u;                                   // tasks (64 tiles) per structure
-    const unsigned long long n_tasks = (unsigned long long)tps * B;
+    const unsigned long long n_tasks = (unsigned long long)tps * c.B;
     if (n_tasks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const int col_vec4 = NPJ * N, slot_vec4 = col_vec4 + rp * NPI * 2;   // 16-byte units: {x, y, z, -} per column atom; two per row-pair atom
-#ifdef PS_K3_AB
-    static const int wgs_env = getenv("PS_K3_FLAT_WGS") ? atoi(getenv("PS_K3_FLAT_WGS")) : 2;
-    static const int passes_env = getenv("PS_K3_FLAT_PASSES") ? atoi(getenv("PS_K3_FLAT_PASSES")) : 4;
-#else
-    constexpr int wgs_env = 2, passes_env = 4;
-#endif
     // two 512-thread workgroups per CU (their LDS requests admit exactly two): one computes while the other stages
-    const int wgs = wgs_env == 1 ? 1 : 2;
-    const unsigned slots = (unsigned)go.cus * (unsigned)wgs;
+    const unsigned slots = (unsigned)go.cus * 2u;
     const unsigned tasks_per_wg = (unsigned)std::max<unsigned long long>((n_tasks + slots - 1) / slots, 4ull);
     const unsigned grid = (unsigned)((n_tasks + tasks_per_wg - 1) / tasks_per_wg);
     // structures per staging pass: a quarter of a workgroup's share (so that the two workgroups of a CU interleave their
     // passes), at most what the LDS holds
-    const size_t lds_cap = wgs == 2 ? K3_LDS_TWO_PER_CU : K3_FLAT_LDS;
     const unsigned share = (tasks_per_wg + tps - 1) / tps + 1;
-    const size_t by_share = std::max<size_t>(1, (share + passes_env - 1) / passes_env);
-    const int KS = (int)std::max<size_t>(1, std::min<size_t>(lds_cap / ((size_t)slot_vec4 * 16), by_share));
-    const size_t dyn = wgs == 2 ? K3_LDS_TWO_PER_CU : std::max((size_t)KS * slot_vec4 * 16, K3_LDS_ONE_PER_CU);
+    const size_t by_share = std::max<size_t>(1, (share + 3) / 4);
+    const int KS = (int)std::max<size_t>(1, std::min<size_t>(K3_LDS_TWO_PER_CU / ((size_t)slot_vec4 * 16), by_share));
     static unsigned long long prepared[1] = {0};
     char name[96];
     snprintf(name, sizeof name, "k3_flat<NP=%d,SRC=%d,FAITHFUL=%d>", NP, SRC, (int)FAITHFUL);
     K3Shape sh;
-    sh.nc = 4; sh.skips = 1; sh.faithful = FAITHFUL; sh.rows_per_task = 0; sh.wgs_per_cu = wgs; sh.structs_per_segment = KS;
+    sh.nc = 4; sh.skips = 1; sh.faithful = FAITHFUL; sh.rows_per_task = 0; sh.wgs_per_cu = 2; sh.structs_per_segment = KS;
     sh.vec = vec / 2;                       // ps_k3_plan.vector_stores: 0 dword, 1 8-byte, 2 16-byte stores
     sh.n_tasks = (unsigned)n_tasks; sh.tasks_per_wg = tasks_per_wg;
-    return k3_go(go, "flat_tiles", name, sh, k3_flat<NP, SRC, FAITHFUL>, &prepared, dim3(grid), dim3(1024 / wgs), dyn, 4u, xyz, out, N, A, sel, row_begin,
-                 row_end, out_rows, out_row_origin, KS, tps, (unsigned)n_tasks, tasks_per_wg, (unsigned)((1ull << 32) / (unsigned)N), col_vec4,
-                 slot_vec4, (unsigned)((1ull << 32) / std::max(1u, TC)), vec);
+    return k3_go(go, "flat_tiles", name, sh, k3_flat<NP, SRC, FAITHFUL>, &prepared, dim3(grid), dim3(512), K3_LDS_TWO_PER_CU, 4u, c.xyz, c.out, N,
+                 c.A, c.sel, c.row_begin, c.row_end, c.out_rows, c.out_row_origin, KS, tps, (unsigned)n_tasks, tasks_per_wg,
+                 (unsigned)((1ull << 32) / (unsigned)N), col_vec4, slot_vec4, (unsigned)((1ull << 32) / std::max(1u, TC)), vec);
 }
 
 // whether one structure's selected atoms fit the flat kernel's LDS (two workgroups per CU)
@@ -1481,8 +1432,6 @@ constexpr int K3_FEATURISE_MIN_N = 40;
 // the tiles' stores are dwords and bytes there)
 constexpr int K3F_TILES_MIN_N = 8, K3F_TILES_MAX_N = 96;     // every chain of 8 .. 96 residues ...
 constexpr int K3F_TILES_MAX_N_EVEN = 200, K3F_TILES_UTIL_PERCENT = 85;   // ... and even lengths up to 200 where < 85 % of the sweep's lanes would have a column
-constexpr unsigned K3F_TILES_WGS = 2;                        // (2 / 3 / 4 workgroups per CU: no difference beyond noise)
-constexpr unsigned K3F_TILES_OVER = 1;                       // workgroups per resident slot
 constexpr int K3_FLAT_MAX_N = 256;        // ... up to this length (above it the fast sweeps are level with the tiles: 57-64 / 59-66 / 38-42 us)
 constexpr int K3_FLAT_MAX_N_WIDE = 448;   // ... this one where the tiles are four columns wide (N % 4 == 0, 16-byte rows): 56-59 / 54-61 / 38-44 us from 288 to 448
                                           // residues against the sweeps' 56-72 / 59-69 / 39-49 (level at 256 and 384; from 480 on the sweeps win)
@@ -1492,45 +1441,65 @@ constexpr int K3_FLAT_UTIL_PERCENT_FAITHFUL = 95;   // (the faithful sweeps, two
 constexpr int K3_SMALL_MAX_N = 32;    // k3_small: one wave per structure (33..64 measured: no better than the one-column kernel)
 
 template <int NP, int SRC, bool FAITHFUL>
-int launch_one_column(const float* xyz, float* out, int B, int N, int A, const AtomSel& sel, int row_begin, int row_end,
-                      int out_rows, int out_row_origin, const K3Go& go) {
-    const int rows = row_end - row_begin, thr1 = k3_one_column_threads(N), IR = 16;
-    const int n_tiles = (N + thr1 - 1) / thr1, n_chunks = (rows + IR - 1) / IR;
-    const unsigned long long n_wg = (unsigned long long)n_tiles * n_chunks * B;
+int launch_one_column(const K3Call& c, const K3Go& go) {
+    const int N = c.N, thr1 = k3_one_column_threads(N), IR = 16;
+    const int n_tiles = (N + thr1 - 1) / thr1, n_chunks = (c.rows() + IR - 1) / IR;
+    const unsigned long long n_wg = (unsigned long long)n_tiles * n_chunks * c.B;
     if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     char name[96];
     snprintf(name, sizeof name, "k3_pairwise_angles<NP=%d,SRC=%d,FAITHFUL=%d>", NP, SRC, (int)FAITHFUL);
     K3Shape sh;
     sh.faithful = FAITHFUL; sh.rows_per_task = IR;
-    return k3_go(go, "one_column", name, sh, k3_pairwise_angles<NP, SRC, FAITHFUL>, nullptr, dim3((unsigned)n_wg), dim3(thr1), 0, 0u, xyz, out,
-                 N, A, sel, row_begin, row_end, out_rows, out_row_origin, IR, n_tiles, n_chunks);
+    return k3_go(go, "one_column", name, sh, k3_pairwise_angles<NP, SRC, FAITHFUL>, nullptr, dim3((unsigned)n_wg), dim3(thr1), 0, 0u, c.xyz,
+                 c.out, N, c.A, c.sel, c.row_begin, c.row_end, c.out_rows, c.out_row_origin, IR, n_tiles, n_chunks);
+}
+
+template <int NP, int SRC, bool FAITHFUL>
+int launch_small(const K3Call& c, const K3Go& go) {   // short chains: lanes = (row group, column), one wave per structure
+    const int N = c.N;
+    const unsigned long long n_wg = ((unsigned long long)c.B + 3) / 4;
+    if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    char name[96];
+    snprintf(name, sizeof name, "k3_small<NP=%d,SRC=%d,FAITHFUL=%d>", NP, SRC, (int)FAITHFUL);
+    K3Shape sh;
+    sh.faithful = FAITHFUL; sh.rows_per_task = 4 * (64 >> (N <= 16 ? 4 : 5)); sh.nc = N <= 16 ? 16 : 32;
+    return k3_go(go, "small", name, sh, k3_small<NP, SRC, FAITHFUL>, nullptr, dim3((unsigned)n_wg), dim3(256), 0, 0u, c.xyz, c.out, c.B, N, c.A,
+                 c.sel, c.row_begin, c.row_end, c.out_rows, c.out_row_origin, N <= 16 ? 4 : N <= 32 ? 5 : 6);
+}
+
+// The sweep layout a launch would take: vector stores or columns 64 apart, columns per lane, and the 64-column groups it
+// evaluates per row pair.  NC columns per lane in the vector layout need N % NC == 0 and 4 * NC-byte aligned rows (`fits`: the
+// sweep can run at all; `can4`: the instantiation keeps its registers at four columns, see launch).
+struct K3SweepLayout {
+    int nc;
+    bool vec;
+    long long groups;
+};
+inline K3SweepLayout k3_sweep_layout(int N, unsigned out_misalign, bool fits, bool can4) {
+    const bool ok4 = can4 && fits && N % 4 == 0 && (out_misalign & 15u) == 0, ok2 = fits && N % 2 == 0 && (out_misalign & 7u) == 0;
+    // lanes past the last column idle: take the width that wastes fewer of them (a tie goes to the wider stores)
+    const long long w4 = (long long)((N + 255) / 256) * 256, w2 = (long long)((N + 127) / 128) * 128;
+    const bool vec4 = ok4 && (!ok2 || w4 <= w2);
+    // The 64-apart layout skips the dead column groups of a row's last strip (every instantiation does since the fast (2,2)
+    // dihedral takes two columns per lane: round 5): it computes ceil(N / 64) groups per row pair where the vector layouts
+    // compute whole strips -- taken also for even N where that saves more than its dword stores cost; four columns per lane
+    // from three groups on
+    const long long gn = (N + 63) / 64, gv = (vec4 ? w4 : w2) / 64;
+    if ((ok4 || ok2) && !(gn * 115 < gv * 100)) return K3SweepLayout{vec4 ? 4 : 2, true, gv};
+    return K3SweepLayout{(can4 && gn > 2) ? 4 : 2, false, gn};
 }
 
 // mode = exact_angles of the C ABI: bit 0 = the reference's order of operations (FAITHFUL), bit 1 = the one-column kernel
 // whatever the shape (diagnostic: the layout-free twin the sweep kernels are held to, bit for bit, in either arithmetic)
 template <int NP, int SRC, bool FAITHFUL>
-int launch(const float* xyz, float* out, int B, int N, int A, const AtomSel& sel, int row_begin, int row_end,
-           int out_rows, int out_row_origin, bool simple, unsigned out_misalign, const K3Go& go) {
+int launch(const K3Call& c, bool simple, const K3Go& go) {
     constexpr int NPI = NP - __builtin_popcount(SRC & ((1 << NP) - 1));
-    const int rows = row_end - row_begin;
-#ifdef PS_K3_AB
-    static const int small_max = getenv("PS_K3_SMALL_MAX") ? atoi(getenv("PS_K3_SMALL_MAX")) : K3_SMALL_MAX_N;
-#else
-    constexpr int small_max = K3_SMALL_MAX_N;
-#endif
-    if (!simple && N <= small_max) {   // short chains: lanes = (row group, column), one wave per structure
-        const unsigned long long n_wg = ((unsigned long long)B + 3) / 4;
-        if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-        char name[96];
-        snprintf(name, sizeof name, "k3_small<NP=%d,SRC=%d,FAITHFUL=%d>", NP, SRC, (int)FAITHFUL);
-        K3Shape sh;
-        sh.faithful = FAITHFUL; sh.rows_per_task = 4 * (64 >> (N <= 16 ? 4 : 5)); sh.nc = N <= 16 ? 16 : 32;
-        return k3_go(go, "small", name, sh, k3_small<NP, SRC, FAITHFUL>, nullptr, dim3((unsigned)n_wg), dim3(256), 0, 0u, xyz, out, B, N, A, sel,
-                     row_begin, row_end, out_rows, out_row_origin, N <= 16 ? 4 : N <= 32 ? 5 : 6);
-    }
-    // NC columns per lane need N % NC == 0 and 4 * NC-byte aligned rows; the segment's rows have to fit the LDS, and its
-    // output has to be addressable by the kernel's 32-bit byte offsets (a row-sharded call on a very long chain)
-    const bool fits = !simple && N >= K3_SWEEP_MIN_N && (size_t)((rows + 2) / 2) * (NPI > 0 ? NPI : 1) * 3 * 8 <= K3_LDS_MAX &&
+    const int N = c.N, rows = c.rows();
+    if (simple) return launch_one_column<NP, SRC, FAITHFUL>(c, go);
+    if (N <= K3_SMALL_MAX_N) return launch_small<NP, SRC, FAITHFUL>(c, go);
+    // the segment's rows have to fit the LDS, and its output has to be addressable by the kernel's 32-bit byte offsets (a
+    // row-sharded call on a very long chain)
+    const bool fits = N >= K3_SWEEP_MIN_N && (size_t)((rows + 2) / 2) * (NPI > 0 ? NPI : 1) * 3 * 8 <= K3_LDS_MAX &&
                       (unsigned long long)rows * (unsigned long long)N * 4ull < (1ull << 31);
     // four columns per lane only where the instantiation keeps its registers (three or two column-side points of a
     // dihedral times four columns do not fit the 128 VGPRs of a 1024-thread workgroup: 4-95 spilled registers -- the (2,2)
@@ -1539,73 +1508,35 @@ int launch(const float* xyz, float* out, int B, int N, int A, const AtomSel& sel
     // the faithful kernels' 512-thread workgroups have 256 and take four columns for every split)
     constexpr bool NC4 = FAITHFUL ? K3_FAITHFUL_NC4(NP, SRC)
                                   : (NP == 3 || SRC == 0 || SRC == 1 || SRC == 2 || SRC == 4 || SRC == 8 || SRC == 15);
-#ifdef PS_K3_AB
-    static const int force_nc = getenv("PS_K3_NC") ? atoi(getenv("PS_K3_NC")) : 0;
-    const bool allow4 = force_nc != 2;
-    static const int flat_util = getenv("PS_K3_FLAT_UTIL") ? atoi(getenv("PS_K3_FLAT_UTIL")) : (FAITHFUL ? K3_FLAT_UTIL_PERCENT_FAITHFUL : K3_FLAT_UTIL_PERCENT);
-    static const int flat_max_n = getenv("PS_K3_FLAT_MAX_N") ? atoi(getenv("PS_K3_FLAT_MAX_N")) : (FAITHFUL ? K3_FLAT_MAX_N_FAITHFUL : K3_FLAT_MAX_N);
-#else
-    constexpr int flat_max_n = FAITHFUL ? K3_FLAT_MAX_N_FAITHFUL : K3_FLAT_MAX_N;
-    const bool allow4 = true;
-    constexpr int flat_util = FAITHFUL ? K3_FLAT_UTIL_PERCENT_FAITHFUL : K3_FLAT_UTIL_PERCENT;
-#endif
-    const bool ok4 = NC4 && allow4 && fits && N % 4 == 0 && (out_misalign & 15u) == 0, ok2 = fits && N % 2 == 0 && (out_misalign & 7u) == 0;
-    // lanes past the last column idle: take the width that wastes fewer of them (a tie goes to the wider stores)
-    const long long w4 = (long long)((N + 255) / 256) * 256, w2 = (long long)((N + 127) / 128) * 128;
-    // The 64-apart layout skips the dead column groups of a row's last strip: it computes ceil(N / 64) groups per row pair
-    // where the vector layouts compute whole strips -- taken also for even N where that saves more than its dword stores cost
-    const long long gn = (N + 63) / 64, gv = (NC4 && ok4 && (!ok2 || w4 <= w2) ? w4 : w2) / 64;
-    constexpr bool SKIPS = true;   // (every instantiation skips dead groups since the fast (2,2) dihedral takes two columns per lane: round 5)
-    // the sweep layout this launch would take: vector stores or columns 64 apart, columns per lane, and the 64-column groups
-    // it evaluates per row pair (dead ones included unless skipped)
-    const bool vec = (ok4 || ok2) && !(SKIPS && gn * 115 < gv * 100);
-    const int nc = vec ? ((NC4 && ok4 && (!ok2 || w4 <= w2)) ? 4 : 2) : ((NC4 && allow4 && (SKIPS ? gn > 2 : w4 <= w2)) ? 4 : 2);
-    const long long g_eval = vec ? gv : (SKIPS ? gn : (nc == 4 ? w4 : w2) / 64);
+    const K3SweepLayout lay = k3_sweep_layout(N, c.out_misalign, fits, NC4);
     // The flat kernel in its 2 x 2 tile map (every lane has an element whatever N is; 59-66 / 66-77 / 45-55 us per 2^25 pairs from
     // 48 to 140 residues, profiles/r05_k3_shapes.log): every chain shorter than the sweeps' minimum, and up to 256 residues wherever
     // fewer than K3_FLAT_UTIL_PERCENT of the sweep's lanes would have a column (N = 140: three groups of 64 for 140 columns,
     // 59 against 102 us; N = 180: 59 / 66 / 46 against 61 / 74 / 50).
-    const bool wide_tiles = N % 4 == 0 && (out_misalign & 15u) == 0;
-#ifdef PS_K3_AB
-    const int flat_max = (getenv("PS_K3_FLAT_MAX_N") || FAITHFUL || !wide_tiles) ? flat_max_n : K3_FLAT_MAX_N_WIDE;
-#else
-    const int flat_max = (FAITHFUL || !wide_tiles) ? flat_max_n : K3_FLAT_MAX_N_WIDE;
-#endif
-    if (!simple && N > small_max && N >= 32 && k3_flat_fits(N, A) &&
-        (N < K3_SWEEP_MIN_N || !fits ||
-         (N <= flat_max && ((long long)N * 100 < (long long)flat_util * 64 * g_eval ||
-                              // ... or where the sweep would write dwords (its columns 64 apart) and the tiles whole 16-byte rows: N = 192
-                              (!vec && wide_tiles))))) {
-        return launch_flat<NP, SRC, FAITHFUL>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, out_misalign, go);
+    constexpr int flat_util = FAITHFUL ? K3_FLAT_UTIL_PERCENT_FAITHFUL : K3_FLAT_UTIL_PERCENT;
+    const bool wide_tiles = N % 4 == 0 && (c.out_misalign & 15u) == 0;
+    const int flat_max = FAITHFUL ? K3_FLAT_MAX_N_FAITHFUL : wide_tiles ? K3_FLAT_MAX_N_WIDE : K3_FLAT_MAX_N;
+    if (k3_flat_fits(N, c.A) &&
+        (!fits || (N <= flat_max && ((long long)N * 100 < (long long)flat_util * 64 * lay.groups ||
+                                     // ... or where the sweep would write dwords (its columns 64 apart) and the tiles whole 16-byte rows: N = 192
+                                     (!lay.vec && wide_tiles)))))
+        return launch_flat<NP, SRC, FAITHFUL>(c, go);
+    if (!fits) return launch_one_column<NP, SRC, FAITHFUL>(c, go);
+    // vector stores, or (odd N, a misaligned output, or fewer groups) the lane's columns 64 apart and dword stores
+    if constexpr (NC4) {
+        if (lay.nc == 4) return lay.vec ? launch_sweep<NP, SRC, 4, true, FAITHFUL>(c, go) : launch_sweep<NP, SRC, 4, false, FAITHFUL>(c, go);
     }
-    if (vec) {
-        if constexpr (NC4) {
-            if (nc == 4)
-                return launch_sweep<NP, SRC, 4, true, FAITHFUL>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, go);
-        }
-        return launch_sweep<NP, SRC, 2, true, FAITHFUL>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, go);
-    }
-    if (fits) {   // odd N, a misaligned output, or fewer groups: the same sweep with the lane's columns 64 apart and dword stores
-        if constexpr (NC4) {   // four columns from three groups on where dead groups are skipped; else by the lanes a strip wastes
-            if (nc == 4)
-                return launch_sweep<NP, SRC, 4, false, FAITHFUL>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, go);
-        }
-        return launch_sweep<NP, SRC, 2, false, FAITHFUL>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, go);
-    }
-    return launch_one_column<NP, SRC, FAITHFUL>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, go);
+    return lay.vec ? launch_sweep<NP, SRC, 2, true, FAITHFUL>(c, go) : launch_sweep<NP, SRC, 2, false, FAITHFUL>(c, go);
 }
 
 template <int NP, int... SRCS>
-int dispatch(int srcmask, const float* xyz, float* out, int B, int N, int A, const AtomSel& sel, int row_begin,
-             int row_end, int out_rows, int out_row_origin, int mode, unsigned out_misalign, const K3Go& go) {
+int dispatch(int srcmask, const K3Call& c, int mode, const K3Go& go) {
     int rc = (int)hipErrorInvalidValue;
     const bool simple = (mode & 2) != 0;
     if (mode & 1)
-        (void)((srcmask == SRCS ? (rc = launch<NP, SRCS, true>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, simple, out_misalign, go), true)
-                                : false) || ...);
+        (void)((srcmask == SRCS ? (rc = launch<NP, SRCS, true>(c, simple, go), true) : false) || ...);
     else
-        (void)((srcmask == SRCS ? (rc = launch<NP, SRCS, false>(xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, simple, out_misalign, go), true)
-                                : false) || ...);
+        (void)((srcmask == SRCS ? (rc = launch<NP, SRCS, false>(c, simple, go), true) : false) || ...);
     return rc;
 }
 
@@ -1627,13 +1558,9 @@ inline int k3_check_args(int B, int N, int A, int n_points, const int* src, cons
     return 0;
 }
 
-inline int k3_run(const float* xyz, float* out, int B, int N, int A, int n_points, const AtomSel& sel, int srcmask, int row_begin,
-                  int row_end, int out_rows, int out_row_origin, int exact_angles, unsigned out_misalign, const K3Go& go) {
-    if (n_points == 4)
-        return dispatch<4, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(srcmask, xyz, out, B, N, A, sel, row_begin, row_end, out_rows,
-                                                                                 out_row_origin, exact_angles, out_misalign, go);
-    return dispatch<3, 0, 1, 2, 3, 4, 5, 6, 7>(srcmask, xyz, out, B, N, A, sel, row_begin, row_end, out_rows, out_row_origin, exact_angles,
-                                               out_misalign, go);
+inline int k3_run(const K3Call& c, int n_points, int srcmask, int exact_angles, const K3Go& go) {
+    if (n_points == 4) return dispatch<4, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(srcmask, c, exact_angles, go);
+    return dispatch<3, 0, 1, 2, 3, 4, 5, 6, 7>(srcmask, c, exact_angles, go);
 }
 
 inline void k3_plan_reset(ps_k3_plan* plan) {
@@ -1649,15 +1576,13 @@ extern "C" int ps_pairwise_angles_f32(const float* xyz, float* out, int B, int N
                                       const int* atom, int row_begin, int row_end, int out_rows, int out_row_origin,
                                       int exact_angles, void* stream) {
     if (!xyz || !out) return (int)hipErrorInvalidValue;
-    AtomSel sel;
+    K3Call c{xyz, out, B, N, A, AtomSel{}, row_begin, row_end, out_rows, out_row_origin, (unsigned)(reinterpret_cast<uintptr_t>(out) & 15u)};
     int srcmask = 0;
-    if (const int e = k3_check_args(B, N, A, n_points, src, atom, row_begin, row_end, out_rows, out_row_origin, exact_angles, sel, srcmask))
+    if (const int e = k3_check_args(B, N, A, n_points, src, atom, row_begin, row_end, out_rows, out_row_origin, exact_angles, c.sel, srcmask))
         return e;
     if (B == 0 || N == 0 || row_begin == row_end) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const K3Go go{s, nullptr, k3_cu_count(s)};
-    return k3_run(xyz, out, B, N, A, n_points, sel, srcmask, row_begin, row_end, out_rows, out_row_origin, exact_angles,
-                  (unsigned)(reinterpret_cast<uintptr_t>(out) & 15u), go);
+    return k3_run(c, n_points, srcmask, exact_angles, K3Go{s, nullptr, k3_cu_count(s)});
 }
 
 extern "C" int ps_k3_plan_f32(int B, int N, int A, int n_points, const int* src, const int* atom, int row_begin, int row_end,
@@ -1665,36 +1590,33 @@ extern "C" int ps_k3_plan_f32(int B, int N, int A, int n_points, const int* src,
                               ps_k3_plan* plan) {
     if (!plan || plan->struct_size != (int)sizeof(ps_k3_plan)) return (int)hipErrorInvalidValue;
     k3_plan_reset(plan);
-    AtomSel sel;
+    K3Call c{nullptr, nullptr, B, N, A, AtomSel{}, row_begin, row_end, out_rows, out_row_origin, (unsigned)out_misalign};
     int srcmask = 0;
-    if (const int e = k3_check_args(B, N, A, n_points, src, atom, row_begin, row_end, out_rows, out_row_origin, exact_angles, sel, srcmask))
+    if (const int e = k3_check_args(B, N, A, n_points, src, atom, row_begin, row_end, out_rows, out_row_origin, exact_angles, c.sel, srcmask))
         return e;
     if (out_misalign < 0 || out_misalign > 15 || (out_misalign & 3)) return (int)hipErrorInvalidValue;
     if (B == 0 || N == 0 || row_begin == row_end) return 0;
-    const K3Go go{nullptr, plan, cu_count > 0 ? cu_count : 256};
-    return k3_run(nullptr, nullptr, B, N, A, n_points, sel, srcmask, row_begin, row_end, out_rows, out_row_origin, exact_angles,
-                  (unsigned)out_misalign, go);
+    return k3_run(c, n_points, srcmask, exact_angles, K3Go{nullptr, plan, cu_count > 0 ? cu_count : 256});
 }
 
 namespace {
+
+// The arguments of one featuriser call (a plan query leaves the pointers NULL).  alf / alm: the low seven bits of the float /
+// mask planes' addresses, OR-ed over the planes.
+struct K3fCall {
+    const float* xyz;
+    const uint8_t* amask;
+    float *d_ca, *d_cb, *d_no, *omega, *theta, *phi;
+    uint8_t *m_ca, *m_cb, *m_no;
+    int B, N, A, exact_sqrt;
+    uintptr_t alf, alm;
+};
 
 // argument checks shared by the featuriser's launcher and its plan query
 inline int k3f_check_args(int B, int N, int A, int exact_sqrt, int exact_angles) {
     if (B < 0 || N < 0 || A < 5 || (exact_sqrt != 0 && exact_sqrt != 1) || exact_angles < 0 || exact_angles > 3)
         return (int)hipErrorInvalidValue;
     return 0;
-}
-
-// one featuriser instantiation by its run-time switches (EXACT: the distance planes' square root)
-template <int NC, bool VEC, bool M16, bool WT, bool FAITHFUL, typename... Args>
-inline int k3f_go(const K3Go& go, bool exact_sqrt, const K3Shape& sh, dim3 grid, dim3 block, size_t dyn, Args&&... args) {
-    static unsigned long long prep[2][1] = {{0}, {0}};
-    char name[96];
-    snprintf(name, sizeof name, "k3_featurise<EXACT=%d,NC=%d,VEC=%d,M16=%d,WT=%d,FAITHFUL=%d>", (int)exact_sqrt, NC, (int)VEC, (int)M16, (int)WT,
-             (int)FAITHFUL);
-    if (exact_sqrt)
-        return k3_go(go, "featurise", name, sh, k3_featurise<true, NC, VEC, M16, WT, FAITHFUL>, &prep[0], grid, block, dyn, 4u, static_cast<Args&&>(args)...);
-    return k3_go(go, "featurise", name, sh, k3_featurise<false, NC, VEC, M16, WT, FAITHFUL>, &prep[1], grid, block, dyn, 4u, static_cast<Args&&>(args)...);
 }
 
 // The featuriser sweep's layout for a chain length and float-plane alignment: vector float stores where rows and planes allow
@@ -1721,173 +1643,177 @@ inline K3fSweepLayout k3f_sweep_layout(int N, uintptr_t alf) {
     return K3fSweepLayout{NC, vec};
 }
 
+// LDS of one structure in the tile kernel, in 16-byte units: column atoms, row atoms, one byte per residue
+inline size_t k3f_tiles_slot_vec4(int N) { return (size_t)3 * N + (size_t)6 * ((N + 1) / 2) + ((size_t)N + 15) / 16; }
+
+// The tile kernel (several structures per pass, every lane busy): chains of K3F_TILES_MIN_N .. K3F_TILES_MAX_N residues, and ...
 template <bool FAITHFUL>
-int k3f_run(const float* xyz, const uint8_t* atom_mask, float* d_ca, float* d_cb, float* d_no, float* omega, float* theta, float* phi,
-            uint8_t* d_ca_mask, uint8_t* d_cb_mask, uint8_t* d_no_mask, int B, int N, int A, int exact_sqrt, bool simple, uintptr_t alf,
-            uintptr_t alm, const K3Go& go) {
-    // one structure's rows (points + mask words), its column points, its column masks (bytes or bit sets)
-    const size_t need = (size_t)((N + 2) / 2) * (9 * 8 + 4) + 32 + 16 + (size_t)((N + 3) & ~3) * 36 +
-                        std::max<size_t>(3 * (size_t)N, 3 * ((size_t)(N + 31) / 32 + 2) * 4) + 16;
-    // Chains of K3F_TILES_MIN_N .. K3F_TILES_MAX_N residues: the tile kernel (several structures per pass, every lane busy)
-#ifdef PS_K3_AB
-    static const int tiles_min = getenv("PS_K3F_TILES_MIN") ? atoi(getenv("PS_K3F_TILES_MIN")) : K3F_TILES_MIN_N;
-    static const int tiles_max = getenv("PS_K3F_TILES_MAX") ? atoi(getenv("PS_K3F_TILES_MAX")) : K3F_TILES_MAX_N;
-#else
-    constexpr int tiles_min = K3F_TILES_MIN_N, tiles_max = K3F_TILES_MAX_N;
-#endif
-    {
-        const int n_rp = (N + 1) / 2;
-        const size_t slot_vec4 = (size_t)3 * N + (size_t)6 * n_rp + ((size_t)N + 15) / 16;   // column atoms, row atoms, one byte per residue
-        // (odd lengths -- dword and byte stores in the tile kernel -- only below 70 %: N = 129 262 against 339 us, but 101 288 against 272)
-        const bool tiles_even = N <= K3F_TILES_MAX_N_EVEN && (long long)N * 100 < (long long)(N % 2 == 0 ? K3F_TILES_UTIL_PERCENT : 70) * 64 * ((N + 63) / 64);
-        // ... and even lengths whose sweep would fall back to its 64-floats-per-store layout (three or five column groups: N = 176,
-        // 192, 272 .. 320): the tiles keep their 8-byte stores (192: 222 against 289 us, 288: 216-255 / 318, 320: 232 / 300,
-        // profiles/r05_featuriser_shapes.log)
-        const bool tiles_dword_sweep = N % 2 == 0 && (alf & 7u) == 0 && (alm & 1u) == 0 && !k3f_sweep_layout<FAITHFUL>(N, alf).vec;
-        // ... and, in the faithful arithmetic (whose sweep has two columns per lane), every length with four-column tiles: level
-        // with the sweep at 192 / 256 / 320 / 384, 5-12 % faster at 128, 224, 352, 448-500 (profiles/r05_featuriser_tile_width.log)
-        const bool tiles_faithful = FAITHFUL && N % 4 == 0 && (alf & 15u) == 0 && (alm & 3u) == 0;
-        if (!simple && N >= tiles_min && (N <= tiles_max || tiles_even || tiles_dword_sweep || tiles_faithful) && (alf & 3u) == 0 && slot_vec4 * 16 <= 48 * 1024 &&
-            (unsigned long long)N * N < (1ull << 29)) {
-            // four-column tiles where a row of the tile is one 16-byte float store and one 4-byte mask store -- unless a structure's
-            // wide tiles would idle > 8 % more lanes of their last task of 64 (as in launch_flat)
-            const unsigned TR = (unsigned)(n_rp + 1) / 2;
-            int vecf = (N % 2 == 0 && (alf & 7u) == 0) ? 2 : 0, vecm = (N % 2 == 0 && (alm & 1u) == 0) ? 2 : 0;
-#ifdef PS_K3_AB
-            static const int tiles_wide = getenv("PS_K3F_TILES_WIDE") ? atoi(getenv("PS_K3F_TILES_WIDE")) : 1;
-#else
-            constexpr int tiles_wide = 1;
-#endif
-            if (tiles_wide && N % 4 == 0 && (alf & 15u) == 0 && (alm & 3u) == 0) {
-                const unsigned ft_w = TR * ((unsigned)N / 4), ft_n = TR * ((unsigned)N / 2);
-                const unsigned long long lanes_w = 64ull * ((ft_w + 63) / 64) * 2, lanes_n = 64ull * ((ft_n + 63) / 64);
-                if (lanes_w * 100 <= lanes_n * 108) vecf = vecm = 4;
-            }
-            const unsigned TC = vecf == 4 ? (unsigned)N / 4 : (unsigned)(N + 1) / 2;
-            const unsigned tps = (TR * TC + 63u) / 64u;
-            const unsigned long long n_tasks = (unsigned long long)tps * B;
-            if (n_tasks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-#ifdef PS_K3_AB
-            static const unsigned tiles_wgs = getenv("PS_K3F_TILES_WGS") ? (unsigned)atoi(getenv("PS_K3F_TILES_WGS")) : K3F_TILES_WGS;
-            static const unsigned tiles_over = getenv("PS_K3F_TILES_OVER") ? (unsigned)atoi(getenv("PS_K3F_TILES_OVER")) : K3F_TILES_OVER;
-#else
-            constexpr unsigned tiles_wgs = K3F_TILES_WGS, tiles_over = K3F_TILES_OVER;
-#endif
-            // K3F_TILES_WGS 256-thread workgroups per CU (their LDS requests admit exactly that many; 132 / 167 VGPRs: three waves per SIMD)
-            const size_t tiles_lds = tiles_wgs == 2 ? K3_LDS_TWO_PER_CU : ((size_t)160 * 1024 / tiles_wgs - 256) & ~(size_t)255;
-            const unsigned slots = (unsigned)go.cus * tiles_wgs * tiles_over;
-            const unsigned tasks_per_wg = (unsigned)std::max<unsigned long long>((n_tasks + slots - 1) / slots, 4ull);
-            const unsigned grid = (unsigned)((n_tasks + tasks_per_wg - 1) / tasks_per_wg);
-            const unsigned share = (tasks_per_wg + tps - 1) / tps + 1;
-            const int KS = (int)std::max<size_t>(1, std::min<size_t>(tiles_lds / (slot_vec4 * 16), (share + 3) / 4));
-            char name[96];
-            snprintf(name, sizeof name, "k3_featurise_tiles<EXACT=%d,FAITHFUL=%d>", exact_sqrt, (int)FAITHFUL);
-            K3Shape sh;
-            sh.nc = 4; sh.vec = vecf / 2; sh.skips = 1; sh.mask_mode = vecm == 4 ? 4 : vecm == 2 ? 3 : 0; sh.faithful = FAITHFUL; sh.wgs_per_cu = (int)tiles_wgs; sh.structs_per_segment = KS;
-            sh.n_tasks = (unsigned)n_tasks; sh.tasks_per_wg = tasks_per_wg;
-            static unsigned long long prep[2][1] = {{0}, {0}};
-            auto tiles = [&](auto kernel, unsigned long long (&prepared)[1]) {
-                return k3_go(go, "featurise_tiles", name, sh, kernel, &prepared, dim3(grid), dim3(256), tiles_lds, 4u, xyz, atom_mask, d_ca, d_cb,
-                             d_no, omega, theta, phi, d_ca_mask, d_cb_mask, d_no_mask, N, A, KS, tps, (unsigned)n_tasks, tasks_per_wg,
-                             (unsigned)((1ull << 32) / (unsigned)N), (unsigned)((1ull << 32) / std::max(1u, TC)), (int)slot_vec4, vecf, vecm);
-            };
-            return exact_sqrt ? tiles(k3_featurise_tiles<true, FAITHFUL>, prep[0]) : tiles(k3_featurise_tiles<false, FAITHFUL>, prep[1]);
-        }
+inline bool k3f_tiles_eligible(const K3fCall& c) {
+    const int N = c.N;
+    const uintptr_t alf = c.alf, alm = c.alm;
+    // (odd lengths -- dword and byte stores in the tile kernel -- only below 70 %: N = 129 262 against 339 us, but 101 288 against 272)
+    const bool tiles_even = N <= K3F_TILES_MAX_N_EVEN && (long long)N * 100 < (long long)(N % 2 == 0 ? K3F_TILES_UTIL_PERCENT : 70) * 64 * ((N + 63) / 64);
+    // ... and even lengths whose sweep would fall back to its 64-floats-per-store layout (three or five column groups: N = 176,
+    // 192, 272 .. 320): the tiles keep their 8-byte stores (192: 222 against 289 us, 288: 216-255 / 318, 320: 232 / 300,
+    // profiles/r05_featuriser_shapes.log)
+    const bool tiles_dword_sweep = N % 2 == 0 && (alf & 7u) == 0 && (alm & 1u) == 0 && !k3f_sweep_layout<FAITHFUL>(N, alf).vec;
+    // ... and, in the faithful arithmetic (whose sweep has two columns per lane), every length with four-column tiles: level
+    // with the sweep at 192 / 256 / 320 / 384, 5-12 % faster at 128, 224, 352, 448-500 (profiles/r05_featuriser_tile_width.log)
+    const bool tiles_faithful = FAITHFUL && N % 4 == 0 && (alf & 15u) == 0 && (alm & 3u) == 0;
+    return N >= K3F_TILES_MIN_N && (N <= K3F_TILES_MAX_N || tiles_even || tiles_dword_sweep || tiles_faithful) && (alf & 3u) == 0 &&
+           k3f_tiles_slot_vec4(N) * 16 <= 48 * 1024 && (unsigned long long)N * N < (1ull << 29);
+}
+
+template <bool FAITHFUL>
+int launch_featurise_tiles(const K3fCall& c, const K3Go& go) {
+    const int N = c.N, n_rp = (N + 1) / 2;
+    const uintptr_t alf = c.alf, alm = c.alm;
+    const size_t slot_vec4 = k3f_tiles_slot_vec4(N);
+    // four-column tiles where a row of the tile is one 16-byte float store and one 4-byte mask store and they pay
+    const unsigned TR = (unsigned)(n_rp + 1) / 2;
+    int vecf = (N % 2 == 0 && (alf & 7u) == 0) ? 2 : 0, vecm = (N % 2 == 0 && (alm & 1u) == 0) ? 2 : 0;
+    if (N % 4 == 0 && (alf & 15u) == 0 && (alm & 3u) == 0 && k3_wide_tiles_pay(TR, N)) vecf = vecm = 4;
+    const unsigned TC = vecf == 4 ? (unsigned)N / 4 : (unsigned)(N + 1) / 2;
+    const unsigned tps = (TR * TC + 63u) / 64u;
+    const unsigned long long n_tasks = (unsigned long long)tps * c.B;
+    if (n_tasks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    // two 256-thread workgroups per CU (their LDS requests admit exactly that many; 132 / 167 VGPRs: three waves per SIMD;
+    // 2 / 3 / 4 workgroups per CU: no difference beyond noise), one workgroup per resident slot
+    const size_t tiles_lds = K3_LDS_TWO_PER_CU;
+    const unsigned slots = (unsigned)go.cus * 2u;
+    const unsigned tasks_per_wg = (unsigned)std::max<unsigned long long>((n_tasks + slots - 1) / slots, 4ull);
+    const unsigned grid = (unsigned)((n_tasks + tasks_per_wg - 1) / tasks_per_wg);
+    const unsigned share = (tasks_per_wg + tps - 1) / tps + 1;
+    const int KS = (int)std::max<size_t>(1, std::min<size_t>(tiles_lds / (slot_vec4 * 16), (share + 3) / 4));
+    char name[96];
+    snprintf(name, sizeof name, "k3_featurise_tiles<EXACT=%d,FAITHFUL=%d>", c.exact_sqrt, (int)FAITHFUL);
+    K3Shape sh;
+    sh.nc = 4; sh.vec = vecf / 2; sh.skips = 1; sh.mask_mode = vecm == 4 ? 4 : vecm == 2 ? 3 : 0; sh.faithful = FAITHFUL; sh.wgs_per_cu = 2; sh.structs_per_segment = KS;
+    sh.n_tasks = (unsigned)n_tasks; sh.tasks_per_wg = tasks_per_wg;
+    static unsigned long long prep[2][1] = {{0}, {0}};
+    auto tiles = [&](auto kernel, unsigned long long (&prepared)[1]) {
+        return k3_go(go, "featurise_tiles", name, sh, kernel, &prepared, dim3(grid), dim3(256), tiles_lds, 4u, c.xyz, c.amask, c.d_ca, c.d_cb,
+                     c.d_no, c.omega, c.theta, c.phi, c.m_ca, c.m_cb, c.m_no, N, c.A, KS, tps, (unsigned)n_tasks, tasks_per_wg,
+                     (unsigned)((1ull << 32) / (unsigned)N), (unsigned)((1ull << 32) / std::max(1u, TC)), (int)slot_vec4, vecf, vecm);
+    };
+    return c.exact_sqrt ? tiles(k3_featurise_tiles<true, FAITHFUL>, prep[0]) : tiles(k3_featurise_tiles<false, FAITHFUL>, prep[1]);
+}
+
+// LDS of one structure in the featuriser's sweep: its rows (points + mask words), its column points, its column masks (bytes or bit sets)
+inline size_t k3f_sweep_need(int N) {
+    return (size_t)((N + 2) / 2) * (9 * 8 + 4) + 32 + 16 + (size_t)((N + 3) & ~3) * 36 +
+           std::max<size_t>(3 * (size_t)N, 3 * ((size_t)(N + 31) / 32 + 2) * 4) + 16;
+}
+
+// the per-CU sweep: any N >= K3_FEATURISE_MIN_N whose rows fit in LDS
+inline bool k3f_sweep_eligible(const K3fCall& c) {
+    return c.N >= K3_FEATURISE_MIN_N && k3f_sweep_need(c.N) <= K3_LDS_MAX && (c.alf & 3u) == 0 && (unsigned long long)c.N * c.N < (1ull << 31);
+}
+
+template <bool FAITHFUL>
+int launch_featurise_sweep(const K3fCall& c, const K3Go& go) {
+    const int N = c.N, cus = go.cus;
+    const uintptr_t alf = c.alf, alm = c.alm;
+    const size_t need = k3f_sweep_need(N);
+    constexpr bool CAN4 = K3_FEATURISE_NC4 && !FAITHFUL;
+    const K3fSweepLayout lay = k3f_sweep_layout<FAITHFUL>(N, alf);
+    const int NC = lay.nc;
+    const bool vec = lay.vec;
+    const bool m16 = vec && N % 16 == 0 && (alm & 15u) == 0;   // strip-local 16-byte mask stores: whole 16-column groups
+    // write-through where strips are whole and every store covers whole lines; same-box A/B, trace: N = 512 174 against 178 us,
+    // 256 181 / 187 -- but N = 480 (15 lines per row, a 224-column second strip) 239 against 212 and 160 308 / 297: there write-back
+    const bool wt = m16 && N % 128 == 0 && (alf & 127u) == 0 && (alm & 127u) == 0;
+    const int n_strips = (N + 64 * NC - 1) / (64 * NC);
+    // a task is CH rows x one strip, the strips of a row chunk adjacent tasks: a workgroup's share has to be many tasks
+    // per wave whatever B and N are -- its waves wait for each other at every structure boundary for up to one task.
+    // Four rows with the M16 mask stores (four rows per instruction; rows are whole 64-byte segments there).  TWO
+    // otherwise: where rows are not whole segments, the segment a row's strips share and the one a row's end shares with
+    // the next row's start get their halves from adjacent tasks, i.e. from two waves up to a task apart -- with
+    // four-row tasks (~16 us) longer than a line stays in L2 at this store rate, so that half of them went out as two
+    // partial writes (2.2 % of the write requests at N = 500, none at N = 496: profiles/r04_featuriser_pmc.log);
+    // same-box A/B, trace: N = 500 260 -> 228 us, 511 264 -> 241, 255 238 -> 218.
+    const bool two_wg = (unsigned long long)c.B >= 4ull * cus;
+    // (chains of up to 64 residues in the 64-apart layout: eight rows, so that a lane's four chains are four row pairs)
+    const int CH = m16 ? 4 : (!vec && N <= 64) ? 8 : 2;
+    const int n_chunks = (N + CH - 1) / CH;
+    const unsigned long long n_tasks = (unsigned long long)n_chunks * n_strips * c.B;
+    if (n_tasks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    // One workgroup per CU -- or, when a CU's share is four or more structures (chains of ~128 residues in large
+    // batches), TWO of half the width: staging a structure (two barriers, a round trip to L2 for its rows and column
+    // points) idles all of a workgroup's waves, and the other workgroup computes meanwhile.  Their LDS requests admit
+    // exactly one / two per CU.
+    const bool two = two_wg && need <= K3_LDS_TWO_PER_CU;
+    const int wgs = two ? 2 * cus : cus;
+    const unsigned tasks_per_wg = (unsigned)std::max<unsigned long long>((n_tasks + wgs - 1) / wgs, 4ull);
+    const unsigned grid = (unsigned)((n_tasks + tasks_per_wg - 1) / tasks_per_wg);
+    const size_t dyn = two ? K3_LDS_TWO_PER_CU : std::max(need, K3_LDS_ONE_PER_CU);
+    // structures per staging pass (round 5): what the LDS request holds, at most a quarter of a workgroup's share (so that
+    // the workgroups of a CU interleave their passes) -- short chains paid two barriers and a round trip to L2 per structure
+    const size_t slot_bytes = (need + 15) & ~(size_t)15;
+    const unsigned long long n_sub = (unsigned long long)n_chunks * n_strips;
+    const unsigned long long share = (tasks_per_wg + n_sub - 1) / n_sub + 1;
+    const int KS = (int)std::max<unsigned long long>(1, std::min<unsigned long long>(dyn / slot_bytes, (share + 3) / 4));
+    const unsigned rcpN = (unsigned)((1ull << 32) / (unsigned)N);
+    // four columns per lane need ~200 VGPRs (three column points x four columns + four interleaved chains): 8 waves; so do
+    // the faithful chains of two columns
+    const dim3 block((unsigned)(((NC == 4 || FAITHFUL) ? 512 : 1024) >> (two ? 1 : 0)));
+    K3Shape sh;
+    sh.nc = NC; sh.vec = vec; sh.skips = !vec; sh.mask_mode = m16 ? 2 : 1; sh.wt = wt; sh.faithful = FAITHFUL; sh.rows_per_task = CH;
+    sh.wgs_per_cu = two ? 2 : 1; sh.structs_per_segment = KS; sh.n_tasks = (unsigned)n_tasks; sh.tasks_per_wg = tasks_per_wg;
+    // one instantiation by its switches (the kernel's last argument: tasks a wave pulls at a time)
+    auto sweep = [&](auto nc_, auto vec_, auto m16_, auto wt_) {
+        constexpr int NC_ = nc_;
+        constexpr bool VEC_ = vec_, M16_ = m16_, WT_ = wt_;
+        static unsigned long long prep[2][1] = {{0}, {0}};   // (per instantiation of this lambda, i.e. per kernel)
+        char name[96];
+        snprintf(name, sizeof name, "k3_featurise<EXACT=%d,NC=%d,VEC=%d,M16=%d,WT=%d,FAITHFUL=%d>", (int)(c.exact_sqrt != 0), NC_, (int)VEC_, (int)M16_,
+                 (int)WT_, (int)FAITHFUL);
+        auto run = [&](auto kernel, unsigned long long (&prepared)[1]) {
+            return k3_go(go, "featurise", name, sh, kernel, &prepared, dim3(grid), block, dyn, 4u, c.xyz, c.amask, c.d_ca, c.d_cb, c.d_no, c.omega,
+                         c.theta, c.phi, c.m_ca, c.m_cb, c.m_no, N, c.A, CH, n_strips, n_chunks, (unsigned)n_tasks, tasks_per_wg, rcpN, KS,
+                         (int)slot_bytes, 1);
+        };
+        return c.exact_sqrt ? run(k3_featurise<true, NC_, VEC_, M16_, WT_, FAITHFUL>, prep[0])
+                            : run(k3_featurise<false, NC_, VEC_, M16_, WT_, FAITHFUL>, prep[1]);
+    };
+    using C2 = std::integral_constant<int, 2>;
+    using C4 = std::integral_constant<int, 4>;
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (wt && NC == 2) return sweep(C2{}, yes, yes, yes);
+    if (m16 && NC == 2) return sweep(C2{}, yes, yes, no);
+    if constexpr (CAN4) {
+        if (wt) return sweep(C4{}, yes, yes, yes);
+        if (m16) return sweep(C4{}, yes, yes, no);
+        if (NC == 4) return vec ? sweep(C4{}, yes, no, no) : sweep(C4{}, no, no, no);
     }
-    // the per-CU sweep: any N >= K3_FEATURISE_MIN_N whose rows fit in LDS
-#ifdef PS_K3_AB
-    static const int feat_min_n = getenv("PS_K3F_MIN_N") ? atoi(getenv("PS_K3F_MIN_N")) : K3_FEATURISE_MIN_N;
-#else
-    constexpr int feat_min_n = K3_FEATURISE_MIN_N;
-#endif
-    if (!simple && N >= feat_min_n && need <= K3_LDS_MAX && (alf & 3u) == 0 && (unsigned long long)N * N < (1ull << 31)) {
-        // vector float stores where rows and planes allow (else 64 consecutive floats per store instruction: any N);
-        // columns per lane by the lanes a strip wastes
-        constexpr bool CAN4 = K3_FEATURISE_NC4 && !FAITHFUL;
-        const K3fSweepLayout lay = k3f_sweep_layout<FAITHFUL>(N, alf);
-        const int NC = lay.nc;
-        const bool vec = lay.vec;
-        const bool m16 = vec && N % 16 == 0 && (alm & 15u) == 0;   // strip-local 16-byte mask stores: whole 16-column groups
-        // write-through where strips are whole and every store covers whole lines; same-box A/B, trace: N = 512 174 against 178 us,
-        // 256 181 / 187 -- but N = 480 (15 lines per row, a 224-column second strip) 239 against 212 and 160 308 / 297: there write-back
-        const bool wt = m16 && N % 128 == 0 && (alf & 127u) == 0 && (alm & 127u) == 0;
-        const int cus = go.cus;
-        const int n_strips = (N + 64 * NC - 1) / (64 * NC);
-        // a task is CH rows x one strip, the strips of a row chunk adjacent tasks: a workgroup's share has to be many tasks
-        // per wave whatever B and N are -- its waves wait for each other at every structure boundary for up to one task.
-        // Four rows with the M16 mask stores (four rows per instruction; rows are whole 64-byte segments there).  TWO
-        // otherwise: where rows are not whole segments, the segment a row's strips share and the one a row's end shares with
-        // the next row's start get their halves from adjacent tasks, i.e. from two waves up to a task apart -- with
-        // four-row tasks (~16 us) longer than a line stays in L2 at this store rate, so that half of them went out as two
-        // partial writes (2.2 % of the write requests at N = 500, none at N = 496: profiles/r04_featuriser_pmc.log);
-        // same-box A/B, trace: N = 500 260 -> 228 us, 511 264 -> 241, 255 238 -> 218.
-        const bool two_wg = (unsigned long long)B >= 4ull * cus;
-        // (chains of up to 64 residues in the 64-apart layout: eight rows, so that a lane's four chains are four row pairs)
-        const int CH = m16 ? 4 : (!vec && N <= 64) ? 8 : 2;
-        const int n_chunks = (N + CH - 1) / CH;
-        const unsigned long long n_tasks = (unsigned long long)n_chunks * n_strips * B;
-        if (n_tasks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-        // One workgroup per CU -- or, when a CU's share is four or more structures (chains of ~128 residues in large
-        // batches), TWO of half the width: staging a structure (two barriers, a round trip to L2 for its rows and column
-        // points) idles all of a workgroup's waves, and the other workgroup computes meanwhile.  Their LDS requests admit
-        // exactly one / two per CU.
-        const bool two = two_wg && need <= K3_LDS_TWO_PER_CU;
-        const int wgs = two ? 2 * cus : cus;
-        const unsigned tasks_per_wg = (unsigned)std::max<unsigned long long>((n_tasks + wgs - 1) / wgs, 4ull);
-        const unsigned grid = (unsigned)((n_tasks + tasks_per_wg - 1) / tasks_per_wg);
-        const size_t dyn = two ? K3_LDS_TWO_PER_CU : std::max(need, K3_LDS_ONE_PER_CU);
-        // structures per staging pass (round 5): what the LDS request holds, at most a quarter of a workgroup's share (so that
-        // the workgroups of a CU interleave their passes) -- short chains paid two barriers and a round trip to L2 per structure
-        const size_t slot_bytes = (need + 15) & ~(size_t)15;
-        const unsigned long long n_sub = (unsigned long long)n_chunks * n_strips;
-        const unsigned long long share = (tasks_per_wg + n_sub - 1) / n_sub + 1;
-#ifdef PS_K3_AB
-        static const int ks_max = getenv("PS_K3F_KS_MAX") ? atoi(getenv("PS_K3F_KS_MAX")) : 1 << 20;
-#else
-        constexpr int ks_max = 1 << 20;
-#endif
-        const int KS = (int)std::max<unsigned long long>(1, std::min<unsigned long long>(std::min<unsigned long long>(dyn / slot_bytes, (share + 3) / 4), (unsigned long long)ks_max));
-        const unsigned rcpN = (unsigned)((1ull << 32) / (unsigned)N);
-#ifdef PS_K3_AB
-        static const int pull = getenv("PS_K3F_PULL") ? std::max(1, atoi(getenv("PS_K3F_PULL"))) : 1;
-#else
-        constexpr int pull = 1;
-#endif
-        // four columns per lane need ~200 VGPRs (three column points x four columns + four interleaved chains): 8 waves; so do
-        // the faithful chains of two columns
-        const dim3 block((unsigned)(((NC == 4 || FAITHFUL) ? 512 : 1024) >> (two ? 1 : 0)));
-        K3Shape sh;
-        sh.nc = NC; sh.vec = vec; sh.skips = !vec; sh.mask_mode = m16 ? 2 : 1; sh.wt = wt; sh.faithful = FAITHFUL; sh.rows_per_task = CH;
-        sh.wgs_per_cu = two ? 2 : 1; sh.structs_per_segment = KS; sh.n_tasks = (unsigned)n_tasks; sh.tasks_per_wg = tasks_per_wg;
-#define K3F_GO(NC_, VEC_, M16_, WT_)                                                                                              \
-    return k3f_go<NC_, VEC_, M16_, WT_, FAITHFUL>(go, exact_sqrt != 0, sh, dim3(grid), block, dyn, xyz, atom_mask, d_ca, d_cb, d_no, omega, theta, \
-                                                  phi, d_ca_mask, d_cb_mask, d_no_mask, N, A, CH, n_strips, n_chunks, (unsigned)n_tasks,  \
-                                                  tasks_per_wg, rcpN, KS, (int)slot_bytes, pull)
-        if (wt && NC == 2) K3F_GO(2, true, true, true);
-        if (m16 && NC == 2) K3F_GO(2, true, true, false);
-        if constexpr (CAN4) {
-            if (wt) K3F_GO(4, true, true, true);
-            if (m16) K3F_GO(4, true, true, false);
-            if (NC == 4 && vec) K3F_GO(4, true, false, false);
-            if (NC == 4) K3F_GO(4, false, false, false);
-        }
-        if (vec) K3F_GO(2, true, false, false);
-        K3F_GO(2, false, false, false);
-#undef K3F_GO
-    }
-    const int IR = 16, thr1 = k3_one_column_threads(N);
+    return vec ? sweep(C2{}, yes, no, no) : sweep(C2{}, no, no, no);
+}
+
+template <bool FAITHFUL>
+int launch_featurise_one_column(const K3fCall& c, const K3Go& go) {
+    const int N = c.N, IR = 16, thr1 = k3_one_column_threads(N);
     const int n_tiles = (N + thr1 - 1) / thr1, n_chunks = (N + IR - 1) / IR;
-    const unsigned long long n_wg = (unsigned long long)n_tiles * n_chunks * B;
+    const unsigned long long n_wg = (unsigned long long)n_tiles * n_chunks * c.B;
     if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     char name[96];
-    snprintf(name, sizeof name, "k3_inter_residue_geometry<EXACT=%d,FAITHFUL=%d>", exact_sqrt, (int)FAITHFUL);
+    snprintf(name, sizeof name, "k3_inter_residue_geometry<EXACT=%d,FAITHFUL=%d>", c.exact_sqrt, (int)FAITHFUL);
     K3Shape sh;
     sh.faithful = FAITHFUL; sh.rows_per_task = IR;
     auto one = [&](auto kernel) {
-        return k3_go(go, "one_column", name, sh, kernel, nullptr, dim3((unsigned)n_wg), dim3(thr1), 0, 0u, xyz, atom_mask, d_ca, d_cb, d_no, omega,
-                     theta, phi, d_ca_mask, d_cb_mask, d_no_mask, N, A, IR, n_tiles, n_chunks);
+        return k3_go(go, "one_column", name, sh, kernel, nullptr, dim3((unsigned)n_wg), dim3(thr1), 0, 0u, c.xyz, c.amask, c.d_ca, c.d_cb, c.d_no,
+                     c.omega, c.theta, c.phi, c.m_ca, c.m_cb, c.m_no, N, c.A, IR, n_tiles, n_chunks);
     };
-    return exact_sqrt ? one(k3_inter_residue_geometry<true, FAITHFUL>) : one(k3_inter_residue_geometry<false, FAITHFUL>);
+    return c.exact_sqrt ? one(k3_inter_residue_geometry<true, FAITHFUL>) : one(k3_inter_residue_geometry<false, FAITHFUL>);
+}
+
+// exact_angles of the C ABI as for K3: bit 0 = FAITHFUL, bit 1 = the one-column kernel whatever the shape
+inline int k3f_run(const K3fCall& c, int exact_angles, const K3Go& go) {
+    const bool faithful = (exact_angles & 1) != 0, simple = (exact_angles & 2) != 0;
+    if (!simple && (faithful ? k3f_tiles_eligible<true>(c) : k3f_tiles_eligible<false>(c)))
+        return faithful ? launch_featurise_tiles<true>(c, go) : launch_featurise_tiles<false>(c, go);
+    if (!simple && k3f_sweep_eligible(c)) return faithful ? launch_featurise_sweep<true>(c, go) : launch_featurise_sweep<false>(c, go);
+    return faithful ? launch_featurise_one_column<true>(c, go) : launch_featurise_one_column<false>(c, go);
 }
 
 }  // namespace
@@ -1905,11 +1831,8 @@ extern "C" int ps_inter_residue_geometry_f32(const float* xyz, const uint8_t* at
         alf |= reinterpret_cast<uintptr_t>(p);
     for (const void* p : {(const void*)d_ca_mask, (const void*)d_cb_mask, (const void*)d_no_mask}) alm |= reinterpret_cast<uintptr_t>(p);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const K3Go go{s, nullptr, k3_cu_count(s)};
-    const bool simple = (exact_angles & 2) != 0;
-    if (exact_angles & 1)
-        return k3f_run<true>(xyz, atom_mask, d_ca, d_cb, d_no, omega, theta, phi, d_ca_mask, d_cb_mask, d_no_mask, B, N, A, exact_sqrt, simple, alf & 127u, alm & 127u, go);
-    return k3f_run<false>(xyz, atom_mask, d_ca, d_cb, d_no, omega, theta, phi, d_ca_mask, d_cb_mask, d_no_mask, B, N, A, exact_sqrt, simple, alf & 127u, alm & 127u, go);
+    const K3fCall c{xyz, atom_mask, d_ca, d_cb, d_no, omega, theta, phi, d_ca_mask, d_cb_mask, d_no_mask, B, N, A, exact_sqrt, alf & 127u, alm & 127u};
+    return k3f_run(c, exact_angles, K3Go{s, nullptr, k3_cu_count(s)});
 }
 
 extern "C" int ps_featuriser_plan_f32(int B, int N, int A, int float_misalign, int mask_misalign, int exact_sqrt, int exact_angles,
@@ -1919,26 +1842,7 @@ extern "C" int ps_featuriser_plan_f32(int B, int N, int A, int float_misalign, i
     if (const int e = k3f_check_args(B, N, A, exact_sqrt, exact_angles)) return e;
     if (float_misalign < 0 || float_misalign > 127 || mask_misalign < 0 || mask_misalign > 127) return (int)hipErrorInvalidValue;
     if (B == 0 || N == 0) return 0;
-    const K3Go go{nullptr, plan, cu_count > 0 ? cu_count : 256};
-    const bool simple = (exact_angles & 2) != 0;
-    if (exact_angles & 1)
-        return k3f_run<true>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, A, exact_sqrt, simple,
-                             (uintptr_t)float_misalign, (uintptr_t)mask_misalign, go);
-    return k3f_run<false>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, A, exact_sqrt, simple,
-                          (uintptr_t)float_misalign, (uintptr_t)mask_misalign, go);
+    K3fCall c{};
+    c.B = B, c.N = N, c.A = A, c.exact_sqrt = exact_sqrt, c.alf = (uintptr_t)float_misalign, c.alm = (uintptr_t)mask_misalign;
+    return k3f_run(c, exact_angles, K3Go{nullptr, plan, cu_count > 0 ? cu_count : 256});
 }
-
-#ifdef PS_K3_AB
-// tools only: the stamps of the last k3_sweep launch on the current device (after a synchronise)
-extern "C" int ps_k3_debug_stamps(unsigned long long* host_dst, int n_words) {
-    if (!host_dst || n_words <= 0 || n_words > 512 * 16 * 4) return (int)hipErrorInvalidValue;
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(k3_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int ps_k3f_debug_probe(int mode) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(k3f_probe), &mode, sizeof mode, 0, hipMemcpyHostToDevice);
-}
-extern "C" int ps_k3f_debug_stamps(unsigned long long* host_dst, int n_words) {
-    if (!host_dst || n_words <= 0 || n_words > 512 * 8 * 16) return (int)hipErrorInvalidValue;
-    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(k3f_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif

@@ -37,6 +37,7 @@
 #include <cstdio>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -326,21 +327,6 @@ __device__ __forceinline__ float4 lds_atom(const float4* p) {
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// MATH: 0 = product arithmetic with the hardware sqrt, 1 = with the correctly rounded sqrt (cfg.exact_sqrt).
-// Builds made with -DPS_EXPERIMENTS (tools/ only, never the product library) add two timing experiments:
-//       2 = stores without any arithmetic (WRONG values);  3 = the first correctly rounded routine (same values as 1).
-template <int MATH>
-__device__ __forceinline__ float dist_pp_m(float4 p, float4 q) {
-#ifdef PS_EXPERIMENTS
-    if (MATH == 3) {
-        return sqrt_rn_pos(norm_sq3(p.x - q.x, p.y - q.y, p.z - q.z));
-    }
-#else
-    static_assert(MATH == 0 || MATH == 1, "experiment modes are compiled only with -DPS_EXPERIMENTS");
-#endif
-    return MATH == 0 ? dist_pp<false>(p, q) : dist_pp<true>(p, q);
-}
-
 // The pattern kernel's per-lane slot decode is the same for every workgroup, so it is a compile-time table
 // (one 16-byte load per lane instead of ~90 VALU instructions of divisions by 225 and 15):
 //   offj: byte k = column atom (jo * RS + c) of element 4 t + k inside a 4-residue group   (float4 slot index in LDS)
@@ -379,7 +365,7 @@ __device__ __forceinline__ uint32_t res_bits(const uint32_t* sbits, unsigned r) 
     return __funnelshift_r(sbits[o >> 5], sbits[(o >> 5) + 1], o & 31u) & 0x7FFFu;
 }
 
-template <int JT, bool NT, int MATH, bool UNROLL>
+template <int JT, bool NT, bool EXACT>
 __global__ __launch_bounds__(256) void k1_pairdist_a15_pat(const float* __restrict__ xyz,
                                                            const uint8_t* __restrict__ amask,
                                                            float* __restrict__ dist, uint8_t* __restrict__ dmask,
@@ -480,31 +466,18 @@ __global__ __launch_bounds__(256) void k1_pairdist_a15_pat(const float* __restri
             const float4* xj = sxj;
             auto group = [&](int g) {
                 uint4 u;
-#ifdef PS_EXPERIMENTS
-                if (MATH == 2) {  // store-only timing run: WRONG values by design
-                    u = make_uint4(__float_as_uint(pi[0].x), __float_as_uint(pi[1].x), __float_as_uint(pi[2].x),
-                                   (unsigned)g);
-                } else
-#endif
-                {
-                    const float4* x = xj + g * (4 * RS);
-                    const float4 q0 = lds_atom(x + offj[0]), q1 = lds_atom(x + offj[1]);
-                    const float4 q2 = lds_atom(x + offj[2]), q3 = lds_atom(x + offj[3]);
-                    u.x = __float_as_uint(dist_pp_m<MATH>(pi[0], q0));
-                    u.y = __float_as_uint(dist_pp_m<MATH>(pi[1], q1));
-                    u.z = __float_as_uint(dist_pp_m<MATH>(pi[2], q2));
-                    u.w = __float_as_uint(dist_pp_m<MATH>(pi[3], q3));
-                }
+                const float4* x = xj + g * (4 * RS);
+                const float4 q0 = lds_atom(x + offj[0]), q1 = lds_atom(x + offj[1]);
+                const float4 q2 = lds_atom(x + offj[2]), q3 = lds_atom(x + offj[3]);
+                u.x = __float_as_uint(dist_pp<EXACT>(pi[0], q0));
+                u.y = __float_as_uint(dist_pp<EXACT>(pi[1], q1));
+                u.z = __float_as_uint(dist_pp<EXACT>(pi[2], q2));
+                u.w = __float_as_uint(dist_pp<EXACT>(pi[3], q3));
                 if (NT) store16<true>(ob + (size_t)g * (4 * AA15) + lo, u);
                 else run.store(4u * lo, (unsigned)g * (16u * AA15), u);
             };
-            if (UNROLL && ngroups == JT / 4) {  // full tile: straight-line code, stores issued back to back
-#pragma unroll
-                for (int g = 0; g < JT / 4; ++g) group(g);
-            } else {
 #pragma unroll 4
-                for (int g = 0; g < ngroups; ++g) group(g);
-            }
+            for (int g = 0; g < ngroups; ++g) group(g);
         }
     }
 
@@ -1657,6 +1630,18 @@ struct K1Go {
     ps_k1_plan* plan;   // non-null: record only, launch nothing
 };
 
+// The arguments of one call.  The host tests the pointers for NULL and for their low four bits only (ps_k1_plan_f32
+// passes stand-in addresses).
+struct K1Call {
+    const float* xyz;
+    const uint8_t* amask;
+    float* dist;
+    uint8_t* dmask;
+    int B, N, A, row_begin, row_end, out_rows, out_row_origin;
+    int rows() const { return row_end - row_begin; }
+    bool full_matrix() const { return row_begin == 0 && row_end == N && out_rows == N && out_row_origin == 0; }
+};
+
 inline void plan_append(char* dst, size_t cap, const char* text) {
     size_t n = strlen(dst);
     if (n && n + 3 < cap) {
@@ -1702,20 +1687,32 @@ inline int k1_go(const K1Go& go, const char* family, const char* name, int tpara
     return 0;
 }
 
+// Run-time booleans to template arguments: `f` is a generic lambda and receives one std::true_type / std::false_type per
+// flag, in order.  Every combination of the flags is instantiated, so a launch site lifts only flags of which both values
+// are product kernels.
+template <typename F>
+inline int lift(F&& f) {
+    return f();
+}
+template <typename F, typename... Bs>
+inline int lift(F&& f, bool b, Bs... rest) {
+    return lift([&](auto... cs) { return b ? f(std::true_type{}, cs...) : f(std::false_type{}, cs...); }, rest...);
+}
+
+// Both planes start on a 16-byte boundary (a NULL plane counts as aligned): every family but the slot-decode and the
+// element-per-lane kernels needs it.
+inline bool planes_aligned(const float* dist, const uint8_t* dmask) {
+    return !((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15));
+}
+
 template <int JT>
-int launch_a15(const K1Cfg& g, const float* xyz, const uint8_t* amask, float* dist, uint8_t* dmask, int B, int N,
-               int row_begin, int row_end, int out_rows, int out_row_origin, const K1Go& go) {
-    const int IR = g.rows_per_block;
-    const int rows = row_end - row_begin;
-    dim3 grid((N + JT - 1) / JT, (rows + IR - 1) / IR, B);
+int launch_a15(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    const int N = c.N, IR = g.rows_per_block;
+    dim3 grid((N + JT - 1) / JT, (c.rows() + IR - 1) / IR, c.B);
     size_t lds = (size_t)(JT + IR) * A15 * sizeof(float4) + (size_t)(JT + 4 + IR) * sizeof(uint32_t);
-    const bool da = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(dist) & 15) == 0);
-    const bool ma = (N % 16 == 0) && ((reinterpret_cast<uintptr_t>(dmask) & 15) == 0);
+    const bool da = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(c.dist) & 15) == 0);
+    const bool ma = (N % 16 == 0) && ((reinterpret_cast<uintptr_t>(c.dmask) & 15) == 0);
     const bool ex = g.exact_sqrt != 0;
-#define PS_K1_LAUNCH1(NT_, DA_, MA_, EX_)                                                                         \
-    k1_go(go, "slot_decode", "k1_pairdist_a15", JT, k1_pairdist_a15<JT, NT_, DA_, MA_, EX_>, grid, dim3(256), lds, xyz, \
-          amask, dist, dmask, N, row_begin, row_end, out_rows, out_row_origin, IR)
-#define PS_K1_LAUNCH(NT_, DA_, MA_) (ex ? PS_K1_LAUNCH1(NT_, DA_, MA_, true) : PS_K1_LAUNCH1(NT_, DA_, MA_, false))
     if (da && ma && g.variant == 0) {
         // LDS: padded float4 images of the JT column and IR row residues, then the two mask bit streams (at most
         // (JT * 15 / 256 + 1) * 8 + (IR * 15 / 256 + 1) * 8 + 1 words, which JT + 4 + IR words always cover for JT >= 32)
@@ -1724,102 +1721,116 @@ int launch_a15(const K1Cfg& g, const float* xyz, const uint8_t* amask, float* di
         const unsigned long long n_wg = (unsigned long long)grid.x * grid.y * grid.z;
         if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
         const int remap = (g.xcd_remap && n_wg % 8 == 0 && n_wg >= 64) ? 1 : 0;
-#define PS_K1_PAT(NT_, M_, U_)                                                                                    \
-    k1_go(go, "pattern", "k1_pairdist_a15_pat", JT, k1_pairdist_a15_pat<JT, NT_, M_, U_>, dim3((unsigned)n_wg),   \
-          dim3(256), lds_pat, xyz, amask, dist, dmask, N, row_begin, row_end, out_rows, out_row_origin, IR,       \
-          (int)grid.x, (int)grid.y, remap)
-#ifdef PS_EXPERIMENTS
-        const int math = g.experiment & 15;
-        const bool unroll = (g.experiment & 16) != 0;
-        if (math == 1) return PS_K1_PAT(false, 3, false);
-        if (math == 2) return unroll ? PS_K1_PAT(false, 2, true) : PS_K1_PAT(false, 2, false);
-        if (unroll) return ex ? PS_K1_PAT(false, 1, true) : PS_K1_PAT(false, 0, true);
-#endif
-        if (g.store_nt) return ex ? PS_K1_PAT(true, 1, false) : PS_K1_PAT(true, 0, false);
-        return ex ? PS_K1_PAT(false, 1, false) : PS_K1_PAT(false, 0, false);
-#undef PS_K1_PAT
+        return lift([&](auto nt, auto exact) {
+            return k1_go(go, "pattern", "k1_pairdist_a15_pat", JT, k1_pairdist_a15_pat<JT, nt, exact>,
+                         dim3((unsigned)n_wg), dim3(256), lds_pat, c.xyz, c.amask, c.dist, c.dmask, N, c.row_begin,
+                         c.row_end, c.out_rows, c.out_row_origin, IR, (int)grid.x, (int)grid.y, remap);
+        }, g.store_nt != 0, ex);
     }
-    if (B > 65535) return (int)hipErrorInvalidValue;   // slot-decode kernel: structure on grid.z
-    if (da && ma) return g.store_nt ? PS_K1_LAUNCH(true, true, true) : PS_K1_LAUNCH(false, true, true);
-    if (da) return PS_K1_LAUNCH(true, true, false);
-    return PS_K1_LAUNCH(true, false, false);
-#undef PS_K1_LAUNCH
-#undef PS_K1_LAUNCH1
+    if (c.B > 65535) return (int)hipErrorInvalidValue;   // slot-decode kernel: structure on grid.z
+    auto slot_decode = [&](auto nt, auto da_, auto ma_) {   // (only the four combinations below are instantiated)
+        constexpr bool NT = nt, DA = da_, MA = ma_;
+        return lift([&](auto exact) {
+            return k1_go(go, "slot_decode", "k1_pairdist_a15", JT, k1_pairdist_a15<JT, NT, DA, MA, exact>, grid, dim3(256),
+                         lds, c.xyz, c.amask, c.dist, c.dmask, N, c.row_begin, c.row_end, c.out_rows, c.out_row_origin, IR);
+        }, ex);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (da && ma) return g.store_nt ? slot_decode(yes, yes, yes) : slot_decode(no, yes, yes);
+    if (da) return slot_decode(yes, yes, no);
+    return slot_decode(yes, no, no);
 }
 
-// Flat pattern kernel over the output pair range [pbeg, pend) (pair index P = (b*out_rows + il)*N + j).
-bool flat_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, int B, int N, int out_rows) {
+// A row range as the flat kernels take it: pair ranges [pbeg, pend) + k * stride, k < n_ranges, on the flat pair axis
+// P = (b * out_rows + il) * N + j.  One contiguous range when every output row is computed, else the same rows of every
+// structure.
+struct FlatRanges {
+    unsigned pbeg, pend, n_ranges, stride;
+    bool empty() const { return pbeg >= pend || n_ranges == 0; }
+    // chunks of 2^L2 pairs per range: exact for one range, an upper bound when the ranges start at different chunk phases
+    unsigned chunks(int L2) const {
+        return n_ranges == 1 ? ((pend + ((1u << L2) - 1)) >> L2) - (pbeg >> L2) : ((pend - pbeg) >> L2) + 2;
+    }
+};
+inline FlatRanges flat_ranges(const K1Call& c) {
+    const unsigned N = (unsigned)c.N;
+    if (c.rows() == c.out_rows) return {0u, (unsigned)((unsigned long long)c.B * c.out_rows * c.N), 1u, 0u};
+    const unsigned r0 = (unsigned)(c.row_begin - c.out_row_origin) * N;
+    return {r0, r0 + (unsigned)c.rows() * N, (unsigned)c.B, (unsigned)c.out_rows * N};
+}
+
+// Flat pattern kernel over the output pair ranges of the call.
+bool flat_eligible(const K1Cfg& g, const K1Call& c) {
+    const int N = c.N, out_rows = c.out_rows;
     if (g.variant != 0 || g.flat == 0) return false;
     if (N < 16 || N >= (1 << 22) || out_rows < 1 || out_rows >= (1 << 22)) return false;
-    if ((unsigned long long)B * out_rows * N > 0xFFFFFF00ull) return false;  // pair indices stay 32-bit
-    if ((unsigned long long)B * N * (A15 * 3) >= 0x80000000ull) return false;  // and so do coordinate indices
-    if ((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15)) return false;
+    if ((unsigned long long)c.B * out_rows * N > 0xFFFFFF00ull) return false;  // pair indices stay 32-bit
+    if ((unsigned long long)c.B * N * (A15 * 3) >= 0x80000000ull) return false;  // and so do coordinate indices
+    if (!planes_aligned(c.dist, c.dmask)) return false;
     return g.flat == 2 || N % 16 != 0;
 }
 
-int launch_a15_flat(const K1Cfg& g, const float* xyz, const uint8_t* amask, float* dist, uint8_t* dmask, int B,
-                    int N, int out_rows, int out_row_origin, unsigned pbeg, unsigned pend, unsigned n_ranges,
-                    unsigned range_stride, const K1Go& go) {
-    if (pbeg >= pend || n_ranges == 0) return 0;
-    // chunks per range: exact for one range, an upper bound when the ranges start at different chunk phases
+int launch_a15_flat(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    const FlatRanges r = flat_ranges(c);
+    if (r.empty()) return 0;
     // default chunk: 64 pairs (72 KB + 18 KB of output per workgroup): with the round-3 inner loop 4 % ahead of 128 pairs on
     // slow and medium buffers and equal on fast ones (profiles/r03_k1_flat_chunk_sweep_final.log); 32 pairs: +8 % / -3 to -10 %
     const int L2 = g.flat_fl_log2 ? g.flat_fl_log2 : 6;
-    const unsigned FL = 1u << L2;
-    const unsigned cpr = n_ranges == 1 ? ((pend + (FL - 1)) >> L2) - (pbeg >> L2) : ((pend - pbeg) >> L2) + 2;
-    const unsigned long long n_chunks = (unsigned long long)n_ranges * cpr;
+    const unsigned cpr = r.chunks(L2);
+    const unsigned long long n_chunks = (unsigned long long)r.n_ranges * cpr;
     if (n_chunks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     // like rows_per_block this depends on the output allocation: four chunks per workgroup are 1-2 % faster on some
     // and 8 % slower on others (profiles/r01_k1_ab_flat_cpw.log), so the default is 1 and ops.py autotunes it
     const unsigned cpw = (n_chunks >= 16384u) ? (unsigned)g.flat_cpw : 1u;
     const unsigned n_wg = (unsigned)((n_chunks + cpw - 1) / cpw);
     const int remap = (g.xcd_remap && n_wg >= 64) ? 1 : 0;
-    const double rn = 1.0 / (double)N, rr = 1.0 / (double)out_rows;
+    const double rn = 1.0 / (double)c.N, rr = 1.0 / (double)c.out_rows;
     const size_t pad = (size_t)g.flat_lds_pad_kb * 1024;  // idle dynamic LDS: residency cap
-#define PS_K1_FLAT2(EX_, HM_, L_)                                                                                 \
-    k1_go(go, "flat", "k1_pairdist_a15_flat", 1 << L_, k1_pairdist_a15_flat<EX_, HM_, L_>, dim3(n_wg), dim3(256),     \
-          K1Lds(pad, (unsigned)((((1 << L_) + FR) * RS) * sizeof(float4) + (2 * (1 << L_) + FR) * sizeof(uint32_t))),    \
-          xyz, amask, dist, dmask, B, N, out_rows, out_row_origin, pbeg, pend, n_ranges, range_stride, cpr,       \
-          (int)cpw, remap, rn, rr)
-#define PS_K1_FLAT(EX_, HM_)                                                                                      \
-    (L2 == 7 ? PS_K1_FLAT2(EX_, HM_, 7) : L2 == 6 ? PS_K1_FLAT2(EX_, HM_, 6) : L2 == 5 ? PS_K1_FLAT2(EX_, HM_, 5)  \
-                                                                              : PS_K1_FLAT2(EX_, HM_, 4))
-    if (g.exact_sqrt) return amask ? PS_K1_FLAT(true, true) : PS_K1_FLAT(true, false);
-    return amask ? PS_K1_FLAT(false, true) : PS_K1_FLAT(false, false);
-#undef PS_K1_FLAT
-#undef PS_K1_FLAT2
+    auto chunk = [&](auto l2) {
+        constexpr int L = l2, FL = 1 << L;
+        return lift([&](auto exact, auto hasmask) {
+            return k1_go(go, "flat", "k1_pairdist_a15_flat", FL, k1_pairdist_a15_flat<exact, hasmask, L>,
+                         dim3(n_wg), dim3(256),
+                         K1Lds(pad, (unsigned)(((FL + FR) * RS) * sizeof(float4) + (2 * FL + FR) * sizeof(uint32_t))),
+                         c.xyz, c.amask, c.dist, c.dmask, c.B, c.N, c.out_rows, c.out_row_origin, r.pbeg, r.pend,
+                         r.n_ranges, r.stride, cpr, (int)cpw, remap, rn, rr);
+        }, g.exact_sqrt != 0, c.amask != nullptr);
+    };
+    using std::integral_constant;
+    return L2 == 7   ? chunk(integral_constant<int, 7>{})
+           : L2 == 6 ? chunk(integral_constant<int, 6>{})
+           : L2 == 5 ? chunk(integral_constant<int, 5>{})
+                     : chunk(integral_constant<int, 4>{});
 }
 
 // Row-tile kernel (A = 4, 8): any N, any row range; planes must be 16-byte aligned.
-bool rowtile_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, int A) {
+bool rowtile_eligible(const K1Cfg& g, const K1Call& c) {
     if (g.variant != 0 || g.flat != 1) return false;   // flat = 4 forces the flat kernels (cross-checks), 0 the simple one
-    if (A != 4 && A != 8) return false;
-    return !((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15));
+    if (c.A != 4 && c.A != 8) return false;
+    return planes_aligned(c.dist, c.dmask);
 }
 
 template <int A>
-int launch_rowtile(const K1Cfg& g, const float* xyz, const uint8_t* amask, float* dist, uint8_t* dmask, int B, int N,
-                   int row_begin, int row_end, int out_rows, int out_row_origin, const K1Go& go) {
+int launch_rowtile(const K1Cfg& g, const K1Call& c, const K1Go& go) {
     constexpr int JT = RowTile<A>::JT;
-    const int rows = row_end - row_begin;
+    const int rows = c.rows();
     // Rows per workgroup: 6 (60 KB of output per workgroup).  Round 2 used 32; same-process sweeps of 2 .. 32 rows on two
     // boxes (profiles/r03_k1_rowtile_rows_per_workgroup.log) have 3-6 rows 3-12 % ahead of 32 at every shape (A = 4,
     // N = 500: 6.5-6.8 against 6.0 TB/s), 6 being the best or within 3 % of it also for short structures (N = 100 / 128),
     // where 2-4 rows lose.  cfg.rows_per_block > 1 overrides (A/B runs).
     const int irmax = g.rows_per_block > 1 ? g.rows_per_block : 6;
     const int IR = rows < irmax ? rows : irmax;
-    const int n_tiles = (N + JT - 1) / JT, n_ichunks = (rows + IR - 1) / IR;
-    const unsigned long long n_wg = (unsigned long long)n_tiles * n_ichunks * B;
+    const int n_tiles = (c.N + JT - 1) / JT, n_ichunks = (rows + IR - 1) / IR;
+    const unsigned long long n_wg = (unsigned long long)n_tiles * n_ichunks * c.B;
     if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const int remap = (g.xcd_remap && n_wg % 8 == 0 && n_wg >= 64) ? 1 : 0;
     const size_t lds = (size_t)(JT + IR) * A * sizeof(float4) + (size_t)(JT + IR) * sizeof(uint32_t);
-    if (g.exact_sqrt)
-        return k1_go(go, "rowtile", "k1_pairdist_rowtile", A, k1_pairdist_rowtile<A, true>, dim3((unsigned)n_wg), dim3(256),
-                     lds, xyz, amask, dist, dmask, N, row_begin, row_end, out_rows, out_row_origin, IR, n_tiles,
-                     n_ichunks, remap);
-    return k1_go(go, "rowtile", "k1_pairdist_rowtile", A, k1_pairdist_rowtile<A, false>, dim3((unsigned)n_wg), dim3(256),
-                 lds, xyz, amask, dist, dmask, N, row_begin, row_end, out_rows, out_row_origin, IR, n_tiles, n_ichunks,
-                 remap);
+    return lift([&](auto exact) {
+        return k1_go(go, "rowtile", "k1_pairdist_rowtile", A, k1_pairdist_rowtile<A, exact>, dim3((unsigned)n_wg),
+                     dim3(256), lds, c.xyz, c.amask, c.dist, c.dmask, c.N, c.row_begin, c.row_end, c.out_rows,
+                     c.out_row_origin, IR, n_tiles, n_ichunks, remap);
+    }, g.exact_sqrt != 0);
 }
 
 // Row-phase kernel: every atom count up to 64 other than 4, 8 (row-tile kernel) and 15; any N, any row range.  The small
@@ -1828,7 +1839,8 @@ int launch_rowtile(const K1Cfg& g, const float* xyz, const uint8_t* amask, float
 // against the fixed-A flat and the A = 15 kernels), 2 = never (fixed-A flat / element kernels instead).
 bool flatA_has(int A);
 
-bool rowphase_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, int N, int A) {
+bool rowphase_eligible(const K1Cfg& g, const K1Call& c) {
+    const int N = c.N, A = c.A;
     const int mode = g.rowphase & 15;     // (bits 4..: A/B switches, see launch_rowphase)
     if (g.variant != 0 || g.flat != 1 || mode == 2) return false;
     if (A < 1 || A > 64 || A == 4 || A == 8) return false;
@@ -1836,7 +1848,7 @@ bool rowphase_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, 
                                                                        // shorter peptides take this kernel (1-D grid: any B)
     if (A != 15 && flatA_has(A) && mode != 1) return false;           // even counts with a fixed-A flat kernel
     if (N < 1 || (long long)N * A * A > (1ll << 28)) return false;   // slot and element indices of a row stay 32-bit
-    return !((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15));
+    return planes_aligned(c.dist, c.dmask);
 }
 
 // CA traces (A = 1) of 8 .. CA_FLAT_MAX_N residues, full matrices: the flat kernel (see k1_pairdist_ca_flat).  cfg.rowphase = 1
@@ -1845,12 +1857,23 @@ bool rowphase_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, 
 // 512 4.75 / 6.75 -- the flat kernel stages whole structures per 8192 elements, which stops paying once a structure is
 // longer than that.
 constexpr int CA_FLAT_MAX_N = 255;
-bool ca_flat_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, int B, int N, int A, int row_begin, int row_end,
-                      int out_rows, int out_row_origin) {
-    if (A != 1 || g.variant != 0 || g.flat != 1 || (g.rowphase & 15) != 0) return false;
-    if (N < 8 || N > CA_FLAT_MAX_N) return false;
-    if (row_begin != 0 || row_end != N || out_rows != N || out_row_origin != 0) return false;
-    return !((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15));
+bool ca_flat_eligible(const K1Cfg& g, const K1Call& c) {
+    if (c.A != 1 || g.variant != 0 || g.flat != 1 || (g.rowphase & 15) != 0) return false;
+    if (c.N < 8 || c.N > CA_FLAT_MAX_N) return false;
+    return c.full_matrix() && planes_aligned(c.dist, c.dmask);
+}
+
+int launch_ca_flat(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    const int N = c.N;
+    const unsigned long long total = (unsigned long long)c.B * N * N;
+    const unsigned long long n_wg = (total + 4ull * CA_CS - 1) / (4ull * CA_CS);
+    if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)ca_max_structs(N) * N * sizeof(float4);
+    const unsigned rcpNN = (unsigned)((1ull << 32) / (unsigned)(N * N)), rcpN = (unsigned)((1ull << 32) / (unsigned)N);
+    return lift([&](auto exact) {
+        return k1_go(go, "ca_flat", "k1_pairdist_ca_flat", -1, k1_pairdist_ca_flat<exact>, dim3((unsigned)n_wg),
+                     dim3(256), lds, c.xyz, c.amask, c.dist, c.dmask, c.B, N, rcpNN, rcpN);
+    }, g.exact_sqrt != 0);
 }
 
 // Short chains of 2 .. 16 atoms per residue, full matrices: the flat kernel above up to the length where the row kernels catch up
@@ -1860,19 +1883,32 @@ bool ca_flat_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, i
 // 16 5.2 / 4.4, 24 4.8 / 6.6).  cfg.rowphase = 1 keeps the row-phase / row-tile kernels (A/B runs).
 // (A = 14 .. 16, TB/s flat / row-phase: N = 4 5.2-5.8 / 3.3-4.0, N = 8 .. 15 within 5 % of each other: up to seven residues)
 inline int small_flat_max_n(int A) { return A <= 4 ? 64 : A == 5 ? 31 : A == 6 ? 24 : A == 7 ? 20 : A == 8 ? 8 : A <= 13 ? 16 : 7; }
-bool small_flat_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, int B, int N, int A, int row_begin, int row_end,
-                         int out_rows, int out_row_origin) {
-    if (A < 2 || A > 16 || g.variant != 0 || g.flat != 1 || (g.rowphase & 15) != 0) return false;
-    if (N < 2 || N > small_flat_max_n(A)) return false;
-    if (row_begin != 0 || row_end != N || out_rows != N || out_row_origin != 0) return false;
-    return !((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15));
+bool small_flat_eligible(const K1Cfg& g, const K1Call& c) {
+    if (c.A < 2 || c.A > 16 || g.variant != 0 || g.flat != 1 || (g.rowphase & 15) != 0) return false;
+    if (c.N < 2 || c.N > small_flat_max_n(c.A)) return false;
+    return c.full_matrix() && planes_aligned(c.dist, c.dmask);
+}
+
+int launch_small_flat(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    const int N = c.N, A = c.A;
+    const unsigned S = (unsigned)N * N * A * A;
+    const unsigned long long total = (unsigned long long)c.B * S;
+    const unsigned long long n_wg = (total + 4ull * CA_CS - 1) / (4ull * CA_CS);
+    if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    const size_t lds = (size_t)((4 * CA_CS + S - 1) / S + 1) * N * A * sizeof(float4);   // the structures a workgroup's slots can touch
+    auto rcp = [](unsigned d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / d); };
+    const unsigned rcpS = rcp(S), rcpR = rcp((unsigned)N * A * A), rcpAA = rcp((unsigned)A * A), rcpA = rcp((unsigned)A);
+    return lift([&](auto exact) {
+        return k1_go(go, "small_flat", "k1_pairdist_small_flat", A, k1_pairdist_small_flat<exact>,
+                     dim3((unsigned)n_wg), dim3(256), lds, c.xyz, c.amask, c.dist, c.dmask, c.B, N, A, rcpS, rcpR, rcpAA,
+                     rcpA);
+    }, g.exact_sqrt != 0);
 }
 
 template <int ACT>
-int launch_rowphase(const K1Cfg& g, const float* xyz, const uint8_t* amask, float* dist, uint8_t* dmask, int B, int N,
-                    int A, int row_begin, int row_end, int out_rows, int out_row_origin, const K1Go& go) {
+int launch_rowphase(const K1Cfg& g, const K1Call& c, const K1Go& go) {
     using T = RowPhase<ACT>;
-    const int rows = row_end - row_begin;
+    const int N = c.N, A = c.A, rows = c.rows();
     const int nel = N * A * A;
     const int nslots = (nel + 3 + ((nel & 3) == 0 ? 0 : (nel & 3) == 2 ? 2 : 3)) / 4;   // over the phases that occur
     // short rows: 2 or 4 row groups of 128 / 64 lanes (every lane still takes ~32 rows), see the kernel
@@ -1893,7 +1929,7 @@ int launch_rowphase(const K1Cfg& g, const float* xyz, const uint8_t* amask, floa
     // for a pass: A = 5, N = 500 ran 4.4 against 5.2 TB/s.)
     const int n_tiles = (nslots + tile_slots - 1) / tile_slots;
     const int spt = tile_slots;
-    const unsigned long long n_wg = (unsigned long long)n_tiles * n_ichunks * B;
+    const unsigned long long n_wg = (unsigned long long)n_tiles * n_ichunks * c.B;
     if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const int remap = (g.xcd_remap && n_wg >= 64) ? 1 : 0;
     const int maxres = rowphase_maxres(A, N);
@@ -1904,14 +1940,22 @@ int launch_rowphase(const K1Cfg& g, const float* xyz, const uint8_t* amask, floa
     const unsigned rcpAA = (unsigned)((1ull << 32) / (unsigned)(A * A)), rcpA = (unsigned)((1ull << 32) / (unsigned)A);   // (A = 1: unused)
     const int tp = ACT > 0 ? ACT : A;     // what the plan prints: the atom count
     const char* name = ACT > 0 ? "k1_pairdist_rowphase" : (ACT == 0 ? "k1_pairdist_rowphase_rt_even" : "k1_pairdist_rowphase_rt_odd");
-    if (g.exact_sqrt)
-        return k1_go(go, "rowphase", name, tp, k1_pairdist_rowphase<ACT, true>, dim3((unsigned)n_wg), dim3(256), lds, xyz,
-                     amask, dist, dmask, N, A, row_begin, row_end, out_rows, out_row_origin, IR, n_tiles, spt, n_ichunks,
-                     lpg_log2, remap, flags, rcpAA, rcpA);
-    return k1_go(go, "rowphase", name, tp, k1_pairdist_rowphase<ACT, false>, dim3((unsigned)n_wg), dim3(256), lds, xyz,
-                 amask, dist, dmask, N, A, row_begin, row_end, out_rows, out_row_origin, IR, n_tiles, spt, n_ichunks,
-                 lpg_log2, remap, flags, rcpAA, rcpA);
+    return lift([&](auto exact) {
+        return k1_go(go, "rowphase", name, tp, k1_pairdist_rowphase<ACT, exact>, dim3((unsigned)n_wg), dim3(256),
+                     lds, c.xyz, c.amask, c.dist, c.dmask, N, A, c.row_begin, c.row_end, c.out_rows, c.out_row_origin, IR,
+                     n_tiles, spt, n_ichunks, lpg_log2, remap, flags, rcpAA, rcpA);
+    }, g.exact_sqrt != 0);
 }
+
+// The compile-time instantiation of the atom count where there is one (25: the reference's own test count; 37: atom37; 15:
+// N < 16, or N >= 16 with cfg.rowphase = 1: the A/B against the pattern kernels), else the run-time one of its parity.
+template <int... As>
+int launch_rowphase_any(const K1Cfg& g, const K1Call& c, const K1Go& go, std::integer_sequence<int, As...>) {
+    int rc = 0;
+    if (((c.A == As ? (rc = launch_rowphase<As>(g, c, go), true) : false) || ...)) return rc;
+    return (c.A & 1) ? launch_rowphase<-1>(g, c, go) : launch_rowphase<0>(g, c, go);
+}
+using RowPhaseCounts = std::integer_sequence<int, 1, 2, 3, 5, 6, 7, 9, 10, 11, 12, 13, 15, 25, 37>;
 
 // Fixed-A flat pattern kernels: the EVEN atom counts 14 (atom14), 16, 24, 32, where their line-aligned chunks make them
 // as fast as the row-phase kernel on aligned lengths and faster on the others (profiles/
@@ -1920,38 +1964,85 @@ int launch_rowphase(const K1Cfg& g, const float* xyz, const uint8_t* amask, floa
 // is instantiated so that the template can be cross-checked against the hand-specialised A = 15 kernels (cfg.flat == 4).
 bool flatA_has(int A) { return A == 14 || A == 15 || A == 16 || A == 24 || A == 32; }
 
-bool flatA_eligible(const K1Cfg& g, const float* dist, const uint8_t* dmask, int B, int N, int A, int out_rows) {
+bool flatA_eligible(const K1Cfg& g, const K1Call& c) {
+    const int N = c.N, A = c.A, out_rows = c.out_rows;
     if (g.variant != 0 || g.flat == 0 || !flatA_has(A)) return false;
     if (A == 15 && g.flat != 4) return false;   // A = 15 has its own kernels
     if (N < 16 || N >= (1 << 22) || out_rows < 1 || out_rows >= (1 << 22)) return false;
-    if ((unsigned long long)B * out_rows * N > 0xFFFFFF00ull) return false;      // pair indices stay 32-bit
-    if ((unsigned long long)B * N * A * 3 >= 0x80000000ull) return false;        // and so do coordinate indices
-    if ((reinterpret_cast<uintptr_t>(dist) & 15) || (reinterpret_cast<uintptr_t>(dmask) & 15)) return false;
-    return true;
+    if ((unsigned long long)c.B * out_rows * N > 0xFFFFFF00ull) return false;      // pair indices stay 32-bit
+    if ((unsigned long long)c.B * N * A * 3 >= 0x80000000ull) return false;        // and so do coordinate indices
+    return planes_aligned(c.dist, c.dmask);
 }
 
 template <int A>
-int launch_flatA(const K1Cfg& g, const float* xyz, const uint8_t* amask, float* dist, uint8_t* dmask, int B, int N,
-                 int out_rows, int out_row_origin, unsigned pbeg, unsigned pend, unsigned n_ranges,
-                 unsigned range_stride, const K1Go& go) {
-    if (pbeg >= pend || n_ranges == 0) return 0;
-    constexpr int L2 = FlatA<A>::FL_LOG2, FLn = FlatA<A>::FLn;
-    const unsigned cpr = n_ranges == 1 ? ((pend + (FLn - 1)) >> L2) - (pbeg >> L2) : ((pend - pbeg) >> L2) + 2;
-    const unsigned long long n_chunks = (unsigned long long)n_ranges * cpr;
+int launch_flatA(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    using T = FlatA<A>;
+    const FlatRanges r = flat_ranges(c);
+    if (r.empty()) return 0;
+    const unsigned cpr = r.chunks(T::FL_LOG2);
+    const unsigned long long n_chunks = (unsigned long long)r.n_ranges * cpr;
     if (n_chunks > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const unsigned cpw = (n_chunks >= 16384u) ? (unsigned)g.flat_cpw : 1u;
     const unsigned n_wg = (unsigned)((n_chunks + cpw - 1) / cpw);
     const int remap = (g.xcd_remap && n_wg >= 64) ? 1 : 0;
-    const double rn = 1.0 / (double)N, rr = 1.0 / (double)out_rows;
-#define PS_K1_FLATA(EX_, HM_)                                                                                     \
-    k1_go(go, "flatA", "k1_pairdist_flatA", A, k1_pairdist_flatA<A, EX_, HM_>, dim3(n_wg), dim3(256),             \
-          K1Lds(0, (unsigned)((FlatA<A>::FLn + FlatA<A>::FRn) * FlatA<A>::RS * sizeof(float4) +                      \
-                              (2 * FlatA<A>::FLn + FlatA<A>::FRn) * sizeof(typename FlatA<A>::mask_t))), xyz,       \
-          amask, dist, dmask, B, N, out_rows, out_row_origin, pbeg, pend, n_ranges, range_stride, cpr, (int)cpw,  \
-          remap, rn, rr)
-    if (g.exact_sqrt) return amask ? PS_K1_FLATA(true, true) : PS_K1_FLATA(true, false);
-    return amask ? PS_K1_FLATA(false, true) : PS_K1_FLATA(false, false);
-#undef PS_K1_FLATA
+    const double rn = 1.0 / (double)c.N, rr = 1.0 / (double)c.out_rows;
+    return lift([&](auto exact, auto hasmask) {
+        return k1_go(go, "flatA", "k1_pairdist_flatA", A, k1_pairdist_flatA<A, exact, hasmask>, dim3(n_wg),
+                     dim3(256),
+                     K1Lds(0, (unsigned)((T::FLn + T::FRn) * T::RS * sizeof(float4) +
+                                         (2 * T::FLn + T::FRn) * sizeof(typename T::mask_t))),
+                     c.xyz, c.amask, c.dist, c.dmask, c.B, c.N, c.out_rows, c.out_row_origin, r.pbeg, r.pend, r.n_ranges,
+                     r.stride, cpr, (int)cpw, remap, rn, rr);
+    }, g.exact_sqrt != 0, c.amask != nullptr);
+}
+
+int launch_flatA_any(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    switch (c.A) {
+        case 14: return launch_flatA<14>(g, c, go);
+        case 15: return launch_flatA<15>(g, c, go);
+        case 16: return launch_flatA<16>(g, c, go);
+        case 24: return launch_flatA<24>(g, c, go);
+        default: return launch_flatA<32>(g, c, go);   // (flatA_has: nothing else gets here)
+    }
+}
+
+// The A = 15 kernels for what the flat pattern kernel does not take: the pattern kernel on aligned planes with
+// N % 16 == 0, else the slot-decode kernel (launch_a15 chooses).  `g` by value: the row count per workgroup is resolved here.
+int launch_a15_any(K1Cfg g, const K1Call& c, const K1Go& go) {
+    const int N = c.N, rows = c.rows();
+    // N < 16 (peptides): a row run is at most 13.5 KB, so the slot-decode kernel takes up to 16 rows per workgroup
+    if (N < 16 && g.rows_per_block == 1) g.rows_per_block = rows < 16 ? rows : 16;
+    // short chains (16 <= N < 64): a workgroup that writes one row of one tile is mostly set-up, so rows_per_block = 1
+    // (the default) means "about 64 column residues' worth of rows": N = 16: 4 rows (6.7 against 4.3 TB/s), N = 32 and 48:
+    // 2 rows (6.8 against 5.0, 6.5 against 5.9; profiles/r03_k1_short_chains_rows.log); consecutive rows are contiguous
+    else if (N < 64 && g.rows_per_block == 1) g.rows_per_block = rows < (64 + N - 1) / N ? rows : (64 + N - 1) / N;
+    if ((rows + g.rows_per_block - 1) / g.rows_per_block > 65535) return (int)hipErrorInvalidValue;
+    // default tile: 32 column residues (36 KB + 9 KB of output per workgroup) at the default 20 KB of idle LDS = 5
+    // workgroups per CU: with the round-3 kernel the best or within 2 % of it on the output buffers of ten boxes (7.0-7.3
+    // TB/s fast class, 6.1-6.4 slow; 128-residue tiles + 8 KB, the default until then: 6.8-7.1 / 5.9)
+    // (a mask-only launch stages no coordinates and writes a quarter of the bytes per tile: 128-residue tiles run it at the
+    // fill rate of the plane, 6.8 TB/s, where 32-residue tiles are set-up bound at 5.4; profiles/r03_k1_plane_split_mask_only.log)
+    switch (g.jt ? g.jt : (c.dist ? 32 : 128)) {
+        case 128: return launch_a15<128>(g, c, go);
+        case 16: return launch_a15<16>(g, c, go);
+        case 32: return launch_a15<32>(g, c, go);
+        default: return launch_a15<64>(g, c, go);
+    }
+}
+
+// Element-per-lane kernel: whatever is left (A > 64, unaligned planes, cfg.flat = 0).
+int launch_element(const K1Cfg& g, const K1Call& c, const K1Go& go) {
+    const int rows = c.rows();
+    if (rows > 65535 || c.B > 65535) return (int)hipErrorInvalidValue;   // (row, structure) on grid.y / grid.z
+    const unsigned long long nE = (unsigned long long)c.N * c.A * c.A;
+    if (nE > 0xFFFFFFFFull) return (int)hipErrorInvalidValue;
+    unsigned gx = (unsigned)((nE + 255) / 256);
+    if (gx > 64) gx = 64;
+    return lift([&](auto exact) {
+        return k1_go(go, "element", "k1_pairdist_generic", -1, k1_pairdist_generic<exact>, dim3(gx, rows, c.B),
+                     dim3(256), 0, c.xyz, c.amask, c.dist, c.dmask, c.N, c.A, c.row_begin, c.row_end, c.out_rows,
+                     c.out_row_origin);
+    }, g.exact_sqrt != 0);
 }
 
 // Range checks of a caller-supplied configuration; the defaults pass by construction.
@@ -1963,11 +2054,7 @@ bool cfg_valid(const K1Cfg& g) {
     if (g.jt != 0 && g.jt != 16 && g.jt != 32 && g.jt != 64 && g.jt != 128) return false;
     if (g.flat_fl_log2 != 0 && (g.flat_fl_log2 < 4 || g.flat_fl_log2 > 7)) return false;
     if (g.rowphase < 0 || (g.rowphase & 15) > 2 || g.rowphase >= 256) return false;
-#ifdef PS_EXPERIMENTS
-    if (g.experiment < 0 || (g.experiment & 15) > 2 || g.experiment > 31) return false;
-#else
-    if (g.experiment != 0) return false;   // timing experiments do not exist in the product library
-#endif
+    if (g.experiment != 0) return false;   // reserved: the library contains no timing experiments
     return true;
 }
 
@@ -1990,126 +2077,28 @@ extern "C" void ps_k1_config_default(ps_k1_config* cfg) {
 namespace {
 
 // The one dispatcher: argument checks, then the first eligible kernel family in a fixed order.  `go` decides whether the
-// chosen kernel is launched or only recorded (ps_k1_plan_f32); pointers are used for their NULL-ness and alignment only.
-int k1_dispatch(const K1Go& go, const float* xyz, const uint8_t* atom_mask, float* dist, uint8_t* dist_mask, int B,
-                int N, int A, int row_begin, int row_end, int out_rows, int out_row_origin, const ps_k1_config* cfg) {
-    if (!xyz || (!dist && !dist_mask) || B < 0 || N < 0 || A <= 0) return (int)hipErrorInvalidValue;
-    if (row_begin < 0 || row_end > N || row_begin > row_end) return (int)hipErrorInvalidValue;
-    if (out_row_origin > row_begin || row_end - out_row_origin > out_rows) return (int)hipErrorInvalidValue;
+// chosen kernel is launched or only recorded (ps_k1_plan_f32).
+int k1_dispatch(const K1Go& go, const K1Call& c, const ps_k1_config* cfg) {
+    if (!c.xyz || (!c.dist && !c.dmask) || c.B < 0 || c.N < 0 || c.A <= 0) return (int)hipErrorInvalidValue;
+    if (c.row_begin < 0 || c.row_end > c.N || c.row_begin > c.row_end) return (int)hipErrorInvalidValue;
+    if (c.out_row_origin > c.row_begin || c.row_end - c.out_row_origin > c.out_rows) return (int)hipErrorInvalidValue;
     K1Cfg g;
     ps_k1_config_default(&g);
     if (cfg) {
         if (!cfg_valid(*cfg)) return (int)hipErrorInvalidValue;
         g = *cfg;   // by value: the caller may change or free its copy as soon as this call returns
     }
-    if (B == 0 || N == 0 || row_begin == row_end) return 0;
-    const int rows = row_end - row_begin;
-    if (small_flat_eligible(g, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin)) {
-        const unsigned S = (unsigned)N * N * A * A;
-        const unsigned long long total = (unsigned long long)B * S;
-        const unsigned long long n_wg = (total + 4ull * CA_CS - 1) / (4ull * CA_CS);
-        if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-        const size_t lds = (size_t)((4 * CA_CS + S - 1) / S + 1) * N * A * sizeof(float4);   // the structures a workgroup's slots can touch
-        auto rcp = [](unsigned d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / d); };
-        const unsigned rcpS = rcp(S), rcpR = rcp((unsigned)N * A * A), rcpAA = rcp((unsigned)A * A), rcpA = rcp((unsigned)A);
-        if (g.exact_sqrt)
-            return k1_go(go, "small_flat", "k1_pairdist_small_flat", A, k1_pairdist_small_flat<true>, dim3((unsigned)n_wg), dim3(256),
-                         lds, xyz, atom_mask, dist, dist_mask, B, N, A, rcpS, rcpR, rcpAA, rcpA);
-        return k1_go(go, "small_flat", "k1_pairdist_small_flat", A, k1_pairdist_small_flat<false>, dim3((unsigned)n_wg), dim3(256),
-                     lds, xyz, atom_mask, dist, dist_mask, B, N, A, rcpS, rcpR, rcpAA, rcpA);
-    }
-    if (rowtile_eligible(g, dist, dist_mask, A)) {
-        if (A == 4)
-            return launch_rowtile<4>(g, xyz, atom_mask, dist, dist_mask, B, N, row_begin, row_end, out_rows, out_row_origin, go);
-        return launch_rowtile<8>(g, xyz, atom_mask, dist, dist_mask, B, N, row_begin, row_end, out_rows, out_row_origin, go);
-    }
-    if (ca_flat_eligible(g, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin)) {
-        const unsigned long long total = (unsigned long long)B * N * N;
-        const unsigned long long n_wg = (total + 4ull * CA_CS - 1) / (4ull * CA_CS);
-        if (n_wg > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-        const size_t lds = (size_t)ca_max_structs(N) * N * sizeof(float4);
-        const unsigned rcpNN = (unsigned)((1ull << 32) / (unsigned)(N * N)), rcpN = (unsigned)((1ull << 32) / (unsigned)N);
-        if (g.exact_sqrt)
-            return k1_go(go, "ca_flat", "k1_pairdist_ca_flat", -1, k1_pairdist_ca_flat<true>, dim3((unsigned)n_wg), dim3(256), lds,
-                         xyz, atom_mask, dist, dist_mask, B, N, rcpNN, rcpN);
-        return k1_go(go, "ca_flat", "k1_pairdist_ca_flat", -1, k1_pairdist_ca_flat<false>, dim3((unsigned)n_wg), dim3(256), lds,
-                     xyz, atom_mask, dist, dist_mask, B, N, rcpNN, rcpN);
-    }
-    if (rowphase_eligible(g, dist, dist_mask, N, A)) {
-#define PS_K1_RP(A_) case A_: return launch_rowphase<A_>(g, xyz, atom_mask, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin, go);
-        switch (A) {
-            PS_K1_RP(1) PS_K1_RP(2) PS_K1_RP(3) PS_K1_RP(5) PS_K1_RP(6) PS_K1_RP(7) PS_K1_RP(9) PS_K1_RP(10) PS_K1_RP(11)
-            PS_K1_RP(12) PS_K1_RP(13) PS_K1_RP(25) PS_K1_RP(37)   // (25: the reference's own test count; 37: atom37)
-            PS_K1_RP(15)                                          // (N < 16; N >= 16 only with cfg.rowphase = 1: the A/B against the pattern kernels)
-            default: break;
-        }
-#undef PS_K1_RP
-        if (A & 1)
-            return launch_rowphase<-1>(g, xyz, atom_mask, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin, go);
-        return launch_rowphase<0>(g, xyz, atom_mask, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin, go);
-    }
-    if (flatA_eligible(g, dist, dist_mask, B, N, A, out_rows)) {
-        // one contiguous pair range when every output row is computed, else the same rows of every structure
-        const bool whole = rows == out_rows;
-        const unsigned r0 = whole ? 0u : (unsigned)(row_begin - out_row_origin) * (unsigned)N;
-        const unsigned r1 = whole ? (unsigned)((unsigned long long)B * out_rows * N) : r0 + (unsigned)rows * (unsigned)N;
-        const unsigned nrg = whole ? 1u : (unsigned)B, stride = whole ? 0u : (unsigned)out_rows * (unsigned)N;
-        switch (A) {
-            case 14: return launch_flatA<14>(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, r0, r1, nrg, stride, go);
-            case 15: return launch_flatA<15>(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, r0, r1, nrg, stride, go);
-            case 16: return launch_flatA<16>(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, r0, r1, nrg, stride, go);
-            case 24: return launch_flatA<24>(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, r0, r1, nrg, stride, go);
-            case 32: return launch_flatA<32>(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, r0, r1, nrg, stride, go);
-            default: break;
-        }
-    }
-    if (A == A15 && flat_eligible(g, dist, dist_mask, B, N, out_rows)) {
-        // one contiguous pair range when every output row is computed, else the same rows of every structure
-        if (rows == out_rows)
-            return launch_a15_flat(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, 0u,
-                                   (unsigned)((unsigned long long)B * out_rows * N), 1u, 0u, go);
-        const unsigned r0 = (unsigned)(row_begin - out_row_origin) * (unsigned)N;
-        return launch_a15_flat(g, xyz, atom_mask, dist, dist_mask, B, N, out_rows, out_row_origin, r0,
-                               r0 + (unsigned)rows * (unsigned)N, (unsigned)B, (unsigned)out_rows * (unsigned)N, go);
-    }
+    if (c.B == 0 || c.N == 0 || c.row_begin == c.row_end) return 0;
+    if (small_flat_eligible(g, c)) return launch_small_flat(g, c, go);
+    if (rowtile_eligible(g, c)) return c.A == 4 ? launch_rowtile<4>(g, c, go) : launch_rowtile<8>(g, c, go);
+    if (ca_flat_eligible(g, c)) return launch_ca_flat(g, c, go);
+    if (rowphase_eligible(g, c)) return launch_rowphase_any(g, c, go, RowPhaseCounts{});
+    if (flatA_eligible(g, c)) return launch_flatA_any(g, c, go);
+    if (c.A == A15 && flat_eligible(g, c)) return launch_a15_flat(g, c, go);
     // the flat kernels above and the pattern kernel run on 1-D grids and take any batch size; the slot-decode and the
     // element-per-lane kernels put the structure on grid.z (checked where they are launched)
-    if (A == A15) {
-        // N < 16 (peptides): a row run is at most 13.5 KB, so the slot-decode kernel takes up to 16 rows per workgroup
-        if (N < 16 && g.rows_per_block == 1) g.rows_per_block = rows < 16 ? rows : 16;
-        // short chains (16 <= N < 64): a workgroup that writes one row of one tile is mostly set-up, so rows_per_block = 1
-        // (the default) means "about 64 column residues' worth of rows": N = 16: 4 rows (6.7 against 4.3 TB/s), N = 32 and 48:
-        // 2 rows (6.8 against 5.0, 6.5 against 5.9; profiles/r03_k1_short_chains_rows.log); consecutive rows are contiguous
-        else if (N < 64 && g.rows_per_block == 1) g.rows_per_block = rows < (64 + N - 1) / N ? rows : (64 + N - 1) / N;
-        if ((rows + g.rows_per_block - 1) / g.rows_per_block > 65535) return (int)hipErrorInvalidValue;
-        // default tile: 32 column residues (36 KB + 9 KB of output per workgroup) at the default 20 KB of idle LDS = 5
-        // workgroups per CU: with the round-3 kernel the best or within 2 % of it on the output buffers of ten boxes (7.0-7.3
-        // TB/s fast class, 6.1-6.4 slow; 128-residue tiles + 8 KB, the default until then: 6.8-7.1 / 5.9)
-        // (a mask-only launch stages no coordinates and writes a quarter of the bytes per tile: 128-residue tiles run it at the
-        // fill rate of the plane, 6.8 TB/s, where 32-residue tiles are set-up bound at 5.4; profiles/r03_k1_plane_split_mask_only.log)
-        const int jt = g.jt ? g.jt : (dist ? 32 : 128);
-        if (jt == 128)
-            return launch_a15<128>(g, xyz, atom_mask, dist, dist_mask, B, N, row_begin, row_end, out_rows,
-                                   out_row_origin, go);
-        if (jt == 16)
-            return launch_a15<16>(g, xyz, atom_mask, dist, dist_mask, B, N, row_begin, row_end, out_rows, out_row_origin,
-                                  go);
-        if (jt == 32)
-            return launch_a15<32>(g, xyz, atom_mask, dist, dist_mask, B, N, row_begin, row_end, out_rows, out_row_origin,
-                                  go);
-        return launch_a15<64>(g, xyz, atom_mask, dist, dist_mask, B, N, row_begin, row_end, out_rows, out_row_origin,
-                              go);
-    }
-    if (rows > 65535 || B > 65535) return (int)hipErrorInvalidValue;   // element kernel: (row, structure) on grid.y / grid.z
-    const unsigned long long nE = (unsigned long long)N * A * A;
-    if (nE > 0xFFFFFFFFull) return (int)hipErrorInvalidValue;
-    unsigned gx = (unsigned)((nE + 255) / 256);
-    if (gx > 64) gx = 64;
-    if (g.exact_sqrt)
-        return k1_go(go, "element", "k1_pairdist_generic", -1, k1_pairdist_generic<true>, dim3(gx, rows, B), dim3(256), 0,
-                     xyz, atom_mask, dist, dist_mask, N, A, row_begin, row_end, out_rows, out_row_origin);
-    return k1_go(go, "element", "k1_pairdist_generic", -1, k1_pairdist_generic<false>, dim3(gx, rows, B), dim3(256), 0, xyz,
-                 atom_mask, dist, dist_mask, N, A, row_begin, row_end, out_rows, out_row_origin);
+    if (c.A == A15) return launch_a15_any(g, c, go);
+    return launch_element(g, c, go);
 }
 
 }  // namespace
@@ -2119,7 +2108,8 @@ extern "C" int ps_pairwise_distance_cfg_f32(const float* xyz, const uint8_t* ato
                                             int out_rows, int out_row_origin, const ps_k1_config* cfg,
                                             void* stream) {
     const K1Go go{reinterpret_cast<hipStream_t>(stream), nullptr};
-    return k1_dispatch(go, xyz, atom_mask, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin, cfg);
+    const K1Call c{xyz, atom_mask, dist, dist_mask, B, N, A, row_begin, row_end, out_rows, out_row_origin};
+    return k1_dispatch(go, c, cfg);
 }
 
 extern "C" int ps_k1_plan_f32(int B, int N, int A, int row_begin, int row_end, int out_rows, int out_row_origin,
@@ -2137,7 +2127,7 @@ extern "C" int ps_k1_plan_f32(int B, int N, int A, int row_begin, int row_end, i
     float* d = dist_misalign < 0 ? nullptr : reinterpret_cast<float*>(base + (uintptr_t)dist_misalign);
     uint8_t* m = mask_misalign < 0 ? nullptr : reinterpret_cast<uint8_t*>(base + (uintptr_t)mask_misalign);
     const K1Go go{nullptr, plan};
-    const int rc = k1_dispatch(go, xyz, am, d, m, B, N, A, row_begin, row_end, out_rows, out_row_origin, cfg);
+    const int rc = k1_dispatch(go, K1Call{xyz, am, d, m, B, N, A, row_begin, row_end, out_rows, out_row_origin}, cfg);
     if (rc == 0 && plan->n_launches == 0) {
         snprintf(plan->kernel, sizeof plan->kernel, "(nothing to launch)");
         snprintf(plan->family, sizeof plan->family, "empty");

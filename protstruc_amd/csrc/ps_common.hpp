@@ -32,29 +32,10 @@ __device__ __forceinline__ float dot3(f3 a, f3 b) {
     return ((0.0f + px) + py) + pz;
 }
 
-// Correctly rounded sqrt for x >= 0 without the subnormal pre-scaling of the
-// library routine: v_sqrt_f32 is within 1 ulp, so the answer is s-1ulp, s or
-// s+1ulp and two exact fma residuals pick it.  0, inf and NaN fall through
-// unchanged (every comparison with a NaN residual is false).  Checked against
-// sqrtf over every float in [0, +inf] (tools/microbench/sqrt_check.hip): equal
-// for every x >= 4.6e-32; below that (atoms closer than 2e-16) the residuals
-// underflow and the result can be 1 ulp off.  Kept as the cross-check of
-// sqrt_rn_mk below, which is what the kernels use.
-__device__ __forceinline__ float sqrt_rn_pos(float x) {
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float lo = __uint_as_float(__float_as_uint(s) - 1u);
-    const float hi = __uint_as_float(__float_as_uint(s) + 1u);
-    const float r_lo = __builtin_fmaf(-lo, s, x);
-    const float r_hi = __builtin_fmaf(-hi, s, x);
-    float r = s;
-    r = (r_lo <= 0.0f) ? lo : r;
-    r = (r_hi > 0.0f) ? hi : r;
-    return r;
-}
-
-// The same correctly rounded result from v_rsq_f32: one coupled Newton step for g ~ sqrt(x) and h ~ 1/(2 sqrt(x)),
+// Correctly rounded sqrt for x >= 0 from v_rsq_f32: one coupled Newton step for g ~ sqrt(x) and h ~ 1/(2 sqrt(x)),
 // then the exact-residual correction g + (x - g*g) * h (fma).  Every operation is a mul or an fma, so two elements
-// share one v_pk_* instruction: 4 + 3.5 + 2 issue slots per element against 4 + 9 for sqrt_rn_pos.  Zero, subnormal
+// share one v_pk_* instruction: 4 + 3.5 + 2 issue slots per element against 4 + 9 for a v_sqrt_f32 with two exact
+// residual tests (sqrt_rn_pos, the first routine; kept in tools/microbench/sqrt_check.hip as the cross-check).  Zero, subnormal
 // and +inf inputs are returned as x (sqrt(0) = 0 and sqrt(inf) = inf exactly; a subnormal squared distance means
 // atoms closer than 1e-19, error < 1.1e-19).  Checked against sqrtf over every float in [0, +inf]
 // (tools/microbench/sqrt_check.hip): equal for every x >= 2.0e-31 (atoms further apart than 4.5e-16), at most

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""profiles/k3_valu_bound.json (what bench.py's other_configs.config3 reports as valu_bound_us) from the SQ counter pass of
-tools/gpu_profile_r05.sh over `tools/profile_workload.py k3`:
+"""profiles/k3_valu_bound.json (what bench.py's other_configs.config3 reports as valu_bound_us) from an SQ counter pass
+(rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_VALU) over `tools/profile_workload.py k3`:
 
     python3 tools/make_k3_valu_bound.py <k3_pmc.json> <out.json> <round>
 

@@ -1,8 +1,10 @@
 // Exhaustive check of candidate fp32 square roots against the correctly rounded library sqrtf over every
 // non-negative float (0 .. +inf, 2^31 bit patterns): which candidates are correctly rounded everywhere?
-//   A: sqrt_rn_pos   (v_sqrt_f32 + two exact residual tests; the product routine in ps_common.hpp)
+//   A: sqrt_rn_pos   (v_sqrt_f32 + two exact residual tests; defined below: the product's first routine, kept here as
+//                     the cross-check of B)
 //   B: sqrt_rn_mk    (v_rsq_f32 + one coupled Newton step for g ~ sqrt(x), h ~ 1/(2 sqrt(x)) + exact residual
-//                     correction g + (x - g*g) * h; zero / subnormal / inf inputs returned as x)
+//                     correction g + (x - g*g) * h; zero / subnormal / inf inputs returned as x; the product routine in
+//                     ps_common.hpp)
 //   C: raw v_sqrt_f32 (how often, and by how much, is the hardware instruction itself off?)
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -11,6 +13,23 @@
 #include <cmath>
 #include <cstring>
 #include "../../protstruc_amd/csrc/ps_common.hpp"
+
+// Correctly rounded sqrt for x >= 0 without the subnormal pre-scaling of the library routine: v_sqrt_f32 is within 1 ulp, so
+// the answer is s-1ulp, s or s+1ulp and two exact fma residuals pick it.  0, inf and NaN fall through unchanged (every
+// comparison with a NaN residual is false).  Equal to sqrtf for every x >= 4.6e-32; below that the residuals underflow and
+// the result can be 1 ulp off.
+__device__ __forceinline__ float sqrt_rn_pos(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float lo = __uint_as_float(__float_as_uint(s) - 1u);
+    const float hi = __uint_as_float(__float_as_uint(s) + 1u);
+    const float r_lo = __builtin_fmaf(-lo, s, x);
+    const float r_hi = __builtin_fmaf(-hi, s, x);
+    float r = s;
+    r = (r_lo <= 0.0f) ? lo : r;
+    r = (r_hi > 0.0f) ? hi : r;
+    return r;
+}
+
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("ERR %s line %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 
 __global__ void check(unsigned long long* counts, unsigned* first_bad, unsigned* last_bad) {

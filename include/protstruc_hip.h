@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 8
+#define PS_ABI_VERSION 9
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -368,6 +368,29 @@ int ps_inter_residue_geometry_f32(const float* xyz, const uint8_t* atom_mask,
 /* The featuriser's twin of ps_k3_plan_f32 (ABI 5; see there). */
 int ps_featuriser_plan_f32(int B, int N, int A, int float_misalign, int mask_misalign,
                            int exact_sqrt, int exact_angles, int cu_count, ps_k3_plan* plan);
+
+/*
+ * Backward pass of ps_inter_residue_geometry_f32 (ABI 9; no reference counterpart: the reference's dihedral goes
+ * through numpy and is not differentiable).  A vector-Jacobian product in one launch:
+ *   grad_xyz[b][r][s][:] = sum over the six float planes and over (i, j) of g_plane[b][i][j] * d plane[b][i][j] / d xyz[b][r][s][:]
+ * g_d_ca .. g_phi are the (B,N,N) fp32 upstream gradients of the planes of the same name; any of them may be NULL, which
+ * means zero (its arithmetic is skipped).  grad_xyz is (B,N,A,3) fp32 and EVERY element of it is written: slots other
+ * than N (0), CA (1), O (3) and CB (4) receive exact zeros, so the buffer need not be initialised.
+ * Active entries.  Entry (b, i, j) of a plane contributes only when (1) every atom it reads is present in atom_mask
+ * (NULL = all present) -- d_ca: CA_i, CA_j; d_cb: CB_i, CB_j; d_no: N_i, O_j; omega: CA_i, CB_i, CA_j, CB_j; theta: N_i,
+ * CA_i, CB_i, CB_j; phi: CA_i, CB_i, CB_j -- and (2) i != j, for every plane but d_no (sqrt(0), atan2(0, 0) and 0 / 0 have
+ * no derivative; the diagonal of d_no is an ordinary N_i - O_i distance).  Every other entry contributes exactly zero, by
+ * selection and not by multiplication: NaN coordinates of absent atoms and NaN upstream values at inactive entries never
+ * reach the result.  The derivative is that of the mathematical functions the forward evaluates (omega is
+ * dihedral(CA_i,CB_i,CA_j,CB_j) as coded; sign of geometry.dihedral).  There is one arithmetic: exact_sqrt / exact_angles
+ * of the forward select no backward variant.  Deterministic: no atomics, a fixed order of summation, so two launches on
+ * the same inputs agree bit for bit.  Needs A >= 5 and N <= 2048 (a structure's four used slots are staged in LDS, 52 bytes
+ * per residue); a longer chain is refused with hipErrorInvalidValue.  One kernel, one dispatch arm.
+ */
+int ps_inter_residue_geometry_backward_f32(const float* xyz, const uint8_t* atom_mask,
+                                           const float* g_d_ca, const float* g_d_cb, const float* g_d_no,
+                                           const float* g_omega, const float* g_theta, const float* g_phi,
+                                           float* grad_xyz, int B, int N, int A, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

@@ -13,6 +13,7 @@
 // 7: ps_backbone_distmat_init_f32 (K8), ps_floyd_warshall_f32 / ps_floyd_warshall_workspace_bytes (K9),
 //    ps_backbone_distmat_finish_f32.
 // 8: ps_smacof_f32 / ps_smacof_workspace_bytes (K10), ps_mds_backbone_finish_f32 (K11).
+// 9: ps_inter_residue_geometry_backward_f32 (the featuriser's vector-Jacobian product).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

@@ -5,6 +5,8 @@ functions the batch kernels use (csrc/ps_common.hpp) through a point-wise
 launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
 ``reconstruct_backbone_distmat_from_interresidue_geometry`` runs the distance-matrix kernels (csrc/distmat.hip);
 ``initialize_backbone_with_mds`` and ``fix_chirality`` the SMACOF and finishing kernels (csrc/mds.hip).
+``inter_residue_geometry`` is the fused featuriser as a differentiable function of the coordinates (its backward pass is
+one HIP kernel, ``ops.inter_residue_geometry_backward``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -134,6 +136,44 @@ def kabsch(a, b):
     mask = torch.ones(1, a.shape[0], dtype=torch.bool, device=a.device)
     R, t = ops.kabsch(a.reshape(1, -1, 1, 3).contiguous(), b.reshape(1, -1, 1, 3).contiguous(), mask)
     return _finish(R[0], ft), _finish(t[0], ft)
+
+
+_IRG_MASK_KEYS = ("d_ca_mask", "d_cb_mask", "d_no_mask")
+
+
+class _InterResidueGeometry(torch.autograd.Function):
+    """ops.inter_residue_geometry with ops.inter_residue_geometry_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, xyz, atom_mask):
+        g = ops.inter_residue_geometry(xyz, atom_mask)
+        masks = tuple(g[k] for k in _IRG_MASK_KEYS)
+        ctx.mark_non_differentiable(*masks)
+        # a plane the loss does not use arrives in backward() as None, not as a (B,N,N) tensor of zeros autograd would
+        # otherwise allocate and fill: the kernel skips the arithmetic of an absent plane
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xyz, atom_mask)   # saved tensors: an in-place change before backward() is an error, not a wrong gradient
+        return tuple(g[k] for k in ops.IRG_GRAD_KEYS) + masks
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grad_outputs):
+        xyz, atom_mask = ctx.saved_tensors
+        grads = {k: g for k, g in zip(ops.IRG_GRAD_KEYS, grad_outputs) if g is not None}
+        grad_xyz = ops.inter_residue_geometry_backward(xyz, grads, atom_mask)
+        return grad_xyz.to(xyz.dtype), None
+
+
+def inter_residue_geometry(xyz, atom_mask=None):
+    """The fused featuriser, differentiable with respect to ``xyz`` (B,N,A,3): the dict of ``ops.inter_residue_geometry``,
+    in its key order -- d_ca, d_cb, d_no, omega, theta, phi (B,N,N) fp32, then the three bool mask planes; every value
+    bit for bit what that call returns -- with the six float planes attached to the autograd graph.  Their backward pass
+    is one launch of the HIP kernel behind ``ops.inter_residue_geometry_backward``, which receives only the planes the
+    loss used (the others are absent, and their arithmetic is skipped): entries that read an atom absent from
+    ``atom_mask`` and the diagonals of every plane but d_no pass no gradient (NaN coordinates of missing atoms never
+    reach ``xyz.grad``).  The mask planes are not differentiable and ``atom_mask`` gets no gradient; no double backward."""
+    out = _InterResidueGeometry.apply(xyz, atom_mask)
+    return dict(zip(ops.IRG_GRAD_KEYS + _IRG_MASK_KEYS, out))   # the order ops.inter_residue_geometry builds its dict in
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

@@ -485,6 +485,66 @@ def inter_residue_geometry(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor] 
     return out
 
 
+IRG_GRAD_KEYS = ("d_ca", "d_cb", "d_no", "omega", "theta", "phi")   # the differentiable planes, in the C ABI's order
+IRG_BACKWARD_MAX_N = 2048   # the backward kernel stages a structure's used slots in LDS (include/protstruc_hip.h)
+
+
+def check_inter_residue_geometry_backward_shapes(xyz, grads, atom_mask=None, out=None) -> None:
+    """Shape rules of ``inter_residue_geometry_backward``, on shapes and dtypes only (no device, no launch): KeyError for
+    a key of ``grads`` that is no float plane, ValueError for a wrong rank or shape, IndexError for fewer than five atom
+    slots (as the forward raises)."""
+    for key in grads:
+        if key not in IRG_GRAD_KEYS:
+            raise KeyError(f"{key!r} is not a differentiable plane of inter_residue_geometry (known: {', '.join(IRG_GRAD_KEYS)})")
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    if not xyz.dtype.is_floating_point:
+        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
+    B, N, A = shape[:3]
+    if A < 5:
+        raise IndexError("inter_residue_geometry needs the N, CA, C, O, CB atom slots")
+    if N > IRG_BACKWARD_MAX_N:
+        raise ValueError(f"inter_residue_geometry_backward takes at most {IRG_BACKWARD_MAX_N} residues, got {N}")
+    if atom_mask is not None and tuple(atom_mask.shape) != (B, N, A):
+        raise ValueError(f"atom_mask must have shape {(B, N, A)} to match xyz {shape}, got {tuple(atom_mask.shape)}")
+    for key, g in grads.items():
+        if g is None:
+            continue
+        if tuple(g.shape) != (B, N, N):
+            raise ValueError(f"grads[{key!r}] must have shape {(B, N, N)} to match xyz {shape}, got {tuple(g.shape)}")
+        if not g.dtype.is_floating_point:
+            raise ValueError(f"grads[{key!r}] must be a floating-point tensor, got {g.dtype}")
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+
+
+def inter_residue_geometry_backward(xyz: torch.Tensor, grads, atom_mask: Optional[torch.Tensor] = None, *,
+                                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Vector-Jacobian product of the fused featuriser in one launch: ``grad_xyz`` (B,N,A,3) fp32 with
+    ``grad_xyz[b, r, s] = sum over planes and (i, j) of grads[plane][b, i, j] * d plane[b, i, j] / d xyz[b, r, s]``.
+    ``grads`` maps any subset of d_ca / d_cb / d_no / omega / theta / phi to (B,N,N) upstream gradients (a missing key or
+    a None value means zero; anything not contiguous fp32 is made so).  Entries that read an atom absent from
+    ``atom_mask``, and the diagonal of every plane but d_no, contribute exactly zero -- NaN coordinates and NaN upstream
+    values there never reach the result (include/protstruc_hip.h).  Every element of ``out`` is written (exact zeros in
+    the slots the featuriser does not read); deterministic; independent of ``set_exact_sqrt`` / ``set_exact_angles``."""
+    check_inter_residue_geometry_backward_shapes(xyz, grads, atom_mask, out)
+    xyz = _f32c(xyz, "xyz")
+    _same_device(xyz, atom_mask=atom_mask, out=out, **{f"grads[{k!r}]": g for k, g in grads.items()})
+    m = _u8c(atom_mask, "atom_mask")
+    gs = [None if grads.get(key) is None else _f32c(grads[key], f"grads[{key!r}]") for key in IRG_GRAD_KEYS]
+    B, N, A = xyz.shape[:3]
+    with _on(xyz.device):
+        if out is None:
+            out = torch.empty(B, N, A, 3, dtype=torch.float32, device=xyz.device)
+        rc = 0
+        if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            rc = _lib.load().ps_inter_residue_geometry_backward_f32(_ptr(xyz), _ptr(m), *[_ptr(g) for g in gs], _ptr(out),
+                                                                    B, N, A, _stream(xyz))
+    _lib.check(rc, "ps_inter_residue_geometry_backward_f32")
+    return out
+
+
 def pointwise(mode: int, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, d: Optional[torch.Tensor] = None):
     """angle (mode 0) / dihedral (1) / gram_schmidt (2) / place_fourth_atom (3, ``d`` packed [length, planar, dihedral])
     over broadcast (*,3) tensors."""

@@ -352,8 +352,13 @@ class StructureBatch:
         return distributed.pairwise_angles_sharded(self.xyz, si, sj, 3, group=group, gather=gather, impl=impl)
 
     def inter_residue_geometry(self) -> Dict[str, torch.Tensor]:
-        """trRosetta-style inter-residue features (protstruc.py:790-817)."""
-        g = ops.inter_residue_geometry(self.xyz, self.atom_mask)  # one fused launch, no (B,N,N,A,A) tensor
+        """trRosetta-style inter-residue features (protstruc.py:790-817).  Differentiable with respect to coordinates that
+        require grad (``geometry.inter_residue_geometry``); the values are the same either way."""
+        if torch.is_grad_enabled() and self.xyz.requires_grad:
+            from . import geometry
+            g = geometry.inter_residue_geometry(self.xyz, self.atom_mask)  # the same launch, with the HIP backward kernel attached
+        else:
+            g = ops.inter_residue_geometry(self.xyz, self.atom_mask)  # one fused launch, no (B,N,N,A,A) tensor
         if self.atom_mask is not None and self.atom_mask.dtype != torch.bool:
             for k in ("d_ca_mask", "d_cb_mask", "d_no_mask"):
                 g[k] = g[k].to(self.atom_mask.dtype)

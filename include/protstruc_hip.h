@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 9
+#define PS_ABI_VERSION 10
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -433,6 +433,38 @@ int ps_frames_to_backbone_f32(const float* rot, const float* trans, const float*
 int ps_backbone_from_dihedrals_f32(const float* dihedrals, const float* bond_angles, const float* bond_lengths,
                                    const float* chain_idx, const uint8_t* residue_mask, float* xyz, float* atom_mask,
                                    int include_cb, int B, int N, int A, void* stream);
+
+/*
+ * K12 (ABI 10) -- backward pass of ps_backbone_from_dihedrals_f32: the vector-Jacobian product of the coordinates with
+ * respect to the dihedrals, bond angles and bond lengths, in one launch and from the coordinates alone.
+ *   xyz (B,N,A,3)       what the forward wrote (the same chain_idx, residue_mask, include_cb and A);
+ *   grad_xyz (B,N,A,3)  the upstream gradient;
+ *   grad_dihedrals, grad_bond_angles, grad_bond_lengths (B,N,3) fp32, in the forward's layouts; the last two may be NULL
+ *   (not wanted: their arithmetic is skipped).  chain_idx and residue_mask may be NULL as in the forward.
+ * An internal coordinate moves everything after it in its segment as a rigid body, so with the effective atom gradients
+ * g (the CB gradient pushed back first: with bb = CA - N, cc = C - CA and CB = k0 (bb x cc) + k1 bb + k2 cc + CA,
+ * g_bb = k0 (cc x g_CB) + k1 g_CB, g_cc = k0 (g_CB x bb) + k2 g_CB, g_N -= g_bb, g_CA += g_bb - g_cc + g_CB, g_C += g_cc)
+ * and the segmented inclusive suffix sums over the backbone atoms in chain order, G[k] = sum g_a and T[k] = sum x_a x g_a
+ * over the atoms a >= k of k's segment, a rotation about the unit axis u through p that moves the atoms k.. has the
+ * gradient u . (T[k] - p x G[k]) and a bond length along u has u . G[k].  For residue i continuing a segment (j = i - 1):
+ *   psi_j    atoms N_i..,  u = unit(C_j - CA_j), p = C_j      angle CA_j-C_j-N_i   atoms N_i..,  u = unit((CA_j - C_j) x (N_i - C_j)), p = C_j
+ *   omega_j  atoms CA_i.., u = unit(N_i - C_j),  p = N_i      angle C_j-N_i-CA_i   atoms CA_i.., u = unit((C_j - N_i) x (CA_i - N_i)), p = N_i
+ *   phi_i    atoms C_i..,  u = unit(CA_i - N_i), p = CA_i     angle N_i-CA_i-C_i   atoms C_i..,  u = unit((N_i - CA_i) x (C_i - CA_i)), p = CA_i
+ *   |C_j-N_i|, |N_i-CA_i|, |CA_i-C_i|  atoms N_i.., CA_i.., C_i..  along unit(N_i - C_j), unit(CA_i - N_i), unit(C_i - CA_i).
+ * A segment's first residue sits in the fixed frame: |N_i-CA_i| and the angle N_i-CA_i-C_i move N_i alone
+ * (unit(N_i - CA_i) . g_N and unit((C_i - CA_i) x (N_i - CA_i)) . ((N_i - CA_i) x g_N)), |CA_i-C_i| moves C_i and
+ * everything after it, phi_i nothing.
+ * Contract.  Every element of every non-NULL output is written; entries the forward never reads (phi at a segment's
+ * first residue, psi / omega / the two peptide angles / |C-N| at its last, every parameter that only moves masked
+ * residues) are exact zeros.  Only slots 0, 1, 2 (and 4 with include_cb) of xyz and grad_xyz are read; rows of masked
+ * residues and all other slots are excluded by selection, so NaN there never reaches the result.  No atomics and a
+ * fixed order of every sum: two launches agree bit for bit.  Any N (tiles of 512 residues walked from the chain's end
+ * with the running G, T carried); nothing is allocated, synchronised or read back, so the launch can be captured in a
+ * graph.  B == 0 or N == 0 returns 0 without a launch.  No second derivatives.
+ */
+int ps_backbone_from_dihedrals_backward_f32(const float* xyz, const float* grad_xyz, const float* chain_idx,
+                                            const uint8_t* residue_mask, float* grad_dihedrals, float* grad_bond_angles,
+                                            float* grad_bond_lengths, int include_cb, int B, int N, int A, void* stream);
 
 /*
  * K8 / K9 (ABI 7) -- backbone N / CA / C distance matrices from inter-residue geometry (trRosetta), behind

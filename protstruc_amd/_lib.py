@@ -10,7 +10,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROTSTRUC_AMD_LIB selects another build of the library: the same-process A/B of two builds (tools/k1_ab_libs.py)
 LIB_PATH = os.environ.get("PROTSTRUC_AMD_LIB") or os.path.join(_HERE, "lib", "libprotstruc_hip.so")
-EXPECTED_ABI = 9  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
+EXPECTED_ABI = 10  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
 
 
 class K1Config(ctypes.Structure):
@@ -78,6 +78,8 @@ SIGNATURES = {
     "ps_frames_to_backbone_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
     "ps_backbone_from_dihedrals_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int,
                                                 _c_int, _c_int, _c_stream]),
+    "ps_backbone_from_dihedrals_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_f32p, _c_int,
+                                                         _c_int, _c_int, _c_int, _c_stream]),
     "ps_backbone_distmat_init_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_u8p, ctypes.c_void_p, _c_f32p,
                                               _c_int, _c_int, _c_stream]),
     "ps_floyd_warshall_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),

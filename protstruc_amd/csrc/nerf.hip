@@ -237,7 +237,222 @@ __global__ __launch_bounds__(NERF_THREADS) void k7_backbone_from_dihedrals(
     }
 }
 
+// ---- K12: the backward pass of K7 -- gradients with respect to the dihedrals, bond angles and bond lengths ----
+// An internal coordinate of a chain moves everything downstream of it as a rigid body, so its gradient is a projection
+// of the downstream force G = sum g_a and torque T = sum x_a x g_a (about the origin, where K7 puts every segment's
+// first CA): a rotation about the unit axis u through p gives u . (T - p x G), a bond length along u gives u . G.  No
+// scan of transforms is needed backwards: G and T are segmented inclusive SUFFIX sums over the 3 N backbone atoms, six
+// floats and a flag per element.  Everything is read off the forward's coordinates; the angles are not needed.
+// One workgroup per structure, tiles of 512 residues walked from the chain's END with the running (G, T) carried from
+// tile to tile (as K7 carries its transform forwards), two residues per lane in descending order:
+//   1. the tile's N / CA / C / CB coordinates (with residue t0 - 1 as a halo) and upstream gradients staged in LDS by
+//      the whole workgroup -- only slots 0, 1, 2 (and 4 with include_cb) are ever addressed;
+//   2. per residue: the CB gradient pushed back onto N, CA, C, then the residue's (sum g, sum x x g).  A masked residue
+//      contributes zeros BY SELECTION (its row of grad_xyz may hold NaN);
+//   3. segmented scan over descending residues (lane pair, __shfl_up over the wave, the four wave totals through LDS);
+//      a residue that is the last of its segment carries the reset flag, which discards everything after it by selection;
+//   4. per residue i: G, T at C_i, CA_i, N_i from the exclusive prefix, then residue i's own parameters (phi_i, angle
+//      N-CA-C, |N-CA|, |CA-C|) and those of the junction to i - 1 (psi, omega, the two peptide angles, |C-N|), each
+//      stored by exactly one lane; parameters that move no visible atom are stored as exact zeros.
+// No atomics and a fixed order of every sum: the same bits on every run.
+constexpr int NB_THREADS = 256;
+constexpr int NB_PER_LANE = 2;
+constexpr int NB_TILE = NB_THREADS * NB_PER_LANE;
+constexpr int NB_WAVES = NB_THREADS / PS_WAVE;
+constexpr float kCB0 = -0.58273431f, kCB1 = 0.56802827f, kCB2 = -0.54067466f;   // K7's CB placement
+
+struct SegGT {
+    f3 g, t;
+    int reset;
+};
+
+__device__ __forceinline__ f3 add3(f3 a, f3 b) { return f3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ f3 sel3(bool c, f3 a, f3 b) { return f3{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z}; }
+__device__ __forceinline__ f3 unit3(f3 a) { return div3(a, norm3(a)); }
+
+__device__ __forceinline__ SegGT gt_identity() { return SegGT{mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 0.f), 0}; }
+
+// a is the earlier element of the scan (the residues AFTER b's in the chain); a reset on b discards it by selection
+__device__ __forceinline__ SegGT gt_combine(const SegGT& a, const SegGT& b) {
+    SegGT o;
+    o.g = sel3(b.reset != 0, b.g, add3(a.g, b.g));
+    o.t = sel3(b.reset != 0, b.t, add3(a.t, b.t));
+    o.reset = a.reset | b.reset;
+    return o;
+}
+
+__device__ __forceinline__ SegGT gt_shfl_up(const SegGT& x, int delta) {
+    SegGT o;
+    o.g = mk3(__shfl_up(x.g.x, delta), __shfl_up(x.g.y, delta), __shfl_up(x.g.z, delta));
+    o.t = mk3(__shfl_up(x.t.x, delta), __shfl_up(x.t.y, delta), __shfl_up(x.t.z, delta));
+    o.reset = __shfl_up(x.reset, delta);
+    return o;
+}
+
+// u . (T - p x G): the gradient of a rotation about the unit axis u through p that moves the atoms summed in (G, T)
+__device__ __forceinline__ float turn3(f3 u, f3 p, f3 G, f3 T) { return dot3(u, sub3(T, cross3(p, G))); }
+
+__global__ __launch_bounds__(NB_THREADS) void k12_backbone_from_dihedrals_backward(
+    const float* __restrict__ xyz, const float* __restrict__ grad_xyz, const float* __restrict__ chain_idx,
+    const uint8_t* __restrict__ residue_mask, float* __restrict__ grad_dihedrals, float* __restrict__ grad_bond_angles,
+    float* __restrict__ grad_bond_lengths, int include_cb, int N, int A) {
+    const size_t row = 3 * (size_t)A;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & (PS_WAVE - 1), wave = threadIdx.x / PS_WAVE;
+    const size_t base = (size_t)b * N;
+    const bool cb = include_cb != 0;
+
+    __shared__ float sx[(NB_TILE + 1) * 12];   // N, CA, C, CB of residues t0 - 1 (the halo) .. t0 + nt - 1
+    __shared__ float sg[NB_TILE * 12];         // their upstream gradients, residues t0 .. t0 + nt - 1
+    __shared__ SegGT wtot[NB_WAVES];
+
+    SegGT carry = gt_identity();   // the suffix sums at the lowest residue of the tile above
+    for (int t0 = ((N - 1) / NB_TILE) * NB_TILE; t0 >= 0; t0 -= NB_TILE) {
+        const int nt = min(NB_TILE, N - t0);
+
+        // ---- stage 1: the used slots of the tile into LDS ----
+        for (int e = threadIdx.x; e < (nt + 1) * 12; e += NB_THREADS) {
+            const int r = e / 12, o = e - r * 12;
+            const int i = t0 + r - 1;
+            float v = 0.f;
+            if (i >= 0 && (o < 9 || cb)) v = xyz[(base + i) * row + (o < 9 ? o : o + 3)];
+            sx[e] = v;
+        }
+        for (int e = threadIdx.x; e < nt * 12; e += NB_THREADS) {
+            const int r = e / 12, o = e - r * 12;
+            float v = 0.f;
+            if (o < 9 || cb) v = grad_xyz[(base + t0 + r) * row + (o < 9 ? o : o + 3)];
+            sg[e] = v;
+        }
+        __syncthreads();
+
+        // ---- stage 2: per residue, descending: lane l holds residues t0 + nt - 1 - 2 l and the one below ----
+        f3 xn[NB_PER_LANE], xa[NB_PER_LANE], xc[NB_PER_LANE], gn[NB_PER_LANE], ga[NB_PER_LANE], gc[NB_PER_LANE];
+        bool live[NB_PER_LANE], start[NB_PER_LANE];
+        SegGT el[NB_PER_LANE];
+#pragma unroll
+        for (int j = 0; j < NB_PER_LANE; ++j) {
+            const int k = nt - 1 - ((int)threadIdx.x * NB_PER_LANE + j);
+            el[j] = gt_identity();
+            live[j] = start[j] = false;
+            xn[j] = xa[j] = xc[j] = gn[j] = ga[j] = gc[j] = mk3(0.f, 0.f, 0.f);
+            if (k < 0) continue;
+            const int i = t0 + k;
+            const size_t res = base + i;
+            const bool lv = !residue_mask || residue_mask[res] != 0;
+            bool st = (i == 0);
+            if (!st && chain_idx) st = chain_idx[res] != chain_idx[res - 1];   // NaN != NaN: a new segment
+            if (!st && residue_mask) st = residue_mask[res - 1] == 0;
+            bool last = (i == N - 1) || !lv;                                    // the residue after a masked one starts a segment
+            if (!last && chain_idx) last = chain_idx[res + 1] != chain_idx[res];
+            const float* x = sx + (k + 1) * 12;
+            const float* g = sg + k * 12;
+            const f3 z = mk3(0.f, 0.f, 0.f);
+            xn[j] = sel3(lv, load3(x), z);
+            xa[j] = sel3(lv, load3(x + 3), z);
+            xc[j] = sel3(lv, load3(x + 6), z);
+            f3 n = sel3(lv, load3(g), z), a = sel3(lv, load3(g + 3), z), c = sel3(lv, load3(g + 6), z);
+            if (cb) {   // CB = k0 (bb x cc) + k1 bb + k2 cc + CA with bb = CA - N, cc = C - CA
+                const f3 gb = sel3(lv, load3(g + 9), z);
+                const f3 bb = sub3(xa[j], xn[j]), cc = sub3(xc[j], xa[j]);
+                const f3 g_bb = add3(scale3(cross3(cc, gb), kCB0), scale3(gb, kCB1));
+                const f3 g_cc = add3(scale3(cross3(gb, bb), kCB0), scale3(gb, kCB2));
+                n = sub3(n, g_bb);
+                a = add3(sub3(add3(a, g_bb), g_cc), gb);
+                c = add3(c, g_cc);
+            }
+            gn[j] = n; ga[j] = a; gc[j] = c;
+            live[j] = lv; start[j] = st;
+            el[j].g = add3(add3(c, a), n);
+            el[j].t = add3(add3(cross3(xc[j], c), cross3(xa[j], a)), cross3(xn[j], n));
+            el[j].reset = last ? 1 : 0;
+        }
+
+        // ---- stage 3: the segmented scan over descending residues ----
+        SegGT inc = gt_combine(el[0], el[1]);
+#pragma unroll
+        for (int off = 1; off < PS_WAVE; off <<= 1) {
+            const SegGT o = gt_shfl_up(inc, off);
+            if (lane >= off) inc = gt_combine(o, inc);
+        }
+        SegGT excl = gt_shfl_up(inc, 1);
+        if (lane == 0) excl = gt_identity();
+        if (lane == PS_WAVE - 1) wtot[wave] = inc;
+        __syncthreads();
+        SegGT pre = carry;
+        for (int w = 0; w < wave; ++w) pre = gt_combine(pre, wtot[w]);
+        for (int w = 0; w < NB_WAVES; ++w) carry = gt_combine(carry, wtot[w]);
+        pre = gt_combine(pre, excl);
+
+        // ---- stage 4: the parameters of residue i and of its junction to i - 1 ----
+#pragma unroll
+        for (int j = 0; j < NB_PER_LANE; ++j) {
+            const int k = nt - 1 - ((int)threadIdx.x * NB_PER_LANE + j);
+            if (k < 0) break;
+            const int i = t0 + k;
+            const size_t res = base + i;
+            const SegGT after = (j == 0) ? pre : gt_combine(pre, el[0]);   // the residues after i
+            const bool last = el[j].reset != 0;
+            const f3 z = mk3(0.f, 0.f, 0.f);
+            const f3 Gc = add3(gc[j], sel3(last, z, after.g)), Tc = add3(cross3(xc[j], gc[j]), sel3(last, z, after.t));
+            const f3 Ga = add3(ga[j], Gc), Ta = add3(cross3(xa[j], ga[j]), Tc);
+            const f3 Gn = add3(gn[j], Ga), Tn = add3(cross3(xn[j], gn[j]), Ta);
+            const bool cont = !start[j] && live[j], head = start[j] && live[j];
+            const f3 an = sub3(xn[j], xa[j]), ac = sub3(xc[j], xa[j]);   // CA -> N, CA -> C
+            const f3 u_ac = unit3(ac);
+            // phi_i turns C_i.. about N_i -> CA_i; the angle N-CA-C turns them about (N - CA) x (C - CA) through CA_i
+            const float d_phi = turn3(unit3(sub3(xa[j], xn[j])), xa[j], Gc, Tc);
+            const float d_nac = turn3(unit3(cross3(an, ac)), xa[j], Gc, Tc);
+            const float d_na = dot3(unit3(sub3(xa[j], xn[j])), Ga);
+            // a segment's first residue sits in the fixed frame: |N-CA| and the angle move N_i alone
+            const float h_nac = dot3(unit3(cross3(ac, an)), cross3(an, gn[j]));
+            const float h_na = dot3(unit3(an), gn[j]);
+            grad_dihedrals[res * 3] = cont ? d_phi : 0.f;
+            if (grad_bond_angles) grad_bond_angles[res * 3] = cont ? d_nac : (head ? h_nac : 0.f);
+            if (grad_bond_lengths) {
+                grad_bond_lengths[res * 3] = cont ? d_na : (head ? h_na : 0.f);
+                grad_bond_lengths[res * 3 + 1] = live[j] ? dot3(u_ac, Gc) : 0.f;
+            }
+            if (i > 0) {
+                const f3 aj = load3(sx + k * 12 + 3), cj = load3(sx + k * 12 + 6);   // CA and C of residue i - 1
+                const f3 cn = sub3(xn[j], cj);
+                const f3 u_cn = unit3(cn);
+                // psi_j turns N_i.. about CA_j -> C_j, omega_j turns CA_i.. about C_j -> N_i
+                const float d_psi = turn3(unit3(sub3(cj, aj)), cj, Gn, Tn);
+                const float d_omega = turn3(u_cn, xn[j], Ga, Ta);
+                grad_dihedrals[(res - 1) * 3 + 1] = cont ? d_psi : 0.f;
+                grad_dihedrals[(res - 1) * 3 + 2] = cont ? d_omega : 0.f;
+                if (grad_bond_angles) {
+                    const float d_cacn = turn3(unit3(cross3(sub3(aj, cj), cn)), cj, Gn, Tn);
+                    const float d_cnca = turn3(unit3(cross3(sub3(cj, xn[j]), sub3(xa[j], xn[j]))), xn[j], Ga, Ta);
+                    grad_bond_angles[(res - 1) * 3 + 1] = cont ? d_cacn : 0.f;
+                    grad_bond_angles[(res - 1) * 3 + 2] = cont ? d_cnca : 0.f;
+                }
+                if (grad_bond_lengths) grad_bond_lengths[(res - 1) * 3 + 2] = cont ? dot3(u_cn, Gn) : 0.f;
+            }
+            if (i == N - 1) {   // nothing follows the last residue
+                grad_dihedrals[res * 3 + 1] = 0.f;
+                grad_dihedrals[res * 3 + 2] = 0.f;
+                if (grad_bond_angles) grad_bond_angles[res * 3 + 1] = grad_bond_angles[res * 3 + 2] = 0.f;
+                if (grad_bond_lengths) grad_bond_lengths[res * 3 + 2] = 0.f;
+            }
+        }
+        __syncthreads();   // the next tile overwrites sx / sg / wtot
+    }
+}
+
 }  // namespace
+
+extern "C" int ps_backbone_from_dihedrals_backward_f32(const float* xyz, const float* grad_xyz, const float* chain_idx,
+                                                       const uint8_t* residue_mask, float* grad_dihedrals,
+                                                       float* grad_bond_angles, float* grad_bond_lengths, int include_cb,
+                                                       int B, int N, int A, void* stream) {
+    if (!xyz || !grad_xyz || !grad_dihedrals || B < 0 || N < 0 || A < 3 || (include_cb && A < 5)) return (int)hipErrorInvalidValue;
+    if (B == 0 || N == 0) return 0;
+    return ps_launch(k12_backbone_from_dihedrals_backward, dim3((unsigned)B), dim3(NB_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), xyz, grad_xyz, chain_idx, residue_mask, grad_dihedrals,
+                     grad_bond_angles, grad_bond_lengths, include_cb, N, A);
+}
 
 extern "C" int ps_backbone_from_dihedrals_f32(const float* dihedrals, const float* bond_angles, const float* bond_lengths,
                                               const float* chain_idx, const uint8_t* residue_mask, float* xyz,

@@ -6,7 +6,8 @@ launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
 ``reconstruct_backbone_distmat_from_interresidue_geometry`` runs the distance-matrix kernels (csrc/distmat.hip);
 ``initialize_backbone_with_mds`` and ``fix_chirality`` the SMACOF and finishing kernels (csrc/mds.hip).
 ``inter_residue_geometry`` is the fused featuriser as a differentiable function of the coordinates (its backward pass is
-one HIP kernel, ``ops.inter_residue_geometry_backward``).
+one HIP kernel, ``ops.inter_residue_geometry_backward``); ``backbone_from_dihedrals`` is the backbone builder as a
+differentiable function of the dihedrals, bond angles and bond lengths (``ops.backbone_from_dihedrals_backward``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -174,6 +175,44 @@ def inter_residue_geometry(xyz, atom_mask=None):
     reach ``xyz.grad``).  The mask planes are not differentiable and ``atom_mask`` gets no gradient; no double backward."""
     out = _InterResidueGeometry.apply(xyz, atom_mask)
     return dict(zip(ops.IRG_GRAD_KEYS + _IRG_MASK_KEYS, out))   # the order ops.inter_residue_geometry builds its dict in
+
+
+class _BackboneFromDihedrals(torch.autograd.Function):
+    """ops.backbone_from_dihedrals with ops.backbone_from_dihedrals_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, dihedrals, chain_idx, residue_mask, bond_angles, bond_lengths, include_cb, n_slots):
+        xyz, atom_mask = ops.backbone_from_dihedrals(dihedrals, chain_idx, residue_mask, bond_angles, bond_lengths,
+                                                     include_cb=include_cb, n_slots=n_slots)
+        ctx.mark_non_differentiable(atom_mask)
+        ctx.include_cb = bool(include_cb)
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (dihedrals, bond_angles, bond_lengths))
+        # the backward pass reads the coordinates and the segment rules, not the angles; saved tensors: an in-place change
+        # of chain_idx / residue_mask before backward() is an error, not a wrong gradient
+        ctx.save_for_backward(xyz, chain_idx, residue_mask)
+        return xyz, atom_mask
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_xyz, _grad_atom_mask):
+        xyz, chain_idx, residue_mask = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4])
+        grads = ops.backbone_from_dihedrals_backward(xyz, grad_xyz, chain_idx, residue_mask, include_cb=ctx.include_cb,
+                                                     want_bond_angles=need[1], want_bond_lengths=need[2])
+        g_dih, g_ang, g_len = (g.to(dt) if wanted else None for g, dt, wanted in zip(grads, ctx.dtypes, need))
+        return g_dih, None, None, g_ang, g_len, None, None
+
+
+def backbone_from_dihedrals(dihedrals, chain_idx=None, residue_mask=None, bond_angles=None, bond_lengths=None,
+                            include_cb=False, n_slots=15):
+    """The backbone builder as a differentiable function: ``(xyz (B,N,n_slots,3), atom_mask (B,N,n_slots))``, bit for
+    bit what ``ops.backbone_from_dihedrals`` returns, with ``xyz`` attached to the autograd graph.  Gradients flow to
+    ``dihedrals`` (B,N,3) and to ``bond_angles`` / ``bond_lengths`` (B,N,3) where given, each only if it requires grad;
+    the backward pass is one launch of the HIP kernel behind ``ops.backbone_from_dihedrals_backward`` (the bond gradients
+    that nobody needs reach it as absent and are not computed).  Angles the builder never reads (phi at a segment's
+    first residue, psi / omega at its last, everything that only moves masked residues) get exact zeros.  ``atom_mask``
+    is not differentiable; ``chain_idx`` / ``residue_mask`` get no gradient; no double backward."""
+    return _BackboneFromDihedrals.apply(dihedrals, chain_idx, residue_mask, bond_angles, bond_lengths, include_cb, n_slots)
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

@@ -610,6 +610,69 @@ def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.T
     return xyz, atom_mask
 
 
+def check_backbone_from_dihedrals_backward_shapes(xyz, grad_xyz, chain_idx=None, residue_mask=None, include_cb=False,
+                                                  want_bond_angles=False, want_bond_lengths=False, out=None) -> None:
+    """Shape rules of ``backbone_from_dihedrals_backward``, on shapes and dtypes only (no device, no launch): ValueError."""
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    if tuple(grad_xyz.shape) != shape:
+        raise ValueError(f"grad_xyz must have shape {shape} to match xyz, got {tuple(grad_xyz.shape)}")
+    for name, t in (("xyz", xyz), ("grad_xyz", grad_xyz)):
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    B, N, A = shape[:3]
+    if A < (5 if include_cb else 3):
+        raise ValueError(f"{A} atom slots leave no room for {'N, CA, C and CB' if include_cb else 'N, CA, C'}")
+    for name, t in (("chain_idx", chain_idx), ("residue_mask", residue_mask)):
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{name} must have shape {(B, N)} to match xyz {shape}, got {tuple(t.shape)}")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise ValueError("out must be a (grad_dihedrals, grad_bond_angles, grad_bond_lengths) triple (None where not wanted)")
+        for name, t, wanted in (("out[0]", out[0], True), ("out[1]", out[1], want_bond_angles), ("out[2]", out[2], want_bond_lengths)):
+            if t is None:
+                continue
+            if not wanted:
+                raise ValueError(f"{name} is given but that gradient is not wanted")
+            if tuple(t.shape) != (B, N, 3) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {(B, N, 3)}")
+
+
+def backbone_from_dihedrals_backward(xyz: torch.Tensor, grad_xyz: torch.Tensor, chain_idx: Optional[torch.Tensor] = None,
+                                     residue_mask: Optional[torch.Tensor] = None, *, include_cb: bool = False,
+                                     want_bond_angles: bool = False, want_bond_lengths: bool = False, out=None):
+    """K12.  Vector-Jacobian product of ``backbone_from_dihedrals`` in one launch: from the coordinates ``xyz`` (B,N,A,3)
+    that call returned (with the same ``chain_idx``, ``residue_mask``, ``include_cb``) and the upstream ``grad_xyz`` of
+    the same shape, returns ``(grad_dihedrals, grad_bond_angles, grad_bond_lengths)``, each (B,N,3) fp32 in the
+    forward's layout; the last two are None unless wanted (their arithmetic is skipped).  Entries the forward never
+    reads are exact zeros; only slots 0, 1, 2 (and 4 with ``include_cb``) of unmasked rows are read, so NaN anywhere
+    else never reaches the result; deterministic (include/protstruc_hip.h).  ``out``: a triple of contiguous fp32
+    (B,N,3) tensors to write into (None where not wanted or to allocate); every element of them is written."""
+    check_backbone_from_dihedrals_backward_shapes(xyz, grad_xyz, chain_idx, residue_mask, include_cb, want_bond_angles,
+                                                  want_bond_lengths, out)
+    xyz = _f32c(xyz, "xyz")
+    outs = list(out) if out is not None else [None, None, None]
+    _same_device(xyz, grad_xyz=grad_xyz, chain_idx=chain_idx, residue_mask=residue_mask,
+                 **{f"out[{k}]": t for k, t in enumerate(outs)})
+    gx = _f32c(grad_xyz, "grad_xyz")
+    chain = None if chain_idx is None else _f32c(chain_idx, "chain_idx")
+    rmask = _u8c(residue_mask, "residue_mask")
+    B, N, A = xyz.shape[:3]
+    dev = xyz.device
+    with _on(dev):
+        for k, wanted in enumerate((True, want_bond_angles, want_bond_lengths)):
+            if wanted and outs[k] is None:
+                outs[k] = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+        rc = 0
+        if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            rc = _lib.load().ps_backbone_from_dihedrals_backward_f32(
+                _ptr(xyz), _ptr(gx), _ptr(chain), _ptr(rmask), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                int(bool(include_cb)), B, N, A, _stream(xyz))
+    _lib.check(rc, "ps_backbone_from_dihedrals_backward_f32")
+    return tuple(outs)
+
+
 
 def check_distmat_shapes(d_cb, omega, theta, phi, mask=None, chain_breaks=None, lengths=None) -> None:
     """Shape rules of ``backbone_distmat_init`` on (B,L,L) inputs, on shapes only (no device, no launch): ValueError."""

@@ -178,7 +178,10 @@ class StructureBatch:
         and psi / omega at its last are never used.  ``bond_angles`` / ``bond_lengths`` (B, N, 3) override the ideal
         [N-CA-C, CA-C-N(next), C-N(next)-CA(next)] and [|N-CA|, |CA-C|, |C-N(next)|] (defaults: ``geometry.IDEAL_*``).
         Masked residues get zero coordinates and a zero mask; the atom mask is float32 ones / zeros.  Computed in float32
-        by one HIP launch (a segmented prefix scan of per-residue rigid transforms), on ``device=`` or the current GPU."""
+        by one HIP launch (a segmented prefix scan of per-residue rigid transforms), on ``device=`` or the current GPU.
+        When grad is enabled and ``dihedrals``, ``bond_angles`` or ``bond_lengths`` requires grad, the batch's coordinates
+        stay attached to the autograd graph (``geometry.backbone_from_dihedrals``: one HIP kernel backwards), so a loss on
+        e.g. :meth:`inter_residue_geometry` reaches the angles; the values are the same either way."""
         from .general import MAX_N_ATOMS_PER_RESIDUE
 
         if (chain_idx is not None and chain_ids is None) or (chain_idx is None and chain_ids is not None):
@@ -191,7 +194,11 @@ class StructureBatch:
         def on_dev(t):
             return None if t is None else t.to(dev)
 
-        xyz, atom_mask = ops.backbone_from_dihedrals(
+        builder = ops.backbone_from_dihedrals
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (dihedrals, bond_angles, bond_lengths)):
+            from . import geometry
+            builder = geometry.backbone_from_dihedrals   # the same launch, with the HIP backward kernel attached
+        xyz, atom_mask = builder(
             on_dev(dihedrals), on_dev(chain_idx), on_dev(residue_mask), on_dev(bond_angles), on_dev(bond_lengths),
             include_cb=include_cb, n_slots=MAX_N_ATOMS_PER_RESIDUE)
         return cls(xyz, atom_mask, chain_idx, chain_ids, seq, residue_idx, **kwargs)

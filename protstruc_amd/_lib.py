@@ -3,9 +3,11 @@
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
 """
+import contextlib
 import ctypes
 import os
 import threading
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROTSTRUC_AMD_LIB selects another build of the library: the same-process A/B of two builds (tools/k1_ab_libs.py)
@@ -159,11 +161,13 @@ def check(code, what):
         raise HipLibraryError(f"{what} failed: hipError {code} ({msg.decode() if msg else '?'})")
 
 
-# ---- K1 launch configuration: a per-device table on the HOST side --------------------------------------------------
-# The library itself is stateless (every launch takes its configuration as an argument).  What the Python shell keeps
-# is one small dict per device -- the autotuner's choice for that device's output buffers, plus whatever a test or
-# tool set explicitly -- guarded by a lock and snapshotted into a fresh struct for every launch, so a thread that
-# changes a knob can never tear the configuration another thread is launching with.
+# ---- launch settings: one immutable record per device, on the HOST side ---------------------------------------------
+# The library itself is stateless (every launch takes its configuration as an argument).  What the Python shell keeps is
+# one record per device: the K1 field values (the autotuner's choice for that device's output buffers, plus whatever a
+# test or tool set explicitly), the ps_k1_config struct built from them with its ctypes.byref, and the K3 / featuriser
+# arithmetic mode.  A record is built once and never mutated: every change builds a new one under _lock and swaps it
+# into _records, so a launch reads its settings with one lock-free dict lookup and a thread that changes a knob can
+# never tear the configuration another thread is launching with (the library copies the struct by value).
 _K1_KEYS = {   # tuning key -> (struct field, lowest, highest)
     "k1_exact_sqrt": ("exact_sqrt", 0, 1), "k1_variant": ("variant", 0, 1), "k1_flat": ("flat", 0, 4),
     "k1_rows_per_block": ("rows_per_block", 1, 32), "k1_lds_pad_kb": ("lds_pad_kb", -1, 120),
@@ -171,8 +175,24 @@ _K1_KEYS = {   # tuning key -> (struct field, lowest, highest)
     "k1_jt": ("jt", 0, 128), "k1_xcd_remap": ("xcd_remap", 0, 1), "k1_store_nt": ("store_nt", 0, 1),
     "k1_flat_fl_log2": ("flat_fl_log2", 0, 7), "k1_rowphase": ("rowphase", 0, 255), "k1_experiment": ("experiment", 0, 31),
 }
-_k1_lock = threading.RLock()
-_k1_table = {}   # device index -> {field: value}
+_lock = threading.RLock()
+_records = {}   # device index -> _Record
+
+
+class _Record(NamedTuple):
+    fields: dict        # ps_k1_config field -> value
+    cfg: K1Config       # the struct built from ``fields``
+    ref: object         # ctypes.byref(cfg): what a launch passes
+    exact_angles: int   # 0 fast / 1 the reference's order of operations
+
+
+def _make_record(fields, exact_angles):
+    cfg = K1Config(**fields)
+    return _Record(fields, cfg, ctypes.byref(cfg), exact_angles)
+
+
+def _env_flag(name):
+    return 1 if os.environ.get(name, "0") not in ("", "0") else 0
 
 
 def _device_index(device=None):
@@ -189,44 +209,113 @@ def _device_index(device=None):
     return d.index if d.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
 
 
-def _k1_defaults():
-    cfg = K1Config()
-    load().ps_k1_config_default(ctypes.byref(cfg))
-    d = {f: getattr(cfg, f) for f, _ in K1Config._fields_}
-    # K1 uses the hardware square root (<= 1 ulp) unless the user asks for the correctly rounded one
-    if os.environ.get("PROTSTRUC_AMD_EXACT_SQRT", "0") not in ("", "0"):
-        d["exact_sqrt"] = 1
-    return d
-
-
-def _k1_entry(device):
+def _record(device=None):
+    """The current record of ``device``; its first use builds it from ``ps_k1_config_default`` and the environment."""
     idx = _device_index(device)
-    with _k1_lock:
-        if idx not in _k1_table:
-            _k1_table[idx] = _k1_defaults()
-        return _k1_table[idx]
+    rec = _records.get(idx)      # the hit path takes no lock: records are replaced, never mutated
+    if rec is None:
+        with _lock:
+            rec = _records.get(idx)
+            if rec is None:
+                cfg = K1Config()
+                load().ps_k1_config_default(ctypes.byref(cfg))
+                fields = {f: getattr(cfg, f) for f, _ in K1Config._fields_}
+                # K1 uses the hardware square root (<= 1 ulp) unless the user asks for the correctly rounded one
+                if _env_flag("PROTSTRUC_AMD_EXACT_SQRT"):
+                    fields["exact_sqrt"] = 1
+                rec = _records[idx] = _make_record(fields, _env_flag("PROTSTRUC_AMD_EXACT_ANGLES"))
+    return rec
 
 
-_k1_structs = {}   # device index -> ps_k1_config built from the table entry; REPLACED (never mutated) by set_tuning
+def _checked_field(key, value):
+    """(struct field, int value) of one tuning change, or HipLibraryError: every range rule of ``set_tuning``."""
+    value = int(value)
+    if key not in _K1_KEYS:
+        raise HipLibraryError(f"unknown tuning key {key!r} (known: {', '.join(sorted(_K1_KEYS))})")
+    field, lo, hi = _K1_KEYS[key]
+    if not lo <= value <= hi or (key == "k1_jt" and value not in (0, 16, 32, 64, 128)) \
+            or (key == "k1_flat_fl_log2" and value in (1, 2, 3)) or (key == "k1_flat" and value == 3):
+        raise HipLibraryError(f"tuning value {key}={value} outside its range")
+    if key == "k1_experiment" and value and not load().ps_has_experiments():
+        raise HipLibraryError("k1_experiment is reserved and must be 0: the product library contains no timing experiments")
+    return field, value
+
+
+def _change(device, changes):
+    """Swap in a record with ``changes`` (tuning keys and / or ``exact_angles``) applied; returns the one it replaced.
+    Everything is validated before anything is stored, so a refused change leaves the settings as they were."""
+    changes = dict(changes)
+    angles = changes.pop("exact_angles", None)
+    updates = dict(_checked_field(key, value) for key, value in changes.items())
+    with _lock:
+        idx = _device_index(device)
+        old = _record(idx)
+        _records[idx] = _make_record({**old.fields, **updates}, old.exact_angles if angles is None else (1 if angles else 0))
+    return old
+
+
+def set_tuning(key, value, device=None):
+    """Set one K1 knob for ``device`` (default: the current device).  Host-side state only."""
+    _change(device, {key: value})
+
+
+def get_tuning(key, device=None):
+    if key not in _K1_KEYS:
+        raise HipLibraryError(f"unknown tuning key {key!r}")
+    return _record(device).fields[_K1_KEYS[key][0]]
+
+
+def all_tuning(device=None):
+    """Every K1 knob of ``device`` as a dict (what ``bench.py`` reports)."""
+    fields = _record(device).fields
+    return {key: fields[field] for key, (field, _, _) in sorted(_K1_KEYS.items())}
+
+
+def set_exact_angles(flag, device=None):
+    """K3 / featuriser arithmetic mode of ``device`` (the library takes it per call, like exact_sqrt)."""
+    _change(device, {"exact_angles": flag})
+
+
+def get_exact_angles(device=None):
+    return _record(device).exact_angles
+
+
+@contextlib.contextmanager
+def scoped_settings(device=None, **changes):
+    """Apply ``changes`` -- tuning keys (``k1_jt=16``, ...) and / or ``exact_angles=...`` -- to ``device`` for the
+    length of a ``with`` block, through ``set_tuning``'s validation.  On exit, also by an exception, the record that
+    was current on entry is put back, which undoes any ``set_tuning`` / ``set_exact_angles`` made inside the block too.
+    For tests and tools: the exit overwrites whatever another thread changed on that device in the meantime."""
+    idx = _device_index(device)
+    old = _change(idx, changes)
+    try:
+        yield
+    finally:
+        with _lock:
+            _records[idx] = old
 
 
 def k1_config(device=None, **overrides):
     """Snapshot of ``device``'s K1 configuration as a ``ps_k1_config`` struct (fields overridden by keyword).
-    Without overrides the struct is the cached one of the device's current settings: it is never modified in place
-    (a change of settings installs a new struct), and the library copies it by value before launching, so sharing
-    it between launches and threads keeps the snapshot semantics."""
-    idx = _device_index(device)
-    if not overrides:
-        cfg = _k1_structs.get(idx)
-        if cfg is not None:
-            return cfg
-    with _k1_lock:
-        d = dict(_k1_entry(idx))
-        if not overrides:
-            cfg = _k1_structs[idx] = K1Config(**d)
-            return cfg
-    d.update(overrides)
-    return K1Config(**d)
+    Without overrides the struct is the one of the device's current record: it is never modified in place (a change
+    of settings installs a new record), and the library copies it by value before launching, so sharing it between
+    launches and threads keeps the snapshot semantics.  With overrides the struct is a fresh one."""
+    rec = _record(device)
+    return K1Config(**{**rec.fields, **overrides}) if overrides else rec.cfg
+
+
+def k1_config_ref(idx):
+    """``ctypes.byref`` of the configuration struct of device ``idx``'s current record (the launch hot path: one dict
+    lookup)."""
+    rec = _records.get(idx)
+    return (rec if rec is not None else _record(idx)).ref
+
+
+def row_range(N, row_begin, row_end, compact):
+    """K1 / K3 row addressing: (row_end, output rows, origin row) of residue rows [row_begin, row_end) written into a
+    compact buffer or into their own rows of a full-size one.  ``row_end`` None means N."""
+    row_end = N if row_end is None else row_end
+    return (row_end, row_end - row_begin, row_begin) if compact else (row_end, N, 0)
 
 
 def k1_plan(B, N, A, row_begin=0, row_end=None, *, compact=False, dist_misalign=0, mask_misalign=0, has_atom_mask=True,
@@ -234,8 +323,7 @@ def k1_plan(B, N, A, row_begin=0, row_end=None, *, compact=False, dist_misalign=
     """Which kernel ``ps_pairwise_distance_cfg_f32`` takes for this shape under ``device``'s current configuration
     (fields overridden by keyword): a dict with ``family``, ``kernel``, ``n_launches``, ``n_workgroups``, ``lds_bytes``.
     Pure host query (``ps_k1_plan_f32``): the library runs its own dispatcher in record-only mode."""
-    row_end = N if row_end is None else row_end
-    out_rows, origin = (row_end - row_begin, row_begin) if compact else (N, 0)
+    row_end, out_rows, origin = row_range(N, row_begin, row_end, compact)
     plan = K1Plan(struct_size=ctypes.sizeof(K1Plan))
     cfg = k1_config(device, **overrides)
     check(load().ps_k1_plan_f32(B, N, A, row_begin, row_end, out_rows, origin, dist_misalign, mask_misalign,
@@ -260,8 +348,7 @@ def k3_plan(B, N, A, slots_i, slots_j, n_points, row_begin=0, row_end=None, *, c
     ``skips_dead_groups``, ``faithful``), ``rows_per_task``, ``workgroups_per_cu``, grid, workgroup size and LDS bytes.
     Pure host query (``ps_k3_plan_f32``): the library runs its own dispatcher in record-only mode; no GPU needed.
     ``cu_count`` <= 0 means 256 (MI355X)."""
-    row_end = N if row_end is None else row_end
-    out_rows, origin = (row_end - row_begin, row_begin) if compact else (N, 0)
+    row_end, out_rows, origin = row_range(N, row_begin, row_end, compact)
     slots = [int(v) for v in slots_i] + [int(v) for v in slots_j]
     src = [0] * len(slots_i) + [1] * len(slots_j)
     arr = ctypes.c_int * n_points
@@ -277,71 +364,3 @@ def featuriser_plan(B, N, A=15, *, float_misalign=0, mask_misalign=0, exact_sqrt
     check(load().ps_featuriser_plan_f32(B, N, A, float_misalign, mask_misalign, int(exact_sqrt), int(exact_angles), cu_count,
                                         ctypes.byref(plan)), "ps_featuriser_plan_f32")
     return _k3_plan_dict(plan)
-
-
-_k1_refs = {}      # device index -> (struct, ctypes.byref(struct)) of the device's current settings
-
-
-def k1_config_ref(idx):
-    """``ctypes.byref`` of the cached configuration struct of device ``idx`` (the launch hot path: one dict lookup).
-    The pair (struct, reference) is replaced, never mutated, when a setting changes; the library copies the struct by
-    value before launching."""
-    ent = _k1_refs.get(idx)      # the hit path takes no lock: entries are replaced, never mutated
-    if ent is None:
-        with _k1_lock:           # look up, build and store under the lock set_tuning holds while it drops the entry,
-            ent = _k1_refs.get(idx)   # so a struct built from the settings before a change can never be cached after it
-            if ent is None:
-                cfg = k1_config(idx)
-                ent = _k1_refs[idx] = (cfg, ctypes.byref(cfg))
-    return ent[1]
-
-
-def set_tuning(key, value, device=None):
-    """Set one K1 knob for ``device`` (default: the current device).  Host-side state only."""
-    value = int(value)
-    if key not in _K1_KEYS:
-        raise HipLibraryError(f"unknown tuning key {key!r} (known: {', '.join(sorted(_K1_KEYS))})")
-    field, lo, hi = _K1_KEYS[key]
-    if not lo <= value <= hi or (key == "k1_jt" and value not in (0, 16, 32, 64, 128)) \
-            or (key == "k1_flat_fl_log2" and value in (1, 2, 3)) or (key == "k1_flat" and value == 3):
-        raise HipLibraryError(f"tuning value {key}={value} outside its range")
-    if key == "k1_experiment" and value and not load().ps_has_experiments():
-        raise HipLibraryError("k1_experiment is reserved and must be 0: the product library contains no timing experiments")
-    with _k1_lock:
-        idx = _device_index(device)
-        _k1_entry(idx)[field] = value
-        _k1_structs.pop(idx, None)     # the next launch builds a fresh struct; structs in flight stay as they were
-        _k1_refs.pop(idx, None)
-
-
-# ---- K3 arithmetic mode: per device, host side (the library takes it per call, like exact_sqrt) ----------------------
-_angle_mode = {}   # device index -> 0 fast / 1 the reference's order of operations
-
-
-def set_exact_angles(flag, device=None):
-    with _k1_lock:
-        _angle_mode[_device_index(device)] = 1 if flag else 0
-
-
-def get_exact_angles(device=None):
-    idx = _device_index(device)
-    v = _angle_mode.get(idx)
-    if v is None:
-        v = 1 if os.environ.get("PROTSTRUC_AMD_EXACT_ANGLES", "0") not in ("", "0") else 0
-        with _k1_lock:
-            v = _angle_mode.setdefault(idx, v)
-    return v
-
-
-def get_tuning(key, device=None):
-    if key not in _K1_KEYS:
-        raise HipLibraryError(f"unknown tuning key {key!r}")
-    with _k1_lock:
-        return _k1_entry(device)[_K1_KEYS[key][0]]
-
-
-def all_tuning(device=None):
-    """Every K1 knob of ``device`` as a dict (what ``bench.py`` reports)."""
-    with _k1_lock:
-        e = dict(_k1_entry(device))
-    return {key: e[field] for key, (field, _, _) in sorted(_K1_KEYS.items())}

@@ -275,16 +275,9 @@ def reconstruct_backbone_distmat_from_interresidue_geometry(d_cb, omega, theta, 
     if mask is not None and tuple(mask.shape) != shape:
         raise ValueError(f"mask must have the shape of d_cb {shape}, got {tuple(mask.shape)}")
     breaks = _chain_break_matrix(chain_breaks, B, L, batched)
-    if lengths is not None:
-        if isinstance(lengths, (int, np.integer)):
-            lengths = [int(lengths)]
-        if not isinstance(lengths, torch.Tensor):
-            lengths = np.asarray(lengths, dtype=np.int64)
-            if lengths.shape != (B,) or (lengths < 0).any() or (lengths > L).any():
-                raise ValueError(f"lengths must be {B} integers in 0 .. {L}, got {lengths.tolist()}")
-            lengths = lengths.astype(np.int32)
-        elif tuple(lengths.shape) != (B,):
-            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    lengths = ops.check_lengths(lengths, B, L)
+    if isinstance(lengths, np.ndarray):
+        lengths = lengths.astype(np.int32)
     ops.check_distmat_size(B, L)
 
     args = [d_cb, omega, theta, phi] + [t for t in (mask, breaks, lengths) if t is not None]
@@ -301,18 +294,8 @@ def reconstruct_backbone_distmat_from_interresidue_geometry(d_cb, omega, theta, 
 
 
 def _lengths_array(lengths, B: int, L: int):
-    if lengths is None:
-        return None
-    if isinstance(lengths, (int, np.integer)):
-        lengths = [int(lengths)]
-    if isinstance(lengths, torch.Tensor):
-        if tuple(lengths.shape) != (B,):
-            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
-        lengths = lengths.cpu().numpy()
-    lengths = np.asarray(lengths, dtype=np.int64)
-    if lengths.shape != (B,) or (lengths < 0).any() or (lengths > L).any():
-        raise ValueError(f"lengths must be {B} integers in 0 .. {L}, got {lengths.tolist()}")
-    return lengths
+    """``lengths`` on the host, as a checked int64 ndarray (None stays None)."""
+    return ops.check_lengths(lengths.cpu().numpy() if isinstance(lengths, torch.Tensor) else lengths, B, L)
 
 
 def initialize_backbone_with_mds(dist_mat, max_iter: int = 500, *, n_init: int = 4, eps: float = 1e-6,

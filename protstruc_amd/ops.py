@@ -63,18 +63,69 @@ def _check_rng_state(rng_state: Optional[torch.Tensor], device: torch.device) ->
                          f"(got shape {tuple(rng_state.shape)})")
 
 
+def _diffusion_operands(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor],
+                        noise: Optional[torch.Tensor]):
+    """The per-structure ``beta`` and the noise source of one diffusion step of ``xyz``, checked: (beta, noise) as
+    contiguous float32; one of ``rng_state`` and ``noise`` is required."""
+    B = xyz.shape[0]
+    beta = _f32c(beta, "beta")
+    if beta.shape != (B,):
+        raise ValueError(f"beta must have shape ({B},), got {tuple(beta.shape)}")
+    if noise is not None:
+        noise = _f32c(noise, "noise")
+        if noise.shape != xyz.shape:
+            raise ValueError("noise must have the shape of xyz")
+    elif rng_state is None:
+        raise ValueError("either rng_state or noise is required")
+    _check_rng_state(rng_state, xyz.device)
+    _same_device(xyz, beta=beta, noise=noise)
+    return beta, noise
+
+
+def _check_atom_slots(A: int, *slots) -> None:
+    for slot in slots:
+        if not 0 <= int(slot) < A:
+            raise ValueError(f"atom slot {slot} outside [0, {A})")
+
+
 def _same_device(ref: torch.Tensor, **tensors) -> None:
     for name, t in tensors.items():
         if t is not None and t.device != ref.device:
             raise ValueError(f"`{name}` lives on {t.device}, the coordinates on {ref.device}")
 
 
-def _check_out(t: Optional[torch.Tensor], shape, name: str, device: torch.device) -> None:
+def _check_out(t: Optional[torch.Tensor], shape, name: str, device: Optional[torch.device] = None,
+               dtype: torch.dtype = torch.float32) -> None:
+    """A caller-supplied output is dereferenced by a kernel: shape, dtype, layout and -- unless ``device`` is None, the
+    shape-only checkers -- the device are checked before anything is launched."""
     if t is None:
         return
-    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != torch.float32
-            or not t.is_contiguous() or t.device != device):
-        raise ValueError(f"{name} must be a contiguous float32 tensor of shape {tuple(shape)} on {device}")
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype
+            or not t.is_contiguous() or (device is not None and t.device != device)):
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)}"
+                         + (f" on {device}" if device is not None else ""))
+
+
+def _row_range(N: int, row_begin: int, row_end: Optional[int], compact: bool):
+    """``_lib.row_range`` with the rows checked against [0, N): (row_end, output rows, origin row)."""
+    row_end, out_rows, origin = _lib.row_range(N, row_begin, row_end, compact)
+    if not (0 <= row_begin <= row_end <= N):
+        raise ValueError(f"row range [{row_begin},{row_end}) outside [0,{N})")
+    return row_end, out_rows, origin
+
+
+def _require_f32c(t: torch.Tensor, name: str, message: str) -> None:
+    """An operand a kernel reads or updates where it lies: on the GPU, float32 and contiguous, or ValueError(message)."""
+    _require_device(t, name)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(message)
+
+
+def _launch(name: str, *args) -> None:
+    """Call entry point ``name`` of the library; HipLibraryError if it does not return hipSuccess."""
+    rc = getattr(_lib.load(), name)(*args)
+    if rc:
+        _lib.check(rc, name)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -282,6 +333,24 @@ def get_exact_angles(device=None) -> bool:
     return bool(_lib.get_exact_angles(device))
 
 
+def exact_sqrt(flag: bool = True, device=None):
+    """``with ops.exact_sqrt():`` -- ``set_exact_sqrt(flag, device)`` for the length of the block; on exit the device's
+    settings are what they were on entry (``_lib.scoped_settings``: for tests and tools, not for concurrent threads)."""
+    return _lib.scoped_settings(device, k1_exact_sqrt=1 if flag else 0)
+
+
+def exact_angles(flag: bool = True, device=None):
+    """``with ops.exact_angles():`` -- ``set_exact_angles(flag, device)`` for the length of the block (see ``exact_sqrt``)."""
+    return _lib.scoped_settings(device, exact_angles=flag)
+
+
+def k1_tuning(device=None, **knobs):
+    """``with ops.k1_tuning(jt=16, lds_pad_kb=0):`` -- K1 launch knobs, named like the ``_lib.k1_config`` overrides
+    (no ``k1_`` prefix), for the length of the block (see ``exact_sqrt``).  A ``_lib.set_tuning`` inside the block is
+    undone on exit too, so a sweep can step a knob in a loop under one enclosing scope."""
+    return _lib.scoped_settings(device, **{"k1_" + name: value for name, value in knobs.items()})
+
+
 def autotune_pairwise_distance(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor], out_dist: torch.Tensor,
                                out_mask: torch.Tensor):
     """Time K1's launch configurations on the given buffers now and keep the fastest for this device (results are
@@ -359,21 +428,16 @@ def pairwise_distance(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor] = Non
     destination of an all-gather)."""
     xyz = _f32c(xyz, "xyz")
     B, N, A = xyz.shape[:3]
-    row_end = N if row_end is None else row_end
-    if not (0 <= row_begin <= row_end <= N):
-        raise ValueError(f"row range [{row_begin},{row_end}) outside [0,{N})")
-    out_rows, origin = (row_end - row_begin, row_begin) if compact else (N, 0)
+    row_end, out_rows, origin = _row_range(N, row_begin, row_end, compact)
     shape = (B, out_rows, N, A, A)
     mask_u8 = _u8c(atom_mask, "atom_mask")
     _same_device(xyz, atom_mask=mask_u8)
     # caller-supplied outputs are dereferenced by a kernel launched on xyz.device: a CPU tensor or a tensor of another
     # GPU would be a wild device write, so device, shape, dtype and layout are all checked before anything is launched
-    for name, t, dt in (("out_dist", out_dist if want_dist else None, torch.float32),
-                        ("out_mask", out_mask if want_mask else None, torch.bool)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.device != xyz.device or tuple(t.shape) != shape
-                              or t.dtype != dt or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape {shape} "
-                             f"on {xyz.device}")
+    if want_dist:
+        _check_out(out_dist, shape, "out_dist", xyz.device)
+    if want_mask:
+        _check_out(out_mask, shape, "out_mask", xyz.device, torch.bool)
     with _on(xyz.device):
         dist = dmask = None
         if want_dist:
@@ -410,12 +474,9 @@ def backbone_dihedrals(xyz: torch.Tensor, chain_idx: torch.Tensor, residue_mask:
         dmask = torch.empty(B, N, 3, dtype=torch.bool, device=dev) if want_mask else None
         nterm = torch.empty(B, N, dtype=torch.bool, device=dev) if want_nterm else None
         cterm = torch.empty(B, N, dtype=torch.bool, device=dev) if want_cterm else None
-        rc = 0
         if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_backbone_dihedrals_f32(
-                _ptr(xyz), _ptr(chain), _ptr(rmask), _ptr(dih), _ptr(dmask), _ptr(nterm), _ptr(cterm), B, N, A,
-                _stream(xyz))
-    _lib.check(rc, "ps_backbone_dihedrals_f32")
+            _launch("ps_backbone_dihedrals_f32", _ptr(xyz), _ptr(chain), _ptr(rmask), _ptr(dih), _ptr(dmask),
+                    _ptr(nterm), _ptr(cterm), B, N, A, _stream(xyz))
     return dih, dmask, nterm, cterm
 
 
@@ -434,22 +495,17 @@ def pairwise_angles(xyz: torch.Tensor, slots_i: Sequence[int], slots_j: Sequence
     if len(slots) < n_points:
         raise IndexError(f"need {n_points} atoms in total, got {len(slots)}")  # the reference indexes past the end
     slots, src = slots[:n_points], src[:n_points]
-    row_end = N if row_end is None else row_end
-    if not (0 <= row_begin <= row_end <= N):
-        raise ValueError(f"row range [{row_begin},{row_end}) outside [0,{N})")
-    out_rows, origin = (row_end - row_begin, row_begin) if compact else (N, 0)
+    row_end, out_rows, origin = _row_range(N, row_begin, row_end, compact)
     arr = ctypes.c_int * n_points
     with _on(xyz.device):
         if out is None:
             out = torch.empty(B, out_rows, N, dtype=torch.float32, device=xyz.device)
         else:
             _check_out(out, (B, out_rows, N), "out", xyz.device)
-        rc = 0
         if not (B == 0 or N == 0 or row_begin == row_end):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_pairwise_angles_f32(
-                _ptr(xyz), _ptr(out), B, N, A, n_points, arr(*src), arr(*slots), row_begin, row_end, out_rows, origin,
-                _lib.get_exact_angles(xyz.device) | (2 if _one_column else 0), _stream(xyz))
-    _lib.check(rc, "ps_pairwise_angles_f32")
+            _launch("ps_pairwise_angles_f32", _ptr(xyz), _ptr(out), B, N, A, n_points, arr(*src), arr(*slots),
+                    row_begin, row_end, out_rows, origin, _lib.get_exact_angles(xyz.device) | (2 if _one_column else 0),
+                    _stream(xyz))
     return out
 
 
@@ -472,14 +528,11 @@ def inter_residue_geometry(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor] 
         fstride, kstride = (plane + 3) & ~3, (plane + 15) & ~15
         f = torch.empty(6, fstride, dtype=torch.float32, device=dev)
         k = torch.empty(3, kstride, dtype=torch.bool, device=dev)
-        rc = 0
         if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
             fp, kp = f.data_ptr(), k.data_ptr()                       # plane addresses by arithmetic, not by 9 views
-            rc = _lib.load().ps_inter_residue_geometry_f32(_ptr(xyz), _ptr(m), *[fp + 4 * fstride * i for i in range(6)],
-                                                           *[kp + kstride * i for i in range(3)], B, N, A,
-                                                           _lib.get_tuning("k1_exact_sqrt", dev),
-                                                           _lib.get_exact_angles(dev) | (2 if _one_column else 0), _stream(xyz))
-    _lib.check(rc, "ps_inter_residue_geometry_f32")
+            _launch("ps_inter_residue_geometry_f32", _ptr(xyz), _ptr(m), *[fp + 4 * fstride * i for i in range(6)],
+                    *[kp + kstride * i for i in range(3)], B, N, A, _lib.get_tuning("k1_exact_sqrt", dev),
+                    _lib.get_exact_angles(dev) | (2 if _one_column else 0), _stream(xyz))
     out = {key: f[i, :plane].view(B, N, N) for i, key in enumerate(fkeys)}
     out.update({key: k[i, :plane].view(B, N, N) for i, key in enumerate(mkeys)})
     return out
@@ -515,8 +568,7 @@ def check_inter_residue_geometry_backward_shapes(xyz, grads, atom_mask=None, out
             raise ValueError(f"grads[{key!r}] must have shape {(B, N, N)} to match xyz {shape}, got {tuple(g.shape)}")
         if not g.dtype.is_floating_point:
             raise ValueError(f"grads[{key!r}] must be a floating-point tensor, got {g.dtype}")
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+    _check_out(out, shape, "out")
 
 
 def inter_residue_geometry_backward(xyz: torch.Tensor, grads, atom_mask: Optional[torch.Tensor] = None, *,
@@ -537,11 +589,9 @@ def inter_residue_geometry_backward(xyz: torch.Tensor, grads, atom_mask: Optiona
     with _on(xyz.device):
         if out is None:
             out = torch.empty(B, N, A, 3, dtype=torch.float32, device=xyz.device)
-        rc = 0
         if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_inter_residue_geometry_backward_f32(_ptr(xyz), _ptr(m), *[_ptr(g) for g in gs], _ptr(out),
-                                                                    B, N, A, _stream(xyz))
-    _lib.check(rc, "ps_inter_residue_geometry_backward_f32")
+            _launch("ps_inter_residue_geometry_backward_f32", _ptr(xyz), _ptr(m), *[_ptr(g) for g in gs], _ptr(out), B,
+                    N, A, _stream(xyz))
     return out
 
 
@@ -558,11 +608,9 @@ def pointwise(mode: int, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, d: O
     dev = flat[0].device
     with _on(dev):
         out = torch.empty({2: (n, 9), 3: (n, 3)}.get(mode, (n,)), dtype=torch.float32, device=dev)
-        rc = 0
         if not (n == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_pointwise_f32(mode, _ptr(flat[0]), _ptr(flat[1]), _ptr(flat[2]),
-                                              _ptr(flat[3]) if mode in (1, 3) else None, _ptr(out), n, _stream(flat[0]))
-    _lib.check(rc, "ps_pointwise_f32")
+            _launch("ps_pointwise_f32", mode, _ptr(flat[0]), _ptr(flat[1]), _ptr(flat[2]),
+                    _ptr(flat[3]) if mode in (1, 3) else None, _ptr(out), n, _stream(flat[0]))
     if mode == 2:
         return out.reshape(*shape, 3, 3)
     return out.reshape(*shape, 3) if mode == 3 else out.reshape(shape)
@@ -601,12 +649,9 @@ def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.T
     with _on(dev):
         xyz = torch.empty(B, N, n_slots, 3, dtype=torch.float32, device=dev)
         atom_mask = torch.empty(B, N, n_slots, dtype=torch.float32, device=dev)
-        rc = 0
         if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_backbone_from_dihedrals_f32(
-                _ptr(dih), _ptr(ang), _ptr(lens), _ptr(chain), _ptr(rmask), _ptr(xyz), _ptr(atom_mask), int(bool(include_cb)),
-                B, N, n_slots, _stream(dih))
-    _lib.check(rc, "ps_backbone_from_dihedrals_f32")
+            _launch("ps_backbone_from_dihedrals_f32", _ptr(dih), _ptr(ang), _ptr(lens), _ptr(chain), _ptr(rmask),
+                    _ptr(xyz), _ptr(atom_mask), int(bool(include_cb)), B, N, n_slots, _stream(dih))
     return xyz, atom_mask
 
 
@@ -631,12 +676,9 @@ def check_backbone_from_dihedrals_backward_shapes(xyz, grad_xyz, chain_idx=None,
         if not isinstance(out, (tuple, list)) or len(out) != 3:
             raise ValueError("out must be a (grad_dihedrals, grad_bond_angles, grad_bond_lengths) triple (None where not wanted)")
         for name, t, wanted in (("out[0]", out[0], True), ("out[1]", out[1], want_bond_angles), ("out[2]", out[2], want_bond_lengths)):
-            if t is None:
-                continue
-            if not wanted:
+            if t is not None and not wanted:
                 raise ValueError(f"{name} is given but that gradient is not wanted")
-            if tuple(t.shape) != (B, N, 3) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {(B, N, 3)}")
+            _check_out(t, (B, N, 3), name)
 
 
 def backbone_from_dihedrals_backward(xyz: torch.Tensor, grad_xyz: torch.Tensor, chain_idx: Optional[torch.Tensor] = None,
@@ -664,12 +706,9 @@ def backbone_from_dihedrals_backward(xyz: torch.Tensor, grad_xyz: torch.Tensor, 
         for k, wanted in enumerate((True, want_bond_angles, want_bond_lengths)):
             if wanted and outs[k] is None:
                 outs[k] = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-        rc = 0
         if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_backbone_from_dihedrals_backward_f32(
-                _ptr(xyz), _ptr(gx), _ptr(chain), _ptr(rmask), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
-                int(bool(include_cb)), B, N, A, _stream(xyz))
-    _lib.check(rc, "ps_backbone_from_dihedrals_backward_f32")
+            _launch("ps_backbone_from_dihedrals_backward_f32", _ptr(xyz), _ptr(gx), _ptr(chain), _ptr(rmask),
+                    _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), int(bool(include_cb)), B, N, A, _stream(xyz))
     return tuple(outs)
 
 
@@ -716,11 +755,9 @@ def backbone_distmat_init(d_cb: torch.Tensor, omega: torch.Tensor, theta: torch.
     dev = d.device
     with _on(dev):
         out = torch.empty(B, 3, 3, L, L, dtype=torch.float32, device=dev)
-        rc = 0
         if not (B == 0 or L == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_backbone_distmat_init_f32(_ptr(d), _ptr(om), _ptr(th), _ptr(ph), _ptr(m), _ptr(brk),
-                                                          _ptr(lens), _ptr(out), B, L, _stream(d))
-    _lib.check(rc, "ps_backbone_distmat_init_f32")
+            _launch("ps_backbone_distmat_init_f32", _ptr(d), _ptr(om), _ptr(th), _ptr(ph), _ptr(m), _ptr(brk),
+                    _ptr(lens), _ptr(out), B, L, _stream(d))
     return out
 
 
@@ -749,18 +786,14 @@ def floyd_warshall_(D: torch.Tensor, G: int = 1) -> torch.Tensor:
     Bit for bit the sequential float32 loop when every entry is >= 0 and not NaN.  The workspace comes from torch's
     allocator on the current stream, so the call can be captured in a graph."""
     B, L = check_floyd_warshall_shape(D, G)
-    _require_device(D, "D")
-    if D.dtype != torch.float32 or not D.is_contiguous():
-        raise ValueError("D must be a contiguous float32 tensor (it is updated in place)")
+    _require_f32c(D, "D", "D must be a contiguous float32 tensor (it is updated in place)")
     lib = _lib.load()
     dev = D.device
     with _on(dev):
-        rc = 0
         if not (B == 0 or L == 0):
             nbytes = lib.ps_floyd_warshall_workspace_bytes(B, G, L)
             ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            rc = lib.ps_floyd_warshall_f32(_ptr(D), B, G, L, _ptr(ws), nbytes, _stream(D))
-    _lib.check(rc, "ps_floyd_warshall_f32")
+            _launch("ps_floyd_warshall_f32", _ptr(D), B, G, L, _ptr(ws), nbytes, _stream(D))
     return D
 
 
@@ -772,18 +805,32 @@ def backbone_distmat_finish_(D: torch.Tensor, chain_breaks: Optional[torch.Tenso
     for name, t, want in (("chain_breaks", chain_breaks, (B, L)), ("lengths", lengths, (B,))):
         if t is not None and tuple(t.shape) != want:
             raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
-    _require_device(D, "D")
-    if D.dtype != torch.float32 or not D.is_contiguous():
-        raise ValueError("D must be a contiguous float32 tensor (it is updated in place)")
+    _require_f32c(D, "D", "D must be a contiguous float32 tensor (it is updated in place)")
     _same_device(D, chain_breaks=chain_breaks, lengths=lengths)
     brk, lens = _u8c(chain_breaks, "chain_breaks"), _i32c(lengths, "lengths")
     dev = D.device
     with _on(dev):
-        rc = 0
         if not (B == 0 or L == 0):
-            rc = _lib.load().ps_backbone_distmat_finish_f32(_ptr(D), _ptr(brk), _ptr(lens), B, L, _stream(D))
-    _lib.check(rc, "ps_backbone_distmat_finish_f32")
+            _launch("ps_backbone_distmat_finish_f32", _ptr(D), _ptr(brk), _ptr(lens), B, L, _stream(D))
     return D
+
+
+def check_lengths(lengths, B: int, L: int):
+    """The ``lengths`` argument of a ragged batch of B structures of at most L residues, normalised: None, a (B,)
+    tensor as it is (its shape is checked, its values stay where they are -- no copy to the host) or host integers
+    as an int64 ndarray of B values in 0 .. L.  ValueError otherwise."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, (int, np.integer)):
+        lengths = [int(lengths)]
+    if not isinstance(lengths, torch.Tensor):
+        lengths = np.asarray(lengths, dtype=np.int64)
+    if tuple(lengths.shape) != (B,):
+        raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    if isinstance(lengths, np.ndarray) and ((lengths < 0).any() or (lengths > L).any()):
+        raise ValueError(f"lengths must lie in 0 .. {L}, got {lengths.tolist()}")
+    return lengths
+
 
 def check_smacof_shapes(D, G: int = 1, n_init: Optional[int] = None, max_iter: int = 300, eps: float = 1e-6, init=None,
                         lengths=None) -> Tuple[int, int, int]:
@@ -806,11 +853,7 @@ def check_smacof_shapes(D, G: int = 1, n_init: Optional[int] = None, max_iter: i
             raise ValueError("init must hold at least one start")
     else:
         K = 4 if n_init is None else n_init
-    if lengths is not None:
-        if tuple(lengths.shape) != (B,):
-            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
-        if isinstance(lengths, np.ndarray) and lengths.size and (lengths.min() < 0 or lengths.max() > L):
-            raise ValueError(f"lengths must lie in 0 .. {L}, got {lengths.tolist()}")
+    check_lengths(lengths, B, L)
     if K > 65535 or B * K * G * L * 3 >= 2 ** 31:
         raise ValueError(f"{B} x {K} starts of {G * L} nodes are too many for one call")
     return B, L, K
@@ -851,18 +894,16 @@ def smacof(D: torch.Tensor, G: int = 1, *, n_init: Optional[int] = None, max_ite
     ``init``) -- or K = ``n_init`` (default 4) random ones drawn on the host exactly as sklearn draws them from
     ``random_state`` (None: numpy's global state; see ``smacof_random_starts``).  ``lengths`` (B,) restricts structure
     b to the nodes i < lengths[b]; padded rows of X are NaN.  Without ``random_state`` draws the call is capturable."""
-    if lengths is not None and not isinstance(lengths, torch.Tensor):
-        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     B, L, K = check_smacof_shapes(D, G, n_init, max_iter, eps, init, lengths)
+    lengths = check_lengths(lengths, B, L)
     if random_state is not None and init is not None:
         raise ValueError("random_state draws starts; it cannot be combined with an explicit init")
     _require_device(D, "D")
     dev = D.device
     d = _f32c(D, "D")
     if init is None:
-        lens_host = None if lengths is None else (lengths.cpu().numpy() if isinstance(lengths, torch.Tensor) else lengths)
-        if lens_host is not None and lens_host.size and (lens_host.min() < 0 or lens_host.max() > L):
-            raise ValueError(f"lengths must lie in 0 .. {L}, got {lens_host.tolist()}")
+        # the random starts are drawn on the host, per structure length: a tensor's values are fetched (and checked)
+        lens_host = check_lengths(lengths.cpu().numpy(), B, L) if isinstance(lengths, torch.Tensor) else lengths
         starts = smacof_random_starts(B, K, G, L, lens_host, random_state)
         x0 = torch.from_numpy(starts.astype(np.float32)).to(dev)
     else:
@@ -878,13 +919,11 @@ def smacof(D: torch.Tensor, G: int = 1, *, n_init: Optional[int] = None, max_ite
         X = torch.empty(B, G * L, 3, dtype=torch.float32, device=dev)
         stress = torch.empty(B, dtype=torch.float64, device=dev)
         n_iter = torch.empty(B, dtype=torch.int32, device=dev)
-        rc = 0
         if B > 0:
             nbytes = lib.ps_smacof_workspace_bytes(B, K, G, L)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
-            rc = lib.ps_smacof_f32(_ptr(d), B, G, L, _ptr(lens), _ptr(x0), K, max_iter, float(eps), _ptr(X),
-                                   _ptr(stress), _ptr(n_iter), _ptr(ws), ws.numel() * 8, _stream(d))
-    _lib.check(rc, "ps_smacof_f32")
+            _launch("ps_smacof_f32", _ptr(d), B, G, L, _ptr(lens), _ptr(x0), K, max_iter, float(eps), _ptr(X),
+                    _ptr(stress), _ptr(n_iter), _ptr(ws), ws.numel() * 8, _stream(d))
     return X, stress, n_iter
 
 
@@ -905,8 +944,7 @@ def mds_backbone_finish(X: torch.Tensor, lengths: Optional[torch.Tensor] = None,
     not have); ``mirror=False`` never mirrors.  O of the last residue is placed from N of the first (the reference's
     np.roll).  Padded residues (``lengths``) are NaN; a NaN in a structure makes its whole output NaN."""
     B, L = check_backbone_coords_shape(X, 3)
-    if lengths is not None and tuple(lengths.shape) != (B,):
-        raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    lengths = check_lengths(lengths, B, L)
     x = _f32c(X, "X")
     _same_device(x, lengths=lengths)
     lens = _i32c(lengths, "lengths")
@@ -914,11 +952,9 @@ def mds_backbone_finish(X: torch.Tensor, lengths: Optional[torch.Tensor] = None,
     dev = x.device
     with _on(dev):
         out = torch.empty(B, A, L, 3, dtype=torch.float32, device=dev)
-        rc = 0
         if not (B == 0 or L == 0):
-            rc = _lib.load().ps_mds_backbone_finish_f32(_ptr(x), _ptr(lens), B, L, 1 if mirror else 0, A, _ptr(out),
-                                                       _stream(x))
-    _lib.check(rc, "ps_mds_backbone_finish_f32")
+            _launch("ps_mds_backbone_finish_f32", _ptr(x), _ptr(lens), B, L, 1 if mirror else 0, A, _ptr(out),
+                    _stream(x))
     return out
 
 
@@ -931,11 +967,9 @@ def frames(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *, wan
     with _on(dev):
         rot = torch.empty(B, N, 3, 3, dtype=torch.float32, device=dev) if want_rot else None
         trans = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if want_trans else None
-        rc = 0
         if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_frames_f32(_ptr(xyz), _ptr(rot), _ptr(trans), B, N, A, int(a1), int(a2), int(a3),
-                                           int(t_atom), _stream(xyz))
-    _lib.check(rc, "ps_frames_f32")
+            _launch("ps_frames_f32", _ptr(xyz), _ptr(rot), _ptr(trans), B, N, A, int(a1), int(a2), int(a3), int(t_atom),
+                    _stream(xyz))
     return rot, trans
 
 
@@ -943,27 +977,13 @@ def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Te
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS
     words, [0] = seed, [1] = draw offset, the rest zero."""
-    _require_device(xyz, "xyz")
-    if xyz.dtype != torch.float32 or not xyz.is_contiguous():
-        raise ValueError("diffuse_ needs a contiguous float32 xyz (it is updated in place)")
+    _require_f32c(xyz, "xyz", "diffuse_ needs a contiguous float32 xyz (it is updated in place)")
     B = xyz.shape[0]
     nps = xyz[0].numel() if B else 0
-    beta = _f32c(beta, "beta")
-    if beta.shape != (B,):
-        raise ValueError(f"beta must have shape ({B},), got {tuple(beta.shape)}")
-    if noise is not None:
-        noise = _f32c(noise, "noise")
-        if noise.shape != xyz.shape:
-            raise ValueError("noise must have the shape of xyz")
-    elif rng_state is None:
-        raise ValueError("either rng_state or noise is required")
-    _check_rng_state(rng_state, xyz.device)
-    _same_device(xyz, beta=beta, noise=noise)
+    beta, noise = _diffusion_operands(xyz, beta, rng_state, noise)
     with _on(xyz.device):
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_diffuse_f32(_ptr(xyz), _ptr(beta), B, nps, _ptr(rng_state), _ptr(noise), _stream(xyz))
-    _lib.check(rc, "ps_diffuse_f32")
+            _launch("ps_diffuse_f32", _ptr(xyz), _ptr(beta), B, nps, _ptr(rng_state), _ptr(noise), _stream(xyz))
     return xyz
 
 
@@ -971,35 +991,19 @@ def diffuse_frames_(xyz: torch.Tensor, beta: torch.Tensor, a1: int, a2: int, a3:
                     rng_state: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                     out_rot: Optional[torch.Tensor] = None, out_trans: Optional[torch.Tensor] = None):
     """Fused K5 + K4: diffuse ``xyz`` in place and return the frames of the new coordinates."""
-    _require_device(xyz, "xyz")
-    if xyz.dtype != torch.float32 or not xyz.is_contiguous():
-        raise ValueError("diffuse_frames_ needs a contiguous float32 xyz (it is updated in place)")
+    _require_f32c(xyz, "xyz", "diffuse_frames_ needs a contiguous float32 xyz (it is updated in place)")
     B, N, A = xyz.shape[:3]
-    beta = _f32c(beta, "beta")
-    if beta.shape != (B,):
-        raise ValueError(f"beta must have shape ({B},), got {tuple(beta.shape)}")
-    if noise is not None:
-        noise = _f32c(noise, "noise")
-        if noise.shape != xyz.shape:
-            raise ValueError("noise must have the shape of xyz")
-    elif rng_state is None:
-        raise ValueError("either rng_state or noise is required")
-    _check_rng_state(rng_state, xyz.device)
-    _same_device(xyz, beta=beta, noise=noise)
-    for slot in (a1, a2, a3, t_atom):
-        if not 0 <= int(slot) < A:
-            raise ValueError(f"atom slot {slot} outside [0, {A})")
+    beta, noise = _diffusion_operands(xyz, beta, rng_state, noise)
+    _check_atom_slots(A, a1, a2, a3, t_atom)
     dev = xyz.device
     _check_out(out_rot, (B, N, 3, 3), "out_rot", dev)
     _check_out(out_trans, (B, N, 3), "out_trans", dev)
     with _on(dev):
         rot = out_rot if out_rot is not None else torch.empty(B, N, 3, 3, dtype=torch.float32, device=dev)
         trans = out_trans if out_trans is not None else torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_diffuse_frames_f32(_ptr(xyz), _ptr(beta), B, N, A, _ptr(rng_state), _ptr(noise), _ptr(rot),
-                                                   _ptr(trans), int(a1), int(a2), int(a3), int(t_atom), _stream(xyz))
-    _lib.check(rc, "ps_diffuse_frames_f32")
+            _launch("ps_diffuse_frames_f32", _ptr(xyz), _ptr(beta), B, N, A, _ptr(rng_state), _ptr(noise), _ptr(rot),
+                    _ptr(trans), int(a1), int(a2), int(a3), int(t_atom), _stream(xyz))
     return rot, trans
 
 
@@ -1010,9 +1014,7 @@ def diffusion_trajectory_(xyz: torch.Tensor, betas: torch.Tensor, a1: int, a2: i
     """K55: T diffusion steps in one launch, coordinates resident in LDS.  ``betas``: (T, B).
     Returns (rot (T,B,N,3,3) | None, trans (T,B,N,3) | None, xyz_traj (T,B,N,A,3) | None); ``xyz`` ends as step T.
     ``out_rot`` / ``out_trans`` / ``out_xyz`` supply caller-owned output buffers (and imply the matching ``want_``)."""
-    _require_device(xyz, "xyz")
-    if xyz.dtype != torch.float32 or not xyz.is_contiguous():
-        raise ValueError("diffusion_trajectory_ needs a contiguous float32 xyz (it is updated in place)")
+    _require_f32c(xyz, "xyz", "diffusion_trajectory_ needs a contiguous float32 xyz (it is updated in place)")
     B, N, A = xyz.shape[:3]
     betas = _f32c(betas, "betas")
     if betas.ndim != 2 or betas.shape[1] != B:
@@ -1021,9 +1023,7 @@ def diffusion_trajectory_(xyz: torch.Tensor, betas: torch.Tensor, a1: int, a2: i
     if rng_state is None:
         raise ValueError(f"rng_state must be an int64 tensor of {RNG_STATE_WORDS} words")
     _check_rng_state(rng_state, xyz.device)
-    for slot in (a1, a2, a3, t_atom):
-        if not 0 <= int(slot) < A:
-            raise ValueError(f"atom slot {slot} outside [0, {A})")
+    _check_atom_slots(A, a1, a2, a3, t_atom)
     dev = xyz.device
     _same_device(xyz, betas=betas)
     _check_out(out_rot, (T, B, N, 3, 3), "out_rot", dev)
@@ -1036,20 +1036,15 @@ def diffusion_trajectory_(xyz: torch.Tensor, betas: torch.Tensor, a1: int, a2: i
             torch.empty(T, B, N, 3, dtype=torch.float32, device=dev) if want_trans else None)
         traj = out_xyz if out_xyz is not None else (
             torch.empty(T, B, N, A, 3, dtype=torch.float32, device=dev) if want_xyz else None)
-        rc = 0
         if not (xyz.numel() == 0 or T == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_diffusion_trajectory_f32(_ptr(xyz), _ptr(betas), T, B, N, A, _ptr(rng_state), _ptr(rot),
-                                                         _ptr(trans), _ptr(traj), int(a1), int(a2), int(a3), int(t_atom),
-                                                         _stream(xyz))
-    _lib.check(rc, "ps_diffusion_trajectory_f32")
+            _launch("ps_diffusion_trajectory_f32", _ptr(xyz), _ptr(betas), T, B, N, A, _ptr(rng_state), _ptr(rot),
+                    _ptr(trans), _ptr(traj), int(a1), int(a2), int(a3), int(t_atom), _stream(xyz))
     return rot, trans, traj
 
 
 def standardize_(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor]):
     """K6, in place.  Returns (mu (B,3), std (B,3))."""
-    _require_device(xyz, "xyz")
-    if xyz.dtype != torch.float32 or not xyz.is_contiguous():
-        raise ValueError("standardize_ needs a contiguous float32 xyz (it is updated in place)")
+    _require_f32c(xyz, "xyz", "standardize_ needs a contiguous float32 xyz (it is updated in place)")
     B, N, A = xyz.shape[:3]
     m = _u8c(atom_mask, "atom_mask")
     dev = xyz.device
@@ -1058,36 +1053,28 @@ def standardize_(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor]):
         alloc = torch.empty if N * A > 0 else (lambda *a, **k: torch.full(a, float("nan"), **k))
         mu = alloc(B, 3, dtype=torch.float32, device=dev)
         std = alloc(B, 3, dtype=torch.float32, device=dev)
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_standardize_f32(_ptr(xyz), _ptr(m), _ptr(mu), _ptr(std), B, N, A, _stream(xyz))
-    _lib.check(rc, "ps_standardize_f32")
+            _launch("ps_standardize_f32", _ptr(xyz), _ptr(m), _ptr(mu), _ptr(std), B, N, A, _stream(xyz))
     return mu, std
 
 
 def affine_(xyz: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
     """xyz[b] <- xyz[b] * scale[b] + shift[b] per axis, in place (unstandardize)."""
-    _require_device(xyz, "xyz")
-    if xyz.dtype != torch.float32 or not xyz.is_contiguous():
-        raise ValueError("affine_ needs a contiguous float32 xyz (it is updated in place)")
+    _require_f32c(xyz, "xyz", "affine_ needs a contiguous float32 xyz (it is updated in place)")
     B = xyz.shape[0]
     n_atoms = xyz[0].numel() // 3 if B else 0
     scale = _f32c(scale, "scale")
     shift = _f32c(shift, "shift")
     with _on(xyz.device):
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_affine_f32(_ptr(xyz), _ptr(scale), _ptr(shift), B, n_atoms, _stream(xyz))
-    _lib.check(rc, "ps_affine_f32")
+            _launch("ps_affine_f32", _ptr(xyz), _ptr(scale), _ptr(shift), B, n_atoms, _stream(xyz))
     return xyz
 
 
 def rigid(xyz: torch.Tensor, R: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, *,
           transpose: bool = False, inplace: bool = False) -> torch.Tensor:
     """x' = R x + t (or R^T x + t).  R: (3,3) | (B,3,3) | (B,N,3,3);  t: (3,) | (B,3) | (B,N,3) | (B,1,3) | (B,N,A,3)."""
-    _require_device(xyz, "xyz")
-    if xyz.dtype != torch.float32 or not xyz.is_contiguous():
-        raise ValueError("rigid needs a contiguous float32 xyz")
+    _require_f32c(xyz, "xyz", "rigid needs a contiguous float32 xyz")
     B, N, A = xyz.shape[:3]
     r_mode = t_mode = 0
     if R is not None:
@@ -1113,11 +1100,9 @@ def rigid(xyz: torch.Tensor, R: Optional[torch.Tensor] = None, t: Optional[torch
         t = t.contiguous()
     with _on(xyz.device):
         out = xyz if inplace else torch.empty_like(xyz)
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_rigid_f32(_ptr(xyz), _ptr(out), _ptr(R), r_mode, int(transpose), _ptr(t), t_mode, B, N, A,
-                                          _stream(xyz))
-    _lib.check(rc, "ps_rigid_f32")
+            _launch("ps_rigid_f32", _ptr(xyz), _ptr(out), _ptr(R), r_mode, int(transpose), _ptr(t), t_mode, B, N, A,
+                    _stream(xyz))
     return out
 
 
@@ -1129,10 +1114,8 @@ def center_of_mass(xyz: torch.Tensor, atom: int = 1) -> torch.Tensor:
         # no residues: the reference's nanmean over nothing is NaN
         com = (torch.empty if xyz.numel() else (lambda *a, **k: torch.full(a, float("nan"), **k)))(
             B, 3, dtype=torch.float32, device=xyz.device)
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_center_of_mass_f32(_ptr(xyz), _ptr(com), B, N, A, int(atom), _stream(xyz))
-    _lib.check(rc, "ps_center_of_mass_f32")
+            _launch("ps_center_of_mass_f32", _ptr(xyz), _ptr(com), B, N, A, int(atom), _stream(xyz))
     return com
 
 
@@ -1146,11 +1129,9 @@ def frames_to_backbone(rot: torch.Tensor, trans: torch.Tensor, ideal: torch.Tens
     ideal = _f32c(ideal.to(rot.device), "ideal")
     with _on(rot.device):
         xyz = torch.empty(B, N, n_slots, 3, dtype=torch.float32, device=rot.device)
-        rc = 0
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
-            rc = _lib.load().ps_frames_to_backbone_f32(_ptr(rot), _ptr(trans), _ptr(ideal), ideal.shape[0], _ptr(xyz), B, N,
-                                                       n_slots, _stream(rot))
-    _lib.check(rc, "ps_frames_to_backbone_f32")
+            _launch("ps_frames_to_backbone_f32", _ptr(rot), _ptr(trans), _ptr(ideal), ideal.shape[0], _ptr(xyz), B, N,
+                    n_slots, _stream(rot))
     return xyz
 
 
@@ -1169,9 +1150,8 @@ def kabsch(src: torch.Tensor, dst: torch.Tensor, atom_mask: torch.Tensor):
     with _on(dev):
         R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
         t = torch.empty(B, 3, dtype=torch.float32, device=dev)
-        rc = _lib.load().ps_kabsch_f32(_ptr(src), _ptr(dst), _ptr(m), _ptr(R), _ptr(t), B, n_atoms,
-                                       int(dst.shape[0] == 1 and B > 1), int(m.shape[0] == 1 and B > 1), _stream(src))
-    _lib.check(rc, "ps_kabsch_f32")
+        _launch("ps_kabsch_f32", _ptr(src), _ptr(dst), _ptr(m), _ptr(R), _ptr(t), B, n_atoms,
+                int(dst.shape[0] == 1 and B > 1), int(m.shape[0] == 1 and B > 1), _stream(src))
     return R, t
 
 
@@ -1182,7 +1162,6 @@ def min_dist_to_points(xyz_one: torch.Tensor, query: torch.Tensor, atom: int = 1
     N, A = xyz_one.shape[:2]
     with _on(xyz_one.device):
         out = torch.empty(N, dtype=torch.float32, device=xyz_one.device)
-        rc = _lib.load().ps_min_dist_to_points_f32(_ptr(xyz_one), _ptr(query), _ptr(out), N, A, int(atom),
-                                                   query.shape[0], _stream(xyz_one))
-    _lib.check(rc, "ps_min_dist_to_points_f32")
+        _launch("ps_min_dist_to_points_f32", _ptr(xyz_one), _ptr(query), _ptr(out), N, A, int(atom), query.shape[0],
+                _stream(xyz_one))
     return out

@@ -60,15 +60,12 @@ def test_tuning_is_a_per_device_host_table(lib_path):
     """K1 knobs live in a per-device table on the Python side and reach the library as a per-call argument: setting
     one device's knob never changes another device's, and unknown keys / values are refused."""
     from protstruc_amd import _lib
-    old0, old1 = _lib.get_tuning("k1_rows_per_block", 0), _lib.get_tuning("k1_rows_per_block", 1)
-    try:
-        _lib.set_tuning("k1_rows_per_block", 4, device=1)
+    old0 = _lib.get_tuning("k1_rows_per_block", 0)
+    with _lib.scoped_settings(1, k1_rows_per_block=4):
         assert _lib.get_tuning("k1_rows_per_block", 1) == 4 and _lib.get_tuning("k1_rows_per_block", 0) == old0
         assert _lib.k1_config(1).rows_per_block == 4 and _lib.k1_config(0).rows_per_block == old0
         assert _lib.k1_config(0, rows_per_block=2).rows_per_block == 2 and _lib.get_tuning("k1_rows_per_block", 0) == old0
         assert set(_lib.all_tuning(0)) == set(_lib._K1_KEYS)
-    finally:
-        _lib.set_tuning("k1_rows_per_block", old1, device=1)
     with pytest.raises(_lib.HipLibraryError):
         _lib.set_tuning("no_such_knob", 1)
     with pytest.raises(_lib.HipLibraryError):

@@ -136,14 +136,8 @@ def test_independent_of_the_forward_arithmetic_modes(ops):
     xyz, mask, grads = random_case(6, 2, 50, 15)
     xg, mg, gg = to_gpu(xyz, mask, grads)
     base = ops.inter_residue_geometry_backward(xg, gg, mg)
-    sq, an = ops.get_exact_sqrt(), ops.get_exact_angles()
-    try:
-        ops.set_exact_sqrt(True)
-        ops.set_exact_angles(True)
+    with ops.exact_sqrt(), ops.exact_angles():
         assert torch.equal(ops.inter_residue_geometry_backward(xg, gg, mg), base)
-    finally:
-        ops.set_exact_sqrt(sq)
-        ops.set_exact_angles(an)
 
 
 @pytest.mark.parametrize("shape", [(2, 33, 15), (1, 64, 7), (3, 5, 5)], ids=lambda s: "x".join(map(str, s)))

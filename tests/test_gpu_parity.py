@@ -70,12 +70,10 @@ def max_ulps(got, want):
 def k1_both_modes(fn):
     """fn() in the correctly rounded square-root mode, then in the default (hardware) mode: (exact, default)."""
     from protstruc_amd import ops
-    try:
-        ops.set_exact_sqrt(True)
+    with ops.exact_sqrt(True):
         exact = fn()
-    finally:
-        ops.set_exact_sqrt(False)
-    return exact, fn()
+    with ops.exact_sqrt(False):
+        return exact, fn()
 
 
 # ----------------------------------------------------------------------------- K1
@@ -148,7 +146,7 @@ def test_k1_every_kernel_family_vs_oracle(SB):
     keys = sorted({k for e in FAMILY_SHAPES for k in e[5]} | {"k1_exact_sqrt"})
     saved = {k: _lib.get_tuning(k) for k in keys}
     SENT, ran, ran_exact = 777.0, set(), set()
-    try:
+    with _lib.scoped_settings():
         for B, N, A, rows, compact, overrides, family in FAMILY_SHAPES:
             for k in keys:
                 _lib.set_tuning(k, overrides.get(k, saved[k]))
@@ -188,9 +186,6 @@ def test_k1_every_kernel_family_vs_oracle(SB):
             if not compact:
                 assert (d[:, :r0] == SENT).all() and (d[:, r1:] == SENT).all(), (family, B, N, A, "exact")
             ran_exact.add(family)
-    finally:
-        for k, v in saved.items():
-            _lib.set_tuning(k, v)
     assert ran == ALL_FAMILIES == ran_exact
 
 
@@ -255,11 +250,8 @@ def test_k1_special_values(SB, A, N):
     assert (tiny & (sq >= 2.0 ** -126)).any()
     assert not tiny[:, :N - 2, :N - 2].any()                 # everything else is as before: the 1e-5 gate covers it
     for exact in (False, True):
-        ops.set_exact_sqrt(exact)
-        try:
+        with ops.exact_sqrt(exact):
             d, m = SB.from_xyz(xyz, mask).pairwise_distance_matrix()
-        finally:
-            ops.set_exact_sqrt(False)
         d = d.cpu()
         assert torch.equal(m.cpu(), wmask)
         assert torch.equal(d.isnan(), want.isnan()), "NaN positions"
@@ -311,8 +303,7 @@ def test_k1_store_policy_variants_agree(SB):
     base = ops.pairwise_distance(xyz, mask)
     rd, rm = O.pairwise_distance_matrix_chunked(xyz.cpu(), mask.cpu())
     assert_close(base[0], rd)
-    nt0, rows0, var0, jt0 = (_lib.get_tuning(k) for k in ("k1_store_nt", "k1_rows_per_block", "k1_variant", "k1_jt"))
-    try:
+    with _lib.scoped_settings():
         for var in (0, 1):          # pattern kernel / slot-decode kernel
             for jt in (0, 16, 32, 64, 128):
                 for nt in (0, 1):
@@ -327,11 +318,6 @@ def test_k1_store_policy_variants_agree(SB):
                             m = torch.zeros_like(base[1])
                             ops.pairwise_distance(xyz, mask, out_dist=d, out_mask=m)
                             assert torch.equal(d, base[0]) and torch.equal(m, base[1]), (var, jt, nt, rows, remap)
-    finally:
-        _lib.set_tuning("k1_store_nt", nt0)
-        _lib.set_tuning("k1_rows_per_block", rows0)
-        _lib.set_tuning("k1_variant", var0)
-        _lib.set_tuning("k1_jt", jt0)
 
 
 def test_k1_pattern_kernel_single_plane_launches(SB):
@@ -341,7 +327,7 @@ def test_k1_pattern_kernel_single_plane_launches(SB):
     from protstruc_amd import _lib, ops
     keys = ("k1_jt", "k1_rows_per_block", "k1_lds_pad_kb")
     saved = {k: _lib.get_tuning(k) for k in keys}
-    try:
+    with _lib.scoped_settings():
         for (B, N) in [(3, 16), (2, 48), (2, 208), (1, 256)]:
             xyz, mask = synth(300 + N, B, N)
             xyz[0, N // 3] = float("nan")
@@ -364,9 +350,6 @@ def test_k1_pattern_kernel_single_plane_launches(SB):
                     _, cm = ops.pairwise_distance(xg, am, row_begin=r0, row_end=r1, compact=True, want_dist=False)
                     assert torch.equal(cd.view(torch.int32), ref_d[:, r0:r1].contiguous().view(torch.int32))
                     assert torch.equal(cm, ref_m[:, r0:r1])
-    finally:
-        for k, v in saved.items():
-            _lib.set_tuning(k, v)
 
 
 @pytest.mark.parametrize("exact", [0, 1])
@@ -374,11 +357,8 @@ def test_k1_flat_kernel_bit_identical_to_slot_decode(SB, exact):
     """The flat pattern kernel (any N >= 16) against the slot-decode kernel: same bits, nothing written outside the
     requested rows, for full / compact / in-place row ranges, chunks that span rows and structures, NaN atoms."""
     from protstruc_amd import _lib, ops
-    keys = ("k1_variant", "k1_flat", "k1_flat_cpw", "k1_store_nt", "k1_exact_sqrt", "k1_flat_fl_log2")
-    saved = {k: _lib.get_tuning(k) for k in keys}
     SENT = 12345.0
-    try:
-        _lib.set_tuning("k1_exact_sqrt", exact)
+    with ops.exact_sqrt(exact):
         for (B, N) in [(1, 16), (3, 17), (2, 18), (5, 19), (2, 37), (3, 100), (2, 127), (2, 128), (1, 437), (2, 250)]:
             xyz, mask = synth(100 + N, B, N)
             xyz[0, N // 3] = float("nan")
@@ -426,9 +406,6 @@ def test_k1_flat_kernel_bit_identical_to_slot_decode(SB, exact):
                     assert torch.equal(fm[:, r0:r1].view(torch.bool), ref_m[:, r0:r1])
                     assert (fd[:, :r0] == SENT).all() and (fd[:, r1:] == SENT).all()
                     assert (fm[:, :r0] == 7).all() and (fm[:, r1:] == 7).all()
-    finally:
-        for k, v in saved.items():
-            _lib.set_tuning(k, v)
 
 
 def _same_floats(a, b):
@@ -444,9 +421,6 @@ def test_k1_any_atom_count_kernel_matches_element_kernel(SB, exact):
     against the element-per-lane kernel (k1_flat=0) for atom counts other than 15 -- and against the pattern kernels
     at A = 15 -- over full, compact and in-place row ranges, with sentinel guards around every output."""
     from protstruc_amd import _lib, ops
-    keys = ("k1_variant", "k1_flat", "k1_flat_cpw", "k1_store_nt", "k1_exact_sqrt", "k1_rowphase")
-    saved = {k: _lib.get_tuning(k) for k in keys}
-    _lib.set_tuning("k1_exact_sqrt", exact)
     SENT = 12345.0
     cases = [(2, 16, 1), (3, 17, 2), (2, 33, 3), (3, 50, 4), (2, 100, 5), (2, 37, 14), (2, 64, 16), (2, 21, 25),
              (1, 40, 37), (1, 19, 64), (2, 250, 4), (2, 37, 15), (1, 128, 15),
@@ -489,7 +463,7 @@ def test_k1_any_atom_count_kernel_matches_element_kernel(SB, exact):
             return [(4, 0), (1, 1)]
         return [(1, 0)]
 
-    try:
+    with ops.exact_sqrt(exact):
         for (B, N, A), (flat, rowphase) in [(c, f) for c in cases for f in paths(c[2])]:
             _lib.set_tuning("k1_rowphase", rowphase)
             xyz, mask = synth(300 + N + A, B, N, A=A)
@@ -532,9 +506,6 @@ def test_k1_any_atom_count_kernel_matches_element_kernel(SB, exact):
                     assert torch.equal(fm[:, r0:r1].view(torch.bool), ref_m[:, r0:r1])
                     assert (fd[:, :r0] == SENT).all() and (fd[:, r1:] == SENT).all()
                     assert (fm[:, :r0] == 7).all() and (fm[:, r1:] == 7).all()
-    finally:
-        for k, v in saved.items():
-            _lib.set_tuning(k, v)
 
 
 def test_k1_square_root_modes_vs_torch_norm(SB):
@@ -543,15 +514,12 @@ def test_k1_square_root_modes_vs_torch_norm(SB):
     root on the same squared length: never more than 1 ulp away from exact mode, identical on most entries.  Every kernel behind the entry point is covered
     (pattern, flat pattern, slot-decode, row-tile, row-phase incl. its run-time atom counts, fixed-A flat, element-per-lane)."""
     from protstruc_amd import _lib, ops
-    keys = ("k1_variant", "k1_flat", "k1_exact_sqrt")
-    saved = {k: _lib.get_tuning(k) for k in keys}
-
     from tests import ref_arith
 
     def numpy_formula(xyz):
         return torch.from_numpy(ref_arith.dist_ref(xyz.numpy()))
 
-    try:
+    with _lib.scoped_settings():
         for (B, N, A, variant, flat) in [(2, 64, 15, 0, 1), (2, 37, 15, 0, 1), (2, 37, 15, 1, 1), (2, 40, 5, 0, 1),
                                          (2, 40, 5, 0, 0), (1, 24, 37, 0, 1), (2, 33, 4, 0, 1), (2, 30, 14, 0, 1),
                                          (1, 20, 40, 0, 1)]:
@@ -568,9 +536,6 @@ def test_k1_square_root_modes_vs_torch_norm(SB):
             ulps = (df.cpu().view(torch.int32) - want.view(torch.int32)).abs()
             assert int(ulps.max()) <= 1, (B, N, A, variant, flat)
             assert float((ulps == 0).float().mean()) > 0.75
-    finally:
-        for k, v in saved.items():
-            _lib.set_tuning(k, v)
 
 
 def test_k1_misaligned_output_buffers(SB):
@@ -702,8 +667,6 @@ def test_k1_knobs_flipped_on_another_thread(SB):
     want_a = ops.pairwise_distance(xa, ma)
     want_b = ops.pairwise_distance(xb, mb)
     torch.cuda.synchronize()
-    keys = ("k1_rows_per_block", "k1_jt", "k1_flat_cpw", "k1_xcd_remap", "k1_store_nt", "k1_lds_pad_kb", "k1_flat")
-    saved = {k: _lib.get_tuning(k) for k in keys}
     stop = threading.Event()
     errors = []
 
@@ -733,16 +696,15 @@ def test_k1_knobs_flipped_on_another_thread(SB):
 
     threads = [threading.Thread(target=flipper), threading.Thread(target=launcher, args=(xa, ma, want_a)),
                threading.Thread(target=launcher, args=(xb, mb, want_b))]
-    try:
-        for t in threads:
-            t.start()
-        for t in threads[1:]:
-            t.join()
-    finally:
-        stop.set()
-        threads[0].join()
-        for k, v in saved.items():
-            _lib.set_tuning(k, v)
+    with _lib.scoped_settings():
+        try:
+            for t in threads:
+                t.start()
+            for t in threads[1:]:
+                t.join()
+        finally:
+            stop.set()
+            threads[0].join()
     assert not errors, errors
     # another device's entry was never touched by any of this
     assert _lib.get_tuning("k1_rows_per_block", device=7) == 1
@@ -821,53 +783,51 @@ def test_k1_autotune_is_explicit_and_transparent(SB):
     xg, mg = xyz.cuda(), mask.cuda()
     saved_tuned = ops._K1_TUNED.pop(xg.device, None)
     rows0, pad0 = _lib.get_tuning("k1_rows_per_block"), _lib.get_tuning("k1_lds_pad_kb")
-    try:
-        assert (rows0, pad0) == (1, -1) or saved_tuned is not None     # the measured-best default (idle LDS by chain length)
-        d0, m0 = ops.pairwise_distance(xg, mg)
-        assert ops.k1_autotune_result(xg.device) is None, "an ordinary call must not tune"
-        out_d, out_m = torch.empty_like(d0), torch.empty_like(m0)
-        res = ops.autotune_pairwise_distance(xg, mg, out_d, out_m)
-        assert res is not None and res["rows_per_block"] in (1, 2)
-        # every candidate but the one that merely NAMES the default launch at this length (36 KB of idle LDS + 32-residue tiles from
-        # N = 256: timing it against candidate 0 was noise, and a "pick" of it made bench.py re-time the default for nothing)
-        alias = {"rows_per_block": 1, "lds_pad_kb": 36, "jt": 32}
-        assert set(res["ms"]) == {ops._cand_label(c) for c in ops._K1_CANDIDATE_PATTERN if c != alias} and len(res["ms"]) == 7
-        assert _lib.get_tuning("k1_rows_per_block") == res["rows_per_block"]
-        assert _lib.get_tuning("k1_lds_pad_kb") == res["lds_pad_kb"] and _lib.get_tuning("k1_jt") == res["jt"]
-        assert torch.equal(out_d, d0) and torch.equal(out_m, m0)
-        d1, m1 = ops.pairwise_distance(xg, mg)
-        assert torch.equal(d0, d1) and torch.equal(m0, m1)
-        # opt-in through the environment; a captured call never tunes and still works
-        ops._K1_TUNED.pop(xg.device, None)
-        ops.set_implicit_autotune(True)     # what PROTSTRUC_AMD_AUTOTUNE=1 at import time selects
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            d2, m2 = ops.pairwise_distance(xg, mg)
-        g.replay(); torch.cuda.synchronize()
-        assert ops.k1_autotune_result(xg.device) is None and torch.equal(d2, d0)
-        ops.pairwise_distance(xg, mg)
-        assert ops.k1_autotune_result(xg.device) is not None
-        # the flat kernel's chunks per workgroup (lengths that are not a multiple of 16) tune the same way
-        xyz2, mask2 = synth(13, 23, 437)   # 4.39 M pairs
-        x2, m2g = xyz2.cuda(), mask2.cuda()
-        ops.set_implicit_autotune(False)
-        e0, f0 = ops.pairwise_distance(x2, m2g)
-        assert "flat_cpw" not in ops.k1_autotune_result(xg.device)
-        e1, f1 = torch.empty_like(e0), torch.empty_like(f0)
-        res2 = ops.autotune_pairwise_distance(x2, m2g, e1, f1)
-        assert res2["flat_cpw"] in (1, 2, 4) and _lib.get_tuning("k1_flat_cpw") == res2["flat_cpw"]
-        assert _lib.get_tuning("k1_flat_lds_pad_kb") == res2["flat_lds_pad_kb"]
-        assert res2["flat_fl_log2"] in (0, 5, 7) and _lib.get_tuning("k1_flat_fl_log2") == res2["flat_fl_log2"]
-        assert len(res2["flat_ms"]) == len(ops._K1_CANDIDATE_FLAT)
-        assert torch.equal(e0, e1) and torch.equal(f0, f1)
-    finally:
-        ops.set_implicit_autotune(False)
-        for k, v in (("k1_rows_per_block", rows0), ("k1_lds_pad_kb", pad0), ("k1_jt", 0), ("k1_flat_cpw", 1),
-                     ("k1_flat_lds_pad_kb", 0), ("k1_flat_fl_log2", 0)):
-            _lib.set_tuning(k, v)
-        ops._K1_TUNED.pop(xg.device, None)
-        if saved_tuned is not None:
-            ops._K1_TUNED[xg.device] = saved_tuned
+    with _lib.scoped_settings():
+        try:
+            assert (rows0, pad0) == (1, -1) or saved_tuned is not None     # the measured-best default (idle LDS by chain length)
+            d0, m0 = ops.pairwise_distance(xg, mg)
+            assert ops.k1_autotune_result(xg.device) is None, "an ordinary call must not tune"
+            out_d, out_m = torch.empty_like(d0), torch.empty_like(m0)
+            res = ops.autotune_pairwise_distance(xg, mg, out_d, out_m)
+            assert res is not None and res["rows_per_block"] in (1, 2)
+            # every candidate but the one that merely NAMES the default launch at this length (36 KB of idle LDS + 32-residue tiles from
+            # N = 256: timing it against candidate 0 was noise, and a "pick" of it made bench.py re-time the default for nothing)
+            alias = {"rows_per_block": 1, "lds_pad_kb": 36, "jt": 32}
+            assert set(res["ms"]) == {ops._cand_label(c) for c in ops._K1_CANDIDATE_PATTERN if c != alias} and len(res["ms"]) == 7
+            assert _lib.get_tuning("k1_rows_per_block") == res["rows_per_block"]
+            assert _lib.get_tuning("k1_lds_pad_kb") == res["lds_pad_kb"] and _lib.get_tuning("k1_jt") == res["jt"]
+            assert torch.equal(out_d, d0) and torch.equal(out_m, m0)
+            d1, m1 = ops.pairwise_distance(xg, mg)
+            assert torch.equal(d0, d1) and torch.equal(m0, m1)
+            # opt-in through the environment; a captured call never tunes and still works
+            ops._K1_TUNED.pop(xg.device, None)
+            ops.set_implicit_autotune(True)     # what PROTSTRUC_AMD_AUTOTUNE=1 at import time selects
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                d2, m2 = ops.pairwise_distance(xg, mg)
+            g.replay(); torch.cuda.synchronize()
+            assert ops.k1_autotune_result(xg.device) is None and torch.equal(d2, d0)
+            ops.pairwise_distance(xg, mg)
+            assert ops.k1_autotune_result(xg.device) is not None
+            # the flat kernel's chunks per workgroup (lengths that are not a multiple of 16) tune the same way
+            xyz2, mask2 = synth(13, 23, 437)   # 4.39 M pairs
+            x2, m2g = xyz2.cuda(), mask2.cuda()
+            ops.set_implicit_autotune(False)
+            e0, f0 = ops.pairwise_distance(x2, m2g)
+            assert "flat_cpw" not in ops.k1_autotune_result(xg.device)
+            e1, f1 = torch.empty_like(e0), torch.empty_like(f0)
+            res2 = ops.autotune_pairwise_distance(x2, m2g, e1, f1)
+            assert res2["flat_cpw"] in (1, 2, 4) and _lib.get_tuning("k1_flat_cpw") == res2["flat_cpw"]
+            assert _lib.get_tuning("k1_flat_lds_pad_kb") == res2["flat_lds_pad_kb"]
+            assert res2["flat_fl_log2"] in (0, 5, 7) and _lib.get_tuning("k1_flat_fl_log2") == res2["flat_fl_log2"]
+            assert len(res2["flat_ms"]) == len(ops._K1_CANDIDATE_FLAT)
+            assert torch.equal(e0, e1) and torch.equal(f0, f1)
+        finally:
+            ops.set_implicit_autotune(False)
+            ops._K1_TUNED.pop(xg.device, None)
+            if saved_tuned is not None:
+                ops._K1_TUNED[xg.device] = saved_tuned
 
 
 def test_k1_headline_shape_properties(SB):
@@ -1044,8 +1004,7 @@ def test_k3_golden_faithful_mode(SB):
     g = load_golden("g3_pairwise_angles")
     sb = SB.from_xyz(g["xyz"], g["atom_mask"])
     checked = 0
-    try:
-        ops.set_exact_angles(True)
+    with ops.exact_angles():
         for key, want in g.items():
             if key[:4] not in ("dih_", "ang_"):
                 continue
@@ -1067,8 +1026,6 @@ def test_k3_golden_faithful_mode(SB):
         diag = torch.diagonal(omega, dim1=1, dim2=2)
         assert (diag == 0).all() and not torch.signbit(diag).any(), "diagonal must be exactly +0.0"
         assert torch.diagonal(sb.pairwise_planar_angles(["CA", "CB"], ["CB"]), dim1=1, dim2=2).isnan().all()
-    finally:
-        ops.set_exact_angles(False)
 
 
 @pytest.mark.parametrize("ai,aj,npts", [
@@ -1153,8 +1110,7 @@ def test_k3_config3_shape_faithful_mode(SB):
     sb = SB.from_xyz(xyz, mask)
     pick = [0, 37, 64, 127]
     same = lambda a, b: torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(5.0), b.nan_to_num(5.0))
-    try:
-        ops.set_exact_angles(True)
+    with ops.exact_angles():
         outs = {}
         for (key, ai, aj, si, sj, npts) in [("omega", ["CA", "CB"], ["CA", "CB"], [1, 4], [1, 4], 4), ("theta", ["N", "CA", "CB"], ["CB"], [0, 1, 4], [4], 4),
                                             ("phi", ["CA", "CB"], ["CB"], [1, 4], [4], 3)]:
@@ -1180,8 +1136,6 @@ def test_k3_config3_shape_faithful_mode(SB):
         geo = sb.inter_residue_geometry()
         for key in ("omega", "theta", "phi"):
             assert same(geo[key], outs[key]), key
-    finally:
-        ops.set_exact_angles(False)
 
 
 def test_config5_shape_diffusion_loop(SB):
@@ -1365,8 +1319,7 @@ def test_k3_sweep_kernels_bit_identical_to_the_one_column_kernel(SB, N, faithful
     same = lambda a, b: torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(5.0), b.nan_to_num(5.0))
     splits = [(4, [1, 4], [1, 4]), (4, [0, 1, 4], [4]), (4, [2], [0, 1, 2]), (4, [1], [4, 1, 0]), (4, [0, 1], [2, 3]),
               (4, [0, 1, 2, 3], []), (4, [], [0, 1, 2, 3]), (3, [1, 4], [4]), (3, [1], [1, 4]), (3, [], [0, 1, 2]), (3, [4, 1, 0], [])]
-    try:
-        ops.set_exact_angles(faithful)
+    with ops.exact_angles(faithful):
         for npts, si, sj in splits:
             one = ops.pairwise_angles(xg, si, sj, npts, _one_column=True)
             big = torch.full((B * N * N + 1,), 7.0, device="cuda")
@@ -1378,8 +1331,6 @@ def test_k3_sweep_kernels_bit_identical_to_the_one_column_kernel(SB, N, faithful
                 r0, r1 = 3, N - 2                                                      # odd number of rows, odd first row
                 c = ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, compact=True)
                 assert same(c, one[:, r0:r1]), (npts, si, sj)
-    finally:
-        ops.set_exact_angles(False)
 
 
 def test_k3_exact_angles_mode(SB):
@@ -1402,8 +1353,7 @@ def test_k3_exact_angles_mode(SB):
     for key, (ai, aj) in {"omega": (["CA", "CB"], ["CA", "CB"]), "theta": (["N", "CA", "CB"], ["CB"])}.items():
         fast[key] = sb.pairwise_dihedrals(ai, aj)
     fast["phi"] = sb.pairwise_planar_angles(["CA", "CB"], ["CB"])
-    try:
-        ops.set_exact_angles(True)
+    with ops.exact_angles():
         assert ops.get_exact_angles() is True
         ex = {}
         for key, (ai, aj, si, sj) in {"omega": (["CA", "CB"], ["CA", "CB"], [1, 4], [1, 4]),
@@ -1431,8 +1381,6 @@ def test_k3_exact_angles_mode(SB):
         part = ops.pairwise_angles(x5, [1, 4], [1, 4], 4, row_begin=5, row_end=20, compact=True)
         assert same(part, full[:, 5:20])
         assert wrap(full.cpu() - O.pairwise_dihedrals(xyz[:2, :37], [1, 4], [1, 4]))[~torch.eye(37, dtype=torch.bool).expand(2, 37, 37)].max() <= 1e-6
-    finally:
-        ops.set_exact_angles(False)
     assert same(sb.pairwise_dihedrals(["CA", "CB"], ["CA", "CB"]), fast["omega"])
     geo = sb.inter_residue_geometry()
     assert same(geo["omega"], fast["omega"]) and same(geo["phi"], fast["phi"])
@@ -1475,15 +1423,12 @@ def test_k3_planar_angle_collinear_and_extreme_arms(SB):
         assert abs(f[3].item() - np.pi / 2) <= 1e-6
         assert f[1].isnan() or abs(f[1].item() - np.pi) <= 5e-4
         assert f[2].isnan() or abs(f[2].item()) <= 5e-4
-    try:
-        ops.set_exact_angles(True)
+    with ops.exact_angles():
         for x in (xyz, big, tiny):
             got = SB.from_xyz(x).pairwise_planar_angles(["CA", "CB"], ["CB"])[0, 0].cpu()
             want = O.pairwise_planar_angles(x, [1, 4], [4])[0, 0]
             assert torch.equal(got.isnan(), want.isnan())
             assert (got - want).nan_to_num(0).abs().max().item() <= 1e-6
-    finally:
-        ops.set_exact_angles(False)
 
 
 @pytest.mark.parametrize("N", [2048, 4608])
@@ -1533,23 +1478,22 @@ def test_k3_differential_fuzz(SB):
         if trial % 7 == 0 and N > 2:
             xyz[-1, 1] = xyz[-1, 0]
         xg = xyz.cuda()
-        ops.set_exact_angles(trial % 3 == 2)        # every third trial in the reference's order of operations
-        one = ops.pairwise_angles(xg, si, sj, npts, _one_column=True)
-        if trial % 4 == 1:          # the misaligned-output path as well
-            big = torch.full((B * N * N + 1,), 7.0, device="cuda")
-            assert same(ops.pairwise_angles(xg, si, sj, npts, out=big[1:].view(B, N, N)), one) and big[0] == 7.0
-        r0 = int(rng.integers(0, N)); r1 = int(rng.integers(r0, N + 1))
-        if trial % 3 == 0:
-            r0, r1 = 0, N
-        if trial % 2 == 0:
-            got = ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, compact=True)
-            assert same(got, one[:, r0:r1]), (trial, B, N, A, npts, si, sj, r0, r1)
-        else:
-            buf = torch.full((B, N, N), 321.0, device="cuda")
-            ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, out=buf)
-            assert same(buf[:, r0:r1], one[:, r0:r1]), (trial, B, N, A, npts, si, sj, r0, r1)
-            assert (buf[:, :r0] == 321.0).all() and (buf[:, r1:] == 321.0).all()
-    ops.set_exact_angles(False)
+        with ops.exact_angles(trial % 3 == 2):        # every third trial in the reference's order of operations
+            one = ops.pairwise_angles(xg, si, sj, npts, _one_column=True)
+            if trial % 4 == 1:          # the misaligned-output path as well
+                big = torch.full((B * N * N + 1,), 7.0, device="cuda")
+                assert same(ops.pairwise_angles(xg, si, sj, npts, out=big[1:].view(B, N, N)), one) and big[0] == 7.0
+            r0 = int(rng.integers(0, N)); r1 = int(rng.integers(r0, N + 1))
+            if trial % 3 == 0:
+                r0, r1 = 0, N
+            if trial % 2 == 0:
+                got = ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, compact=True)
+                assert same(got, one[:, r0:r1]), (trial, B, N, A, npts, si, sj, r0, r1)
+            else:
+                buf = torch.full((B, N, N), 321.0, device="cuda")
+                ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, out=buf)
+                assert same(buf[:, r0:r1], one[:, r0:r1]), (trial, B, N, A, npts, si, sj, r0, r1)
+                assert (buf[:, :r0] == 321.0).all() and (buf[:, r1:] == 321.0).all()
 
 
 @pytest.mark.parametrize("N", [1, 2, 3, 5, 8, 15, 16, 17, 31, 32, 33, 48, 63, 64])
@@ -1568,8 +1512,7 @@ def test_k3_short_chain_kernel_bit_identical_to_the_one_column_kernel(SB, N):
             xyz[B - 1, 1] = xyz[B - 1, 0]
         xg = xyz.cuda()
         for faithful in (False, True):               # the fast arithmetic, and the reference's order of operations
-            try:
-                ops.set_exact_angles(faithful)
+            with ops.exact_angles(faithful):
                 for npts, si, sj in splits:
                     one = ops.pairwise_angles(xg, si, sj, npts, _one_column=True)
                     assert same(ops.pairwise_angles(xg, si, sj, npts), one), (N, B, npts, si, sj, faithful)
@@ -1578,8 +1521,6 @@ def test_k3_short_chain_kernel_bit_identical_to_the_one_column_kernel(SB, N):
                     buf = torch.full((B, N, N), 321.0, device="cuda")
                     ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, out=buf)
                     assert same(buf[:, r0:r1], one[:, r0:r1]) and (buf[:, :r0] == 321.0).all() and (buf[:, r1:] == 321.0).all()
-            finally:
-                ops.set_exact_angles(False)
 
 
 def _angle_gates(got, ref, npts, faithful, where):
@@ -1633,11 +1574,8 @@ def test_k3_every_dispatch_arm_vs_oracle(SB, entry):
     plan = _lib.k3_plan(B, N, 15, si, sj, npts, r0, r1, compact=compact, out_misalign=mis, exact_angles=mode, cu_count=cus)
     if cus == 256:
         assert arm_key(plan, K3_ARM_KEYS) == tuple(want[k] for k in K3_ARM_KEYS), plan
-    try:
-        ops.set_exact_angles(bool(mode & 1))
+    with ops.exact_angles(bool(mode & 1)):
         got = ops.pairwise_angles(xg, si, sj, npts, row_begin=r0, row_end=r1, compact=compact, out=out, _one_column=bool(mode & 2))
-    finally:
-        ops.set_exact_angles(False)
     torch.cuda.synchronize()
     assert got is out
     assert (big[:base] == 777.0).all() and (big[base + B * out_rows * N:] == 777.0).all(), "a sentinel around the output changed"
@@ -2074,13 +2012,8 @@ def test_inter_residue_geometry_golden_exact_modes(SB):
     positions, the masks are exact."""
     from protstruc_amd import ops
     g = load_golden("g8_inter_residue_geometry")
-    try:
-        ops.set_exact_sqrt(True)
-        ops.set_exact_angles(True)
+    with ops.exact_sqrt(), ops.exact_angles():
         geo = SB.from_xyz(g["xyz"], g["atom_mask"]).inter_residue_geometry()
-    finally:
-        ops.set_exact_sqrt(False)
-        ops.set_exact_angles(False)
     for k in ("d_ca", "d_cb", "d_no"):
         assert_bits(geo[k], g[k], k)
         assert torch.equal(geo[k + "_mask"].cpu(), g[k + "_mask"]), k
@@ -2102,16 +2035,13 @@ def test_inter_residue_geometry_matches_unfused_kernels(SB, N):
     sb = SB.from_xyz(xyz, mask)
     was = ops.get_exact_sqrt()
     geos = {}
-    try:
-        for exact in (False, True):
-            ops.set_exact_sqrt(exact)
+    for exact in (False, True):
+        with ops.exact_sqrt(exact):
             geos[exact] = sb.inter_residue_geometry()
             d, m = sb.pairwise_distance_matrix()
             for key, (a, c) in {"d_ca": (1, 1), "d_cb": (4, 4), "d_no": (0, 3)}.items():
                 assert torch.equal(geos[exact][key], d[:, :, :, a, c]), (key, exact)
                 assert torch.equal(geos[exact][key + "_mask"], m[:, :, :, a, c]), (key, exact)
-    finally:
-        ops.set_exact_sqrt(was)
     for key in ("d_ca", "d_cb", "d_no"):
         ulps = (geos[True][key].view(torch.int32) - geos[False][key].view(torch.int32)).abs()
         assert int(ulps.max()) <= 1

@@ -93,3 +93,86 @@ def test_no_cpu_fallback(call):
     sb, _, _ = make()
     with pytest.raises(RuntimeError, match="HIP-only"):
         call(sb)
+
+
+# ---- per-device launch settings: one record per device, scoped overrides (host side only: no GPU needed) ----------------
+def test_scoped_settings_restore_on_exit_and_after_an_exception():
+    from protstruc_amd import _lib
+    before = _lib.all_tuning(0)
+    with _lib.scoped_settings(0, k1_jt=16, exact_angles=True):
+        assert _lib.get_tuning("k1_jt", 0) == 16 and _lib.get_exact_angles(0) == 1
+    assert _lib.all_tuning(0) == before and _lib.get_exact_angles(0) == 0
+    with pytest.raises(ZeroDivisionError):
+        with _lib.scoped_settings(0, k1_rows_per_block=8):
+            assert _lib.k1_config(0).rows_per_block == 8
+            1 / 0
+    assert _lib.all_tuning(0) == before
+
+
+def test_scoped_settings_nest_and_undo_an_inner_set_tuning():
+    from protstruc_amd import _lib, ops
+    before = _lib.all_tuning(0)
+    with ops.k1_tuning(0, jt=32):
+        with ops.k1_tuning(0, jt=64, flat_cpw=2):
+            _lib.set_tuning("k1_store_nt", 1, 0)
+            _lib.set_exact_angles(True, 0)
+            assert (_lib.get_tuning("k1_jt", 0), _lib.get_tuning("k1_flat_cpw", 0), _lib.get_tuning("k1_store_nt", 0)) == (64, 2, 1)
+        assert _lib.get_tuning("k1_jt", 0) == 32 and _lib.get_tuning("k1_flat_cpw", 0) == before["k1_flat_cpw"]
+        assert _lib.get_tuning("k1_store_nt", 0) == before["k1_store_nt"] and _lib.get_exact_angles(0) == 0
+    assert _lib.all_tuning(0) == before
+
+
+def test_scoped_settings_leave_other_devices_alone():
+    from protstruc_amd import _lib
+    _lib.all_tuning(1)                                 # device 1's record exists before the scope
+    ref1, cfg1 = _lib.k1_config_ref(1), _lib.k1_config(1)
+    with _lib.scoped_settings(0, k1_rows_per_block=4, exact_angles=True):
+        assert _lib.get_tuning("k1_rows_per_block", 1) == 1 and _lib.get_exact_angles(1) == 0
+        assert _lib.k1_config_ref(1) is ref1 and _lib.k1_config(1) is cfg1
+    assert _lib.k1_config_ref(1) is ref1
+
+
+def test_scoped_settings_refuse_an_invalid_value_and_change_nothing():
+    from protstruc_amd import _lib, ops
+    before, ref = _lib.all_tuning(0), _lib.k1_config_ref(0)
+    for bad in ({"k1_jt": 96}, {"k1_rows_per_block": 33}, {"no_such_knob": 1}, {"k1_flat_cpw": 2, "k1_flat": 3}):
+        with pytest.raises(_lib.HipLibraryError):
+            with _lib.scoped_settings(0, **bad):
+                raise AssertionError("the block must not run")
+    with pytest.raises(_lib.HipLibraryError):
+        with ops.k1_tuning(0, jt=96):
+            raise AssertionError("the block must not run")
+    assert _lib.all_tuning(0) == before and _lib.k1_config_ref(0) is ref
+
+
+def test_k1_config_ref_is_cached_until_a_change():
+    from protstruc_amd import _lib
+    ref, cfg = _lib.k1_config_ref(0), _lib.k1_config(0)
+    assert _lib.k1_config_ref(0) is ref and _lib.k1_config(0) is cfg
+    assert _lib.k1_config(0, jt=16) is not cfg and _lib.k1_config(0, jt=16).jt == 16 and cfg.jt != 16
+    with _lib.scoped_settings(0, k1_jt=16):
+        assert _lib.k1_config_ref(0) is not ref and _lib.k1_config(0).jt == 16
+        inner = _lib.k1_config_ref(0)
+        _lib.set_exact_angles(True, 0)                 # any change installs a new record
+        assert _lib.k1_config_ref(0) is not inner
+    assert _lib.k1_config_ref(0) is ref and _lib.k1_config(0) is cfg
+
+
+@pytest.mark.parametrize("var,scope,getter", [("PROTSTRUC_AMD_EXACT_ANGLES", "exact_angles", "get_exact_angles"),
+                                              ("PROTSTRUC_AMD_EXACT_SQRT", "exact_sqrt", "get_exact_sqrt")])
+def test_leaving_a_scope_gives_back_the_mode_the_environment_selected(var, scope, getter):
+    """With the mode switched on through the environment, a ``with ops.exact_...(False)`` block ends in that mode again
+    (a fresh child process: the variable is read when a device's record is first built)."""
+    import os
+    import subprocess
+    import sys
+    code = ("from protstruc_amd import ops\n"
+            f"assert ops.{getter}(0) is True\n"
+            f"with ops.{scope}(False, 0):\n"
+            f"    assert ops.{getter}(0) is False\n"
+            f"assert ops.{getter}(0) is True\n"
+            "print('restored')\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, **{var: "1", "PYTHONPATH": root + os.pathsep + os.environ.get("PYTHONPATH", "")})
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "restored" in out.stdout, out.stderr

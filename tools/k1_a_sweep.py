@@ -33,30 +33,29 @@ for A, N in shapes:
                 "element": (0, True, True, 0), "default_dist_only": (1, True, False, 0),
                 "default_mask_only": (1, False, True, 0), "fill": None}
     best = {k: float("inf") for k in variants}
-    for rnd in range(3):
-        for name, var in variants.items():
-            if name == "element" and rnd > 0: continue    # slow; once is enough
-            if var is None:
-                run = lambda: (d.fill_(0.0), m.fill_(False))
-            else:
-                flat, wd, wm, rowphase = var
-                _lib.set_tuning("k1_flat", flat)
-                _lib.set_tuning("k1_rowphase", rowphase)
-                run = lambda: ops.pairwise_distance(xyz, mask, out_dist=d if wd else None, out_mask=m if wm else None,
-                                                    want_dist=wd, want_mask=wm)
-            try:
-                for _ in range(4): run()      # (the variant that follows `fill` reads ~3 % low with only two warm-up launches)
-            except Exception as exc:          # e.g. B > 65535 for the simple kernels (structure on grid.z)
-                if rnd == 0: print(f"   [{name}: {type(exc).__name__}: {exc}]", flush=True)
-                continue
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(5): run()
-            e1.record(); torch.cuda.synchronize()
-            best[name] = min(best[name], e0.elapsed_time(e1) / 5)
-    _lib.set_tuning("k1_flat", 1)
-    _lib.set_tuning("k1_rowphase", 0)
+    with ops.k1_tuning():      # the variants below step k1_flat / k1_rowphase
+        for rnd in range(3):
+            for name, var in variants.items():
+                if name == "element" and rnd > 0: continue    # slow; once is enough
+                if var is None:
+                    run = lambda: (d.fill_(0.0), m.fill_(False))
+                else:
+                    flat, wd, wm, rowphase = var
+                    _lib.set_tuning("k1_flat", flat)
+                    _lib.set_tuning("k1_rowphase", rowphase)
+                    run = lambda: ops.pairwise_distance(xyz, mask, out_dist=d if wd else None, out_mask=m if wm else None,
+                                                        want_dist=wd, want_mask=wm)
+                try:
+                    for _ in range(4): run()      # (the variant that follows `fill` reads ~3 % low with only two warm-up launches)
+                except Exception as exc:          # e.g. B > 65535 for the simple kernels (structure on grid.z)
+                    if rnd == 0: print(f"   [{name}: {type(exc).__name__}: {exc}]", flush=True)
+                    continue
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(5): run()
+                e1.record(); torch.cuda.synchronize()
+                best[name] = min(best[name], e0.elapsed_time(e1) / 5)
     nbytes = {"default": 5, "rowphase": 5, "element": 5, "default_dist_only": 4, "default_mask_only": 1, "fill": 5}
     row = {"A": A, "N": N, "B": B, "kernel": _lib.k1_plan(B, N, A)["kernel"], **{k: {"ms": round(v, 4), "TBps": round(B * N * N * A * A * nbytes[k] / v / 1e9, 3)}
                                      for k, v in best.items()}}

@@ -28,21 +28,21 @@ for A, N in shapes:
     m = torch.empty(B, N, N, A, A, dtype=torch.bool, device="cuda")
     best = {r: float("inf") for r in ROWS}
     best["fill"] = float("inf")
-    for rnd in range(3):
-        for r in list(ROWS) + ["fill"]:
-            if r == "fill":
-                run = lambda: (d.fill_(0.0), m.fill_(False))
-            else:
-                _lib.set_tuning("k1_rows_per_block", r if r else 1)
-                run = lambda: ops.pairwise_distance(xyz, mask, out_dist=d, out_mask=m)
-            run(); run()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(4):
-                run()
-            e1.record(); torch.cuda.synchronize()
-            best[r] = min(best[r], e0.elapsed_time(e1) / 4)
-    _lib.set_tuning("k1_rows_per_block", 1)
+    with ops.k1_tuning():
+        for rnd in range(3):
+            for r in list(ROWS) + ["fill"]:
+                if r == "fill":
+                    run = lambda: (d.fill_(0.0), m.fill_(False))
+                else:
+                    _lib.set_tuning("k1_rows_per_block", r if r else 1)
+                    run = lambda: ops.pairwise_distance(xyz, mask, out_dist=d, out_mask=m)
+                run(); run()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(4):
+                    run()
+                e1.record(); torch.cuda.synchronize()
+                best[r] = min(best[r], e0.elapsed_time(e1) / 4)
     nb = B * N * N * A * A * 5
     print(f"A={A:3d} N={N:4d} B={B:5d}  " + "  ".join(f"{nb / best[r] / 1e9:5.2f}" for r in ROWS) + f"  {nb / best['fill'] / 1e9:5.2f}"
           + f"   [{_lib.k1_plan(B, N, A)['kernel']}]", flush=True)

@@ -20,11 +20,8 @@ ab_flags = [1]   # row-phase A/B switches (cfg.rowphase bits 4..): 1 = seams wri
 
 
 def with_flags(fl, run):
-    _lib.set_tuning("k1_rowphase", 16 * fl)
-    try:
+    with ops.k1_tuning(rowphase=16 * fl):
         run()
-    finally:
-        _lib.set_tuning("k1_rowphase", 0)
 
 
 def timed(run):

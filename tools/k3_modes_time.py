@@ -42,12 +42,11 @@ feats = {"dihedral (2,2) CA,CB|CA,CB": (4, [1, 4], [1, 4]), "dihedral (3,1) N,CA
 out = torch.empty(B, N, N, device="cuda")
 print(f"B={B} N={N}  us per launch: median / min of single launches, mean of a {reps}-launch train   (PS_K3_NC={os.environ.get('PS_K3_NC', '-')})")
 for mode in (0, 1):
-    ops.set_exact_angles(bool(mode))
-    for name, (npts, si, sj) in feats.items():
-        med, mn, train = timed(lambda: ops.pairwise_angles(xyz, si, sj, npts, out=out))
-        k = _lib.k3_plan(B, N, 15, si, sj, npts, exact_angles=mode, cu_count=cus)["kernel"]
-        print(f"mode {mode} {name:28s} {med:6.1f} / {mn:6.1f} / {train:6.1f}   {k}", flush=True)
-    med, mn, train = timed(lambda: sb.inter_residue_geometry())
-    k = _lib.featuriser_plan(B, N, 15, exact_angles=mode, cu_count=cus)["kernel"]
-    print(f"mode {mode} {'inter_residue_geometry':28s} {med:6.1f} / {mn:6.1f} / {train:6.1f}   {k}", flush=True)
-ops.set_exact_angles(False)
+    with ops.exact_angles(bool(mode)):
+        for name, (npts, si, sj) in feats.items():
+            med, mn, train = timed(lambda: ops.pairwise_angles(xyz, si, sj, npts, out=out))
+            k = _lib.k3_plan(B, N, 15, si, sj, npts, exact_angles=mode, cu_count=cus)["kernel"]
+            print(f"mode {mode} {name:28s} {med:6.1f} / {mn:6.1f} / {train:6.1f}   {k}", flush=True)
+        med, mn, train = timed(lambda: sb.inter_residue_geometry())
+        k = _lib.featuriser_plan(B, N, 15, exact_angles=mode, cu_count=cus)["kernel"]
+        print(f"mode {mode} {'inter_residue_geometry':28s} {med:6.1f} / {mn:6.1f} / {train:6.1f}   {k}", flush=True)

@@ -53,12 +53,11 @@ if what in ("k3", "k3p"):
     xyz, mask = synth(128, 512)
     sb = StructureBatch.from_xyz(xyz, mask)
     for faithful in (False, True):      # the fast arithmetic, then the reference's order of operations (kernel names differ: FAITHFUL)
-        ops.set_exact_angles(faithful)
-        repeat(lambda: sb.pairwise_dihedrals(["CA", "CB"], ["CA", "CB"]))
-        repeat(lambda: sb.pairwise_dihedrals(["N", "CA", "CB"], ["CB"]))
-        repeat(lambda: sb.pairwise_planar_angles(["CA", "CB"], ["CB"]))
-        repeat(lambda: sb.inter_residue_geometry())
-    ops.set_exact_angles(False)
+        with ops.exact_angles(faithful):
+            repeat(lambda: sb.pairwise_dihedrals(["CA", "CB"], ["CA", "CB"]))
+            repeat(lambda: sb.pairwise_dihedrals(["N", "CA", "CB"], ["CB"]))
+            repeat(lambda: sb.pairwise_planar_angles(["CA", "CB"], ["CB"]))
+            repeat(lambda: sb.inter_residue_geometry())
 elif what == "k3flat":      # the tile K3 kernel at 2^25 pairs: N = 64 (four-column tiles), 99 and 48 (two-column tiles), N = 512 (the sweep) beside it
     for n in (64, 99, 48, 512):
         b = (1 << 25) // (n * n)
@@ -95,9 +94,8 @@ elif what == "k1a":
         d = torch.empty(B, N, N, A, A, device="cuda")
         m = torch.empty(B, N, N, A, A, dtype=torch.bool, device="cuda")
         for rp in (0, 1):
-            _lib.set_tuning("k1_rowphase", rp)
-            repeat(lambda: ops.pairwise_distance(xyz, mask, out_dist=d, out_mask=m))
-        _lib.set_tuning("k1_rowphase", 0)
+            with ops.k1_tuning(rowphase=rp):
+                repeat(lambda: ops.pairwise_distance(xyz, mask, out_dist=d, out_mask=m))
         del xyz, mask, d, m
 elif what == "k1s":
     for A, N in ((5, 512), (5, 500), (5, 501), (3, 501), (1, 512), (2, 512)):

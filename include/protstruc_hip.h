@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 10
+#define PS_ABI_VERSION 11
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -267,6 +267,20 @@ int ps_frames_f32(const float* xyz, float* rot, float* trans,
                   void* stream);
 
 /*
+ * Backward pass of ps_frames_f32 (ABI 11): the vector-Jacobian product of the Gram-Schmidt frame (v1 = a3 - a2,
+ * e1 = v1 / |v1|, u2 = (a1 - a2) - (e1 . (a1 - a2)) e1, e2 = u2 / |u2|, e3 = e1 x e2) and of the translation pick, per
+ * residue:  grad_xyz[b][i][s][:] = sum over the entries of rot[b][i] and trans[b][i] of their upstream gradient times
+ * their derivative with respect to xyz[b][i][s][:].  grad_rot (B,N,3,3) is an unconstrained 3x3 gradient (not assumed
+ * tangent to the rotations), grad_trans (B,N,3); either may be NULL (zero; its arithmetic is skipped), not both.
+ * Contributions are summed where slots coincide (t_atom == a2 is the normal case).  EVERY element of grad_xyz (B,N,A,3)
+ * is written: slots that are not read, and every slot of a residue whose residue_mask byte is 0 (NULL = all present),
+ * receive exact zeros by selection -- NaN coordinates or NaN upstream values of a masked residue never reach the result.
+ */
+int ps_frames_backward_f32(const float* xyz, const float* grad_rot, const float* grad_trans,
+                           const uint8_t* residue_mask, float* grad_xyz,
+                           int B, int N, int A, int a1, int a2, int a3, int t_atom, void* stream);
+
+/*
  * Point-wise geometry primitives -- replace the free functions geometry.angle,
  * geometry.dihedral and geometry.gram_schmidt (geometry.py:39-124, :413-439) on
  * (n,3) point arrays:  mode 0: out[n] = angle(a,b,c);  mode 1: out[n] =
@@ -391,6 +405,52 @@ int ps_inter_residue_geometry_backward_f32(const float* xyz, const uint8_t* atom
                                            const float* g_d_ca, const float* g_d_cb, const float* g_d_no,
                                            const float* g_omega, const float* g_theta, const float* g_phi,
                                            float* grad_xyz, int B, int N, int A, void* stream);
+
+/*
+ * K13 (ABI 11) -- frame-aligned point error (FAPE; AlphaFold 2 suppl. alg. 28), fused: no (B,N,M) pair tensor exists.
+ * For structure b with frames (R_i, t_i), i < N (rot (B,N,3,3) row-major with the basis vectors as columns, as
+ * ps_frames_f32 writes them; trans (B,N,3)), points x_j, j < M (pts (B,M,3)) and the same for the target (_t):
+ *   u_ij = R_i^T (x_j - t_i)    u'_ij = R'_i^T (x'_j - t'_i)    d_ij = sqrt(|u_ij - u'_ij|^2 + eps)
+ *   loss[b] = (1 / scale) * sum_ij f_i p_j min(d_ij, clamp[b]) / max(sum_ij f_i p_j, 1)
+ * f = frame_mask (B,N), p = point_mask (B,M), one byte each, NULL = all present; clamp (B,) fp32 on the device, +inf =
+ * unclamped; scale > 0, eps >= 0.  count[b] = sum_ij f_i p_j as fp32 (exact below 2^24 pairs).  A structure without a
+ * valid pair has loss 0.  Masked frames and points are dropped by selection: NaN there never reaches the result.  Points
+ * may be any (B,M,3) view of coordinates, e.g. all N*A atom slots with the atom mask as point_mask: masked points are
+ * compacted away while a tile is staged, at no cost to the pair loop.
+ * partials: caller-owned scratch of B * ceil(N / PS_FAPE_FRAME_TILE) doubles (one partial sum per workgroup; a second
+ * small launch adds them in index order).  The sums run over min(d_ij, clamp) - min(sqrt(eps), clamp), the excess over
+ * the value of a perfectly placed point, which is added back once at the end: a structure compared with itself gives
+ * sqrt(eps) / scale exactly.  No atomics, fixed summation order: bit-for-bit repeatable.  Any N and M.
+ * B <= 65535; N, M <= 2^30.
+ */
+#define PS_FAPE_FRAME_TILE 64
+int ps_fape_f32(const float* rot_p, const float* trans_p, const float* pts_p,
+                const float* rot_t, const float* trans_t, const float* pts_t,
+                const uint8_t* frame_mask, const uint8_t* point_mask, const float* clamp,
+                float scale, float eps, float* loss, float* count, double* partials,
+                int B, int N, int M, void* stream);
+
+/*
+ * K14 (ABI 11) -- backward pass of ps_fape_f32 with respect to the predicted side (the target is a constant), in one
+ * launch that recomputes every pair; nothing is saved from the forward.  With
+ *   w_ij = grad_loss[b] f_i p_j [d_ij < clamp[b]] / (scale * max(count[b], 1))   and   e_ij = (u_ij - u'_ij) / d_ij:
+ *   grad_pts[b][j]   =  sum_i w_ij R_i e_ij
+ *   grad_trans[b][i] = -R_i sum_j w_ij e_ij
+ *   grad_rot[b][i]   =  sum_j w_ij (x_j - t_i) e_ij^T        (unconstrained 3x3)
+ * Any of the three outputs may be NULL (not all): the frame-owned workgroups (grad_rot, grad_trans) or the point-owned
+ * ones (grad_pts) are then not launched.  Every element of a given output is written; masked frames and points, and
+ * every entry of a structure without a valid pair, receive exact zeros by selection (NaN coordinates, rotations or
+ * translations at a masked frame or point never reach an output).  Owner-computes on both sides: no atomics, fixed
+ * summation order, bit-for-bit repeatable.  Limits as ps_fape_f32.  With eps = 0 a valid pair with u_ij == u'_ij has
+ * d_ij = 0 and no derivative (0 * inf): its owners' rows come out NaN, as under autograd; use eps > 0 where prediction
+ * and target can coincide.
+ */
+int ps_fape_backward_f32(const float* rot_p, const float* trans_p, const float* pts_p,
+                         const float* rot_t, const float* trans_t, const float* pts_t,
+                         const uint8_t* frame_mask, const uint8_t* point_mask, const float* clamp,
+                         float scale, float eps, const float* grad_loss,
+                         float* grad_rot, float* grad_trans, float* grad_pts,
+                         int B, int N, int M, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

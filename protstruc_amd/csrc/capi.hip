@@ -15,6 +15,8 @@
 // 8: ps_smacof_f32 / ps_smacof_workspace_bytes (K10), ps_mds_backbone_finish_f32 (K11).
 // 9: ps_inter_residue_geometry_backward_f32 (the featuriser's vector-Jacobian product).
 // 10: ps_backbone_from_dihedrals_backward_f32 (K12, the backbone builder's vector-Jacobian product).
+// 11: ps_fape_f32 / ps_fape_backward_f32 (K13 / K14, frame-aligned point error and its gradient),
+//     ps_frames_backward_f32 (K4's vector-Jacobian product).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

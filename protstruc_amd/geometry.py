@@ -7,7 +7,9 @@ launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
 ``initialize_backbone_with_mds`` and ``fix_chirality`` the SMACOF and finishing kernels (csrc/mds.hip).
 ``inter_residue_geometry`` is the fused featuriser as a differentiable function of the coordinates (its backward pass is
 one HIP kernel, ``ops.inter_residue_geometry_backward``); ``backbone_from_dihedrals`` is the backbone builder as a
-differentiable function of the dihedrals, bond angles and bond lengths (``ops.backbone_from_dihedrals_backward``).
+differentiable function of the dihedrals, bond angles and bond lengths (``ops.backbone_from_dihedrals_backward``);
+``frame_aligned_point_error`` is the fused FAPE loss (``ops.fape`` / ``ops.fape_backward``) and ``backbone_frames`` the
+per-residue frames as a differentiable function of the coordinates (``ops.frames_backward``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -213,6 +215,85 @@ def backbone_from_dihedrals(dihedrals, chain_idx=None, residue_mask=None, bond_a
     first residue, psi / omega at its last, everything that only moves masked residues) get exact zeros.  ``atom_mask``
     is not differentiable; ``chain_idx`` / ``residue_mask`` get no gradient; no double backward."""
     return _BackboneFromDihedrals.apply(dihedrals, chain_idx, residue_mask, bond_angles, bond_lengths, include_cb, n_slots)
+
+
+def _slot(atom) -> int:
+    """An atom slot from its name ("CA"; KeyError on an unknown one, as StructureBatch raises) or its index."""
+    from .general import ATOM
+    return int(ATOM[atom]) if isinstance(atom, str) else int(atom)
+
+
+class _BackboneFrames(torch.autograd.Function):
+    """ops.frames (K4) with ops.frames_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, xyz, residue_mask, a1, a2, a3, t_atom):
+        # t_atom None: the rotation alone (no translation is computed or written; that output is None)
+        rot, trans = ops.frames(xyz, a1, a2, a3, 0 if t_atom is None else t_atom, want_trans=t_atom is not None)
+        ctx.slots = (a1, a2, a3, 0 if t_atom is None else t_atom)
+        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None: its arithmetic is skipped
+        ctx.save_for_backward(xyz, residue_mask)
+        return rot, trans
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_rot, grad_trans):
+        xyz, residue_mask = ctx.saved_tensors
+        if grad_rot is None and grad_trans is None:
+            return (None,) * 6
+        grad_xyz = ops.frames_backward(xyz, *ctx.slots, grad_rot=grad_rot, grad_trans=grad_trans, residue_mask=residue_mask)
+        return grad_xyz.to(xyz.dtype), None, None, None, None, None
+
+
+def backbone_frames(xyz, a1="N", a2="CA", a3="C", atom="CA", residue_mask=None):
+    """Per-residue frames as a differentiable function of the coordinates: ``(rot (B,N,3,3), trans (B,N,3))``, bit for
+    bit what ``ops.frames`` (K4) returns -- the Gram-Schmidt basis of (a3 - a2, a1 - a2) as the columns of ``rot`` and the
+    position of ``atom`` -- attached to the autograd graph.  The backward pass is one launch of the HIP kernel behind
+    ``ops.frames_backward``; an output the loss does not use costs nothing there.  Atoms are names ("CA") or slot indices;
+    ``atom=None`` computes the rotation alone and returns ``(rot, None)``.
+    Residues absent from ``residue_mask`` (B,N) get an exactly zero gradient whatever their coordinates hold (NaN of
+    missing atoms included); their frames are still computed and are the caller's to mask.  No double backward."""
+    return _BackboneFrames.apply(xyz, residue_mask, _slot(a1), _slot(a2), _slot(a3), None if atom is None else _slot(atom))
+
+
+class _FrameAlignedPointError(torch.autograd.Function):
+    """ops.fape with ops.fape_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, rot, trans, points, target_rot, target_trans, target_points, frame_mask, point_mask, clamp, scale, eps):
+        loss, _ = ops.fape(rot, trans, points, target_rot, target_trans, target_points, frame_mask, point_mask,
+                           clamp=clamp, scale=scale, eps=eps)
+        ctx.scalars = (None if isinstance(clamp, torch.Tensor) else clamp, scale, eps)
+        ctx.dtypes = (rot.dtype, trans.dtype, points.dtype)
+        # nothing of the forward's arithmetic is kept: the backward kernel recomputes the pairs from the inputs
+        ctx.save_for_backward(rot, trans, points, target_rot, target_trans, target_points, frame_mask, point_mask,
+                              clamp if isinstance(clamp, torch.Tensor) else None)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        *operands, frame_mask, point_mask, clamp_t = ctx.saved_tensors
+        clamp, scale, eps = ctx.scalars
+        need = ctx.needs_input_grad[:3]
+        grads = ops.fape_backward(*operands, grad_loss, frame_mask, point_mask, clamp=clamp_t if clamp is None else clamp,
+                                  scale=scale, eps=eps, want_rot=need[0], want_trans=need[1], want_points=need[2])
+        return tuple(g.to(dt) if wanted else None for g, dt, wanted in zip(grads, ctx.dtypes, need)) + (None,) * 8
+
+
+def frame_aligned_point_error(rot, trans, points, target_rot, target_trans, target_points, frame_mask=None,
+                              point_mask=None, *, clamp=10.0, scale=10.0, eps=1e-4):
+    """Frame-aligned point error (AlphaFold 2 suppl. alg. 28) per structure, ``(B,)`` fp32, differentiable with respect to
+    ``rot`` (B,N,3,3; basis vectors as columns), ``trans`` (B,N,3) and ``points`` (B,M,3):
+    the mean over valid (frame, point) pairs of ``min(sqrt(|R_i^T (x_j - t_i) - R'_i^T (x'_j - t'_i)|^2 + eps), clamp) / scale``.
+    ``frame_mask`` (B,N) and ``point_mask`` (B,M) select the pairs (None = all); ``clamp`` is a float or a (B,) tensor
+    and ``inf`` means unclamped, so a per-sample mixture of clamped and unclamped structures is one call.  Forward and
+    backward are one fused HIP kernel each (``ops.fape``, ``ops.fape_backward``): no (B,N,M) tensor is ever built, and only
+    the gradients autograd asks for are computed.  A pair passes gradient iff its distance is below the clamp; a structure
+    without a valid pair has loss 0 and zero gradients; masked frames and points get exact zeros, and NaN there (missing
+    atoms) never reaches the loss or a gradient.  The target side is a constant; no double backward."""
+    detach = [t.detach() for t in (target_rot, target_trans, target_points)]
+    return _FrameAlignedPointError.apply(rot, trans, points, *detach, frame_mask, point_mask, clamp, scale, eps)
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

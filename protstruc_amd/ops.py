@@ -973,6 +973,178 @@ def frames(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *, wan
     return rot, trans
 
 
+def _check_float_tensor(t, shape, name: str, like: str) -> None:
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)} to match {like}, got {tuple(t.shape)}")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+
+
+def check_frames_backward_shapes(xyz, a1: int, a2: int, a3: int, t_atom: int = 1, grad_rot=None, grad_trans=None,
+                                 residue_mask=None, out=None) -> None:
+    """Shape rules of ``frames_backward``, on shapes, dtypes and slots only (no device, no launch): ValueError."""
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[-1] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    if not xyz.dtype.is_floating_point:
+        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
+    B, N, A = shape[:3]
+    if grad_rot is None and grad_trans is None:
+        raise ValueError("at least one of grad_rot and grad_trans is required")
+    if grad_rot is not None:
+        _check_float_tensor(grad_rot, (B, N, 3, 3), "grad_rot", f"xyz {shape}")
+        _check_atom_slots(A, a1, a2, a3)
+    if grad_trans is not None:
+        _check_float_tensor(grad_trans, (B, N, 3), "grad_trans", f"xyz {shape}")
+        _check_atom_slots(A, t_atom)
+    if residue_mask is not None and tuple(residue_mask.shape) != (B, N):
+        raise ValueError(f"residue_mask must have shape {(B, N)} to match xyz {shape}, got {tuple(residue_mask.shape)}")
+    _check_out(out, shape, "out")
+
+
+def frames_backward(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *,
+                    grad_rot: Optional[torch.Tensor] = None, grad_trans: Optional[torch.Tensor] = None,
+                    residue_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Vector-Jacobian product of K4 (``frames``) in one launch: ``grad_xyz`` (B,N,A,3) fp32 from the upstream
+    ``grad_rot`` (B,N,3,3; any 3x3, not assumed tangent to the rotations) and / or ``grad_trans`` (B,N,3); an absent one
+    is zero and its arithmetic is skipped.  Contributions are summed where slots coincide; every element of the result is
+    written: slots that are not read, and residues absent from ``residue_mask`` (B,N), are exact zeros -- NaN there never
+    reaches the result (include/protstruc_hip.h)."""
+    check_frames_backward_shapes(xyz, a1, a2, a3, t_atom, grad_rot, grad_trans, residue_mask, out)
+    xyz = _f32c(xyz, "xyz")
+    _same_device(xyz, grad_rot=grad_rot, grad_trans=grad_trans, residue_mask=residue_mask, out=out)
+    g_rot = None if grad_rot is None else _f32c(grad_rot, "grad_rot")
+    g_trans = None if grad_trans is None else _f32c(grad_trans, "grad_trans")
+    rmask = _u8c(residue_mask, "residue_mask")
+    B, N, A = xyz.shape[:3]
+    with _on(xyz.device):
+        if out is None:
+            out = torch.empty(B, N, A, 3, dtype=torch.float32, device=xyz.device)
+        if not (B == 0 or N == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_frames_backward_f32", _ptr(xyz), _ptr(g_rot), _ptr(g_trans), _ptr(rmask), _ptr(out), B, N, A,
+                    int(a1), int(a2), int(a3), int(t_atom), _stream(xyz))
+    return out
+
+
+FAPE_FRAME_TILE = 64   # PS_FAPE_FRAME_TILE of include/protstruc_hip.h: frames per workgroup = one partial sum each
+
+
+def check_fape_shapes(rot, trans, points, target_rot, target_trans, target_points, frame_mask=None, point_mask=None,
+                      clamp=10.0, scale=10.0, eps=1e-4, grad_loss=None) -> None:
+    """Shape rules of ``fape`` / ``fape_backward``, on shapes, dtypes, devices and the three scalars only (no launch):
+    ValueError.  ``clamp`` is a positive float (``inf`` = unclamped) or a (B,) float tensor; the values of a tensor are
+    checked where that costs no device synchronisation, i.e. when it lives on the host."""
+    shape = tuple(rot.shape)
+    if len(shape) != 4 or shape[2:] != (3, 3):
+        raise ValueError(f"rot must have shape (batch, frames, 3, 3), got {shape}")
+    B, N = shape[:2]
+    pshape = tuple(points.shape)
+    if len(pshape) != 3 or pshape[0] != B or pshape[2] != 3:
+        raise ValueError(f"points must have shape ({B}, points, 3), got {pshape}")
+    M = pshape[1]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if N > 2 ** 30 or M > 2 ** 30:
+        raise ValueError(f"at most 2^30 frames and points per structure, got {N} and {M}")
+    for name, t, want in (("rot", rot, shape), ("trans", trans, (B, N, 3)), ("points", points, pshape),
+                          ("target_rot", target_rot, shape), ("target_trans", target_trans, (B, N, 3)),
+                          ("target_points", target_points, pshape)):
+        _check_float_tensor(t, want, name, f"rot {shape} and points {pshape}")
+    for name, t, want in (("frame_mask", frame_mask, (B, N)), ("point_mask", point_mask, (B, M))):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
+    if isinstance(clamp, torch.Tensor):
+        _check_float_tensor(clamp, (B,), "clamp", f"rot {shape}")
+        if not clamp.is_cuda and not bool((clamp > 0).all()):
+            raise ValueError("clamp must be positive (inf = unclamped)")
+    elif not float(clamp) > 0:
+        raise ValueError(f"clamp must be positive (inf = unclamped), got {clamp}")
+    if not (float(scale) > 0 and float(scale) != float("inf")):
+        raise ValueError(f"scale must be positive and finite, got {scale}")
+    if not (float(eps) >= 0 and float(eps) != float("inf")):
+        raise ValueError(f"eps must be non-negative and finite, got {eps}")
+    if grad_loss is not None:
+        _check_float_tensor(grad_loss, (B,), "grad_loss", f"rot {shape}")
+    tensors = {"trans": trans, "points": points, "target_rot": target_rot, "target_trans": target_trans,
+               "target_points": target_points, "frame_mask": frame_mask, "point_mask": point_mask, "grad_loss": grad_loss}
+    if isinstance(clamp, torch.Tensor):
+        tensors["clamp"] = clamp
+    _same_device(rot, **tensors)
+
+
+def _fape_operands(rot, trans, points, target_rot, target_trans, target_points, frame_mask, point_mask, clamp):
+    """The eight tensor operands of the two FAPE launches as the kernels read them, and the (B,) clamp on the device."""
+    rot = _f32c(rot, "rot")
+    floats = [rot] + [_f32c(t, name) for t, name in ((trans, "trans"), (points, "points"), (target_rot, "target_rot"),
+                                                      (target_trans, "target_trans"), (target_points, "target_points"))]
+    if isinstance(clamp, torch.Tensor):
+        clamp = _f32c(clamp, "clamp")
+    else:
+        clamp = torch.full((rot.shape[0],), float(clamp), dtype=torch.float32, device=rot.device)
+    return floats, _u8c(frame_mask, "frame_mask"), _u8c(point_mask, "point_mask"), clamp
+
+
+def fape(rot: torch.Tensor, trans: torch.Tensor, points: torch.Tensor, target_rot: torch.Tensor,
+         target_trans: torch.Tensor, target_points: torch.Tensor, frame_mask: Optional[torch.Tensor] = None,
+         point_mask: Optional[torch.Tensor] = None, *, clamp=10.0, scale: float = 10.0, eps: float = 1e-4):
+    """K13.  Frame-aligned point error, fused: ``(loss (B,), count (B,))`` fp32 with
+    ``loss[b] = mean over valid (frame i, point j) of min(sqrt(|R_i^T (x_j - t_i) - R'_i^T (x'_j - t'_i)|^2 + eps), clamp[b]) / scale``
+    and ``count[b]`` the number of valid pairs (``frame_mask`` (B,N) times ``point_mask`` (B,M); None = all), as fp32:
+    exact below 2^24 pairs per structure, rounded above.  ``rot``
+    (B,N,3,3) has the basis vectors as columns, as ``frames`` returns it; ``points`` (B,M,3) may be the (B, N*A, 3) view
+    of coordinates with the atom mask as ``point_mask`` (masked points cost nothing).  ``clamp``: a float or a (B,)
+    tensor, ``inf`` = unclamped.  A structure without a valid pair has loss 0; NaN at masked frames / points never
+    reaches the result; deterministic (include/protstruc_hip.h)."""
+    check_fape_shapes(rot, trans, points, target_rot, target_trans, target_points, frame_mask, point_mask, clamp, scale, eps)
+    floats, fm, pm, cl = _fape_operands(rot, trans, points, target_rot, target_trans, target_points, frame_mask,
+                                        point_mask, clamp)
+    B, N, M = floats[0].shape[0], floats[0].shape[1], floats[2].shape[1]
+    dev = floats[0].device
+    with _on(dev):
+        if B == 0 or N == 0 or M == 0:   # empty input: nothing to launch (an empty tensor has no device pointer); no pair
+            return torch.zeros(B, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.float32, device=dev)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        count = torch.empty(B, dtype=torch.float32, device=dev)
+        partials = torch.empty(B * -(-N // FAPE_FRAME_TILE), dtype=torch.float64, device=dev)   # one sum per workgroup
+        _launch("ps_fape_f32", *[_ptr(t) for t in floats], _ptr(fm), _ptr(pm), _ptr(cl), float(scale), float(eps),
+                _ptr(loss), _ptr(count), _ptr(partials), B, N, M, _stream(loss))
+    return loss, count
+
+
+def fape_backward(rot: torch.Tensor, trans: torch.Tensor, points: torch.Tensor, target_rot: torch.Tensor,
+                  target_trans: torch.Tensor, target_points: torch.Tensor, grad_loss: torch.Tensor,
+                  frame_mask: Optional[torch.Tensor] = None, point_mask: Optional[torch.Tensor] = None, *, clamp=10.0,
+                  scale: float = 10.0, eps: float = 1e-4, want_rot: bool = True, want_trans: bool = True,
+                  want_points: bool = True):
+    """K14.  Vector-Jacobian product of ``fape`` with respect to the predicted side in one launch that recomputes the
+    pairs: ``(grad_rot (B,N,3,3), grad_trans (B,N,3), grad_points (B,M,3))`` fp32 from the upstream ``grad_loss`` (B,).
+    A gradient that is not wanted comes back as None and its work is skipped (the frame-owned workgroups compute
+    ``grad_rot`` and ``grad_trans`` together, the point-owned ones ``grad_points``).  ``grad_rot`` is the unconstrained
+    3x3 gradient.  A pair passes gradient iff its distance is below ``clamp``; masked frames and points get exact zeros
+    and NaN there never reaches an output; the target side gets no gradient; deterministic (include/protstruc_hip.h).
+    With ``eps = 0`` a valid pair whose two sides coincide has distance 0 and no derivative: its rows come out NaN, as under
+    autograd, so keep ``eps > 0`` where prediction and target can be equal."""
+    check_fape_shapes(rot, trans, points, target_rot, target_trans, target_points, frame_mask, point_mask, clamp, scale,
+                      eps, grad_loss)
+    if not (want_rot or want_trans or want_points):
+        raise ValueError("at least one gradient must be wanted")
+    floats, fm, pm, cl = _fape_operands(rot, trans, points, target_rot, target_trans, target_points, frame_mask,
+                                        point_mask, clamp)
+    g = _f32c(grad_loss, "grad_loss")
+    B, N, M = floats[0].shape[0], floats[0].shape[1], floats[2].shape[1]
+    dev = floats[0].device
+    with _on(dev):
+        # empty input: nothing to launch (an empty tensor has no device pointer); without a pair every gradient is zero
+        alloc = torch.zeros if (B == 0 or N == 0 or M == 0) else torch.empty
+        g_rot = alloc(B, N, 3, 3, dtype=torch.float32, device=dev) if want_rot else None
+        g_trans = alloc(B, N, 3, dtype=torch.float32, device=dev) if want_trans else None
+        g_pts = alloc(B, M, 3, dtype=torch.float32, device=dev) if want_points else None
+        if alloc is torch.empty:
+            _launch("ps_fape_backward_f32", *[_ptr(t) for t in floats], _ptr(fm), _ptr(pm), _ptr(cl), float(scale),
+                    float(eps), _ptr(g), _ptr(g_rot), _ptr(g_trans), _ptr(g_pts), B, N, M, _stream(g))
+    return g_rot, g_trans, g_pts
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -306,6 +306,9 @@ class StructureBatch:
     def backbone_orientations(self, a1: str = "N", a2: str = "CA", a3: str = "C") -> torch.FloatTensor:
         """Gram-Schmidt frame of each residue, basis vectors as columns (protstruc.py:543-571)."""
         s1, s2, s3 = ATOM[a1], ATOM[a2], ATOM[a3]  # KeyError on unknown names, as in the reference
+        if torch.is_grad_enabled() and self.xyz.requires_grad:
+            from . import geometry
+            return geometry.backbone_frames(self.xyz, s1, s2, s3, atom=None)[0]  # the same launch, with the HIP backward kernel attached
         return ops.frames(self.xyz, s1, s2, s3, want_trans=False)[0]
 
     def backbone_translations(self, atom: str = "CA") -> torch.FloatTensor:
@@ -313,8 +316,54 @@ class StructureBatch:
         return self.xyz[:, :, ATOM[atom]]
 
     def backbone_orientations_and_translations(self, a1: str = "N", a2: str = "CA", a3: str = "C", atom: str = "CA"):
-        """Both frame outputs from one launch (rotation (B,N,3,3), translation (B,N,3), contiguous)."""
+        """Both frame outputs from one launch (rotation (B,N,3,3), translation (B,N,3), contiguous).  Like
+        :meth:`backbone_orientations`, differentiable with respect to coordinates that require grad
+        (``geometry.backbone_frames``); the values are the same either way."""
+        if torch.is_grad_enabled() and self.xyz.requires_grad:
+            from . import geometry
+            return geometry.backbone_frames(self.xyz, ATOM[a1], ATOM[a2], ATOM[a3], ATOM[atom])
         return ops.frames(self.xyz, ATOM[a1], ATOM[a2], ATOM[a3], ATOM[atom])
+
+    def frame_aligned_point_error(self, target: "StructureBatch", atoms=("N", "CA", "C"), a1: str = "N", a2: str = "CA",
+                                  a3: str = "C", clamp=10.0, scale: float = 10.0, eps: float = 1e-4) -> torch.Tensor:
+        """Frame-aligned point error of this batch against ``target`` per structure, (B,) (AlphaFold 2 suppl. alg. 28;
+        ``geometry.frame_aligned_point_error``).  Frames are the Gram-Schmidt frames of (a1, a2, a3) with the origin at
+        ``a2``, from this batch and from ``target``; points are the named ``atoms`` of every residue, or every atom slot
+        with ``atoms=None``.  The frame mask is the residues whose three frame atoms are present in both batches, the
+        point mask the atoms present in both; the points reach the kernel as the (B, N*A, 3) view of the coordinates with
+        the slot selection folded into the mask -- no gather, no copy.  A single-structure target serves the whole batch,
+        as in :meth:`align`.  ``clamp`` is a float or a (B,) tensor (``inf`` = unclamped).  Differentiable with respect to
+        this batch's coordinates where they require grad (frames and points both; HIP kernels all the way); the target is
+        a constant.  NaN coordinates of missing atoms never reach the loss or the gradient."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        if target.get_batch_size() != 1 and B != target.get_batch_size():
+            raise ValueError("Batch size of the two structures must be the same.")
+        txyz = target.get_xyz().detach().to(self.device)
+        if tuple(txyz.shape[1:]) != (N, A, 3):
+            raise ValueError(f"target coordinates {tuple(txyz.shape)} do not match this batch's {tuple(self.xyz.shape)}")
+        s1, s2, s3 = int(ATOM[a1]), int(ATOM[a2]), int(ATOM[a3])
+        present = torch.ones(B, N, A, dtype=torch.bool, device=self.device)
+        for m in (self.atom_mask, target.get_atom_mask()):
+            if m is not None:
+                present = present & (m.to(self.device) != 0)      # (1,N,A) of a single-structure target broadcasts
+        frame_mask = present[:, :, s1] & present[:, :, s2] & present[:, :, s3]
+        if atoms is not None:
+            for atom in atoms:
+                if not ATOM.is_valid(atom):
+                    raise ValueError(f"Atom {atom} is not valid.")
+            chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+            chosen[[int(ATOM[a]) for a in atoms]] = True
+            present = present & chosen
+        if txyz.shape[0] != B:
+            txyz = txyz.expand(B, N, A, 3).contiguous()
+        with torch.no_grad():
+            target_rot, target_trans = ops.frames(txyz, s1, s2, s3, s2)
+        rot, trans = geometry.backbone_frames(self.xyz, s1, s2, s3, s2, residue_mask=frame_mask)
+        return geometry.frame_aligned_point_error(rot, trans, self.xyz.reshape(B, N * A, 3), target_rot, target_trans,
+                                                  txyz.reshape(B, N * A, 3), frame_mask, present.reshape(B, N * A),
+                                                  clamp=clamp, scale=scale, eps=eps)
 
     # ------------------------------------------------------------------ A6-A8 inter-residue angles
     @staticmethod

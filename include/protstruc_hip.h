@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 11
+#define PS_ABI_VERSION 12
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -451,6 +451,47 @@ int ps_fape_backward_f32(const float* rot_p, const float* trans_p, const float* 
                          float scale, float eps, const float* grad_loss,
                          float* grad_rot, float* grad_trans, float* grad_pts,
                          int B, int N, int M, void* stream);
+
+/*
+ * K15 (ABI 12) -- lDDT (local distance difference test) per point, fused: no (B,M,M) tensor exists.  For structure b
+ * with predicted points x_i and target points x'_i, i < M (pts_p, pts_t (B,M,3)), p = point_mask (B,M), one byte each,
+ * NULL = all present, and groups (B,M) int32 on the device, NULL = none:
+ *   d_ij = sqrt(|x_i - x_j|^2 + eps)    d'_ij likewise on the target    delta_ij = |d_ij - d'_ij|
+ *   c_ij = p_i p_j [i != j] [groups_i != groups_j, when groups are given] [d'_ij < cutoff]
+ *   e_ij = (1/T) sum_t [delta_ij < thresholds[t]]             (smooth == 0: the metric)
+ *   e_ij = (1/T) sum_t sigmoid(thresholds[t] - delta_ij)      (smooth != 0: AlphaFold 3 suppl. alg. 27)
+ *   S[b][i] = sum_j c_ij e_ij        count[b][i] = sum_j c_ij
+ * S and count are (B,M) fp32; count is integer-valued (exact below 2^24 pairs per point).  A score is S / max(count, 1):
+ * a point without an included pair has S = 0 and count = 0, never 1 or NaN.  thresholds is a HOST array of T floats,
+ * 1 <= T <= PS_LDDT_MAX_THRESHOLDS, strictly increasing, each in (0, PS_LDDT_MAX_THRESHOLD]; cutoff > 0 and eps >= 0,
+ * finite.  The inclusion test is evaluated as |x'_i - x'_j|^2 + eps < cutoff^2 in fp32 (no square root; the same bits for
+ * (i, j) and (j, i)), so a target pair within fp32 rounding of the cutoff may fall on either side.  Masked points are
+ * dropped by selection -- they are compacted away while a tile is staged, NaN there never reaches an output -- and get
+ * S = count = 0.  pts may be any (B,M,3) view of coordinates, e.g. all N*A atom slots with the atom mask as point_mask
+ * and the residue index as groups.  Owner-computes, PS_LDDT_POINT_TILE points per workgroup; no atomics, fixed
+ * summation order: bit-for-bit repeatable.  Any M.  B <= 65535; M <= 2^30.
+ */
+#define PS_LDDT_POINT_TILE 64
+#define PS_LDDT_MAX_THRESHOLDS 8
+#define PS_LDDT_MAX_THRESHOLD 64.0f
+int ps_lddt_f32(const float* pts_p, const float* pts_t, const uint8_t* point_mask, const int32_t* groups,
+                float cutoff, const float* thresholds, int T, int smooth, float eps,
+                float* S, float* count, int B, int M, void* stream);
+
+/*
+ * K16 (ABI 12) -- backward pass of the smooth form of ps_lddt_f32 with respect to the predicted points (the target is a
+ * constant), in one launch that recomputes every pair; nothing is saved from the forward.  With w = grad_S (B,M) =
+ * dL/dS, s_t = sigmoid(thresholds[t] - delta_ij) and e'(delta) = -(1/T) sum_t s_t (1 - s_t):
+ *   grad_pts[b][i] = sum_j c_ij (w_i + w_j) e'(delta_ij) sign(d_ij - d'_ij) (x_i - x_j) / d_ij
+ * with sign(0) = 0, as under autograd: a prediction equal to its target has an exactly zero gradient.  c is symmetric, so
+ * this is one row sweep per owner: no atomics, fixed summation order, bit-for-bit repeatable.  Every element of grad_pts
+ * (B,M,3) is written; masked points get exact zeros by selection (NaN coordinates or NaN grad_S there never reach an
+ * output).  Arguments and limits as ps_lddt_f32.  With eps = 0 an included pair of coincident predicted points has
+ * d_ij = 0 and no derivative (0 * inf): its owners' rows come out NaN, as under autograd; keep eps > 0.
+ */
+int ps_lddt_backward_f32(const float* pts_p, const float* pts_t, const uint8_t* point_mask, const int32_t* groups,
+                         float cutoff, const float* thresholds, int T, float eps,
+                         const float* grad_S, float* grad_pts, int B, int M, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

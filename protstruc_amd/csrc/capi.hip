@@ -17,6 +17,7 @@
 // 10: ps_backbone_from_dihedrals_backward_f32 (K12, the backbone builder's vector-Jacobian product).
 // 11: ps_fape_f32 / ps_fape_backward_f32 (K13 / K14, frame-aligned point error and its gradient),
 //     ps_frames_backward_f32 (K4's vector-Jacobian product).
+// 12: ps_lddt_f32 / ps_lddt_backward_f32 (K15 / K16, lDDT per point, hard and smooth, and the smooth form's gradient).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

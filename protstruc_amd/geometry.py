@@ -9,7 +9,8 @@ launcher; ``dot`` / ``norm`` / ``unit`` are single broadcasting tensor ops.
 one HIP kernel, ``ops.inter_residue_geometry_backward``); ``backbone_from_dihedrals`` is the backbone builder as a
 differentiable function of the dihedrals, bond angles and bond lengths (``ops.backbone_from_dihedrals_backward``);
 ``frame_aligned_point_error`` is the fused FAPE loss (``ops.fape`` / ``ops.fape_backward``) and ``backbone_frames`` the
-per-residue frames as a differentiable function of the coordinates (``ops.frames_backward``).
+per-residue frames as a differentiable function of the coordinates (``ops.frames_backward``); ``lddt`` is the fused lDDT,
+hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -294,6 +295,61 @@ def frame_aligned_point_error(rot, trans, points, target_rot, target_trans, targ
     atoms) never reaches the loss or a gradient.  The target side is a constant; no double backward."""
     detach = [t.detach() for t in (target_rot, target_trans, target_points)]
     return _FrameAlignedPointError.apply(rot, trans, points, *detach, frame_mask, point_mask, clamp, scale, eps)
+
+
+class _LDDT(torch.autograd.Function):
+    """ops.lddt with ops.lddt_backward as the vector-Jacobian product of its smooth form."""
+
+    @staticmethod
+    def forward(ctx, points, target_points, point_mask, groups, cutoff, thresholds, smooth, eps):
+        S, n = ops.lddt(points, target_points, point_mask, groups, cutoff=cutoff, thresholds=thresholds, smooth=smooth,
+                        eps=eps)
+        ctx.scalars = (cutoff, thresholds, eps)
+        ctx.dtype = points.dtype
+        if smooth:
+            # nothing of the forward's arithmetic is kept: the backward kernel recomputes the pairs from the inputs
+            ctx.save_for_backward(points, target_points, point_mask, groups)
+            ctx.mark_non_differentiable(n)
+        else:
+            ctx.mark_non_differentiable(S, n)   # a step function of the coordinates: a metric, not a loss
+        return S, n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_S, _grad_n):
+        points, target_points, point_mask, groups = ctx.saved_tensors
+        cutoff, thresholds, eps = ctx.scalars
+        grad = ops.lddt_backward(points, target_points, grad_S, point_mask, groups, cutoff=cutoff, thresholds=thresholds,
+                                 eps=eps)
+        return (grad.to(ctx.dtype),) + (None,) * 7
+
+
+def lddt(points, target_points, point_mask=None, groups=None, cutoff=15.0, thresholds=ops.LDDT_THRESHOLDS, smooth=False,
+         reduction="point", eps=1e-10):
+    """lDDT (local distance difference test) of ``points`` (B,M,3) against ``target_points``: for every point the mean,
+    over the points within ``cutoff`` of it ON THE TARGET (itself, points outside ``point_mask`` (B,M) and, where
+    ``groups`` (B,M; integers) are given, points of its own group excluded), of the fraction of ``thresholds`` under which
+    the pair's distance stays preserved.  ``reduction="point"`` returns ``S / max(n, 1)`` per point, (B,M);
+    ``"structure"`` returns ``sum S / max(sum n, 1)``, (B,), the score over all pairs; ``"none"`` returns the kernel's
+    ``(S, n)``.  A point (a structure) without a counted pair scores 0, never 1 or NaN.
+
+    ``smooth=False`` is the METRIC: a step function of the coordinates, so the result carries no ``grad_fn`` even when
+    the inputs require grad; per residue it is the training target of a confidence (pLDDT) head (AlphaFold 2 suppl.
+    1.9.6).  ``smooth=True`` replaces every step by ``sigmoid(threshold - |d - d'|)`` (AlphaFold 3 suppl. alg. 27) and is
+    differentiable with respect to ``points``: ``1 - lddt(..., smooth=True, reduction="structure")`` is a loss.
+
+    Forward and backward are one fused HIP kernel each (``ops.lddt``, ``ops.lddt_backward``): nothing of size M^2 is ever
+    built; the reductions are ordinary torch on (B,M) tensors.  Masked points get exact zeros (score and gradient), and NaN
+    there (missing atoms) never reaches a result.  The target is a constant; no double backward."""
+    if reduction not in ("point", "structure", "none"):
+        raise ValueError(f"reduction must be 'point', 'structure' or 'none', got {reduction!r}")
+    S, n = _LDDT.apply(points, target_points.detach(), point_mask, groups, float(cutoff),
+                       tuple(float(t) for t in thresholds), bool(smooth), float(eps))
+    if reduction == "none":
+        return S, n
+    if reduction == "point":
+        return S / n.clamp(min=1)
+    return S.sum(-1) / n.sum(-1).clamp(min=1)
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

@@ -1145,6 +1145,99 @@ def fape_backward(rot: torch.Tensor, trans: torch.Tensor, points: torch.Tensor, 
     return g_rot, g_trans, g_pts
 
 
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+LDDT_MAX_THRESHOLDS = 8     # PS_LDDT_MAX_THRESHOLDS of include/protstruc_hip.h
+LDDT_MAX_THRESHOLD = 64.0   # PS_LDDT_MAX_THRESHOLD: exp(-threshold) stays a normal float32
+
+
+def check_lddt_shapes(points, target_points, point_mask=None, groups=None, cutoff=15.0, thresholds=LDDT_THRESHOLDS,
+                      eps=1e-10, grad_S=None) -> None:
+    """Shape rules of ``lddt`` / ``lddt_backward``, on shapes, dtypes, devices and the scalars only (no launch):
+    ValueError.  ``thresholds``: 1 to 8 strictly increasing floats in (0, 64]; ``cutoff`` positive and finite; ``groups``
+    an integer tensor."""
+    shape = tuple(points.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
+    B, M = shape[:2]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if M > 2 ** 30:
+        raise ValueError(f"at most 2^30 points per structure, got {M}")
+    _check_float_tensor(points, shape, "points", f"points {shape}")
+    _check_float_tensor(target_points, shape, "target_points", f"points {shape}")
+    if point_mask is not None and tuple(point_mask.shape) != (B, M):
+        raise ValueError(f"point_mask must have shape {(B, M)}, got {tuple(point_mask.shape)}")
+    if groups is not None:
+        if tuple(groups.shape) != (B, M):
+            raise ValueError(f"groups must have shape {(B, M)}, got {tuple(groups.shape)}")
+        if groups.dtype.is_floating_point or groups.dtype.is_complex or groups.dtype == torch.bool:
+            raise ValueError(f"groups must be an integer tensor, got {groups.dtype}")
+    if not (float(cutoff) > 0 and float(cutoff) != float("inf")):
+        raise ValueError(f"cutoff must be positive and finite, got {cutoff}")
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= LDDT_MAX_THRESHOLDS:
+        raise ValueError(f"between 1 and {LDDT_MAX_THRESHOLDS} thresholds, got {len(thr)}")
+    if not all(0 < t <= LDDT_MAX_THRESHOLD for t in thr) or any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError(f"thresholds must be strictly increasing and in (0, {LDDT_MAX_THRESHOLD}], got {tuple(thr)}")
+    if not (float(eps) >= 0 and float(eps) != float("inf")):
+        raise ValueError(f"eps must be non-negative and finite, got {eps}")
+    if grad_S is not None:
+        _check_float_tensor(grad_S, (B, M), "grad_S", f"points {shape}")
+    _same_device(points, target_points=target_points, point_mask=point_mask, groups=groups, grad_S=grad_S)
+
+
+def _lddt_operands(points, target_points, point_mask, groups, thresholds):
+    thr = (ctypes.c_float * len(thresholds))(*[float(t) for t in thresholds])   # a host array: the library reads it there
+    return (_f32c(points, "points"), _f32c(target_points, "target_points"), _u8c(point_mask, "point_mask"),
+            _i32c(groups, "groups"), thr)
+
+
+def lddt(points: torch.Tensor, target_points: torch.Tensor, point_mask: Optional[torch.Tensor] = None,
+         groups: Optional[torch.Tensor] = None, *, cutoff: float = 15.0, thresholds=LDDT_THRESHOLDS, smooth: bool = False,
+         eps: float = 1e-10):
+    """K15.  lDDT per point, fused: ``(S (B,M), n (B,M))`` fp32 with ``n_i`` the number of points j that count for point
+    i -- both in ``point_mask`` (None = all), ``j != i``, in another group where ``groups`` (B,M; integers) are given, and
+    within ``cutoff`` of i ON THE TARGET -- and ``S_i`` the sum over them of the fraction of ``thresholds`` that
+    ``| |x_i - x_j| - |x'_i - x'_j| |`` stays under (``smooth=False``, the metric), or of the mean of
+    ``sigmoid(threshold - that difference)`` (``smooth=True``, AlphaFold 3 suppl. alg. 27).  The score of a point is
+    ``S / n.clamp(min=1)``; a point without a partner has ``S = n = 0``.  Distances are ``sqrt(|.|^2 + eps)``.  ``points``
+    may be the (B, N*A, 3) view of coordinates with the atom mask as ``point_mask`` and the residue index as ``groups``.
+    Nothing of size M^2 is built; masked points get zeros and NaN there never reaches the result; deterministic
+    (include/protstruc_hip.h)."""
+    check_lddt_shapes(points, target_points, point_mask, groups, cutoff, thresholds, eps)
+    x, t, pm, gr, thr = _lddt_operands(points, target_points, point_mask, groups, thresholds)
+    B, M = x.shape[:2]
+    with _on(x.device):
+        if B == 0 or M == 0:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            return torch.zeros(B, M, dtype=torch.float32, device=x.device), torch.zeros(B, M, dtype=torch.float32, device=x.device)
+        S = torch.empty(B, M, dtype=torch.float32, device=x.device)
+        n = torch.empty(B, M, dtype=torch.float32, device=x.device)
+        _launch("ps_lddt_f32", _ptr(x), _ptr(t), _ptr(pm), _ptr(gr), float(cutoff), thr, len(thr), int(bool(smooth)),
+                float(eps), _ptr(S), _ptr(n), B, M, _stream(x))
+    return S, n
+
+
+def lddt_backward(points: torch.Tensor, target_points: torch.Tensor, grad_S: torch.Tensor,
+                  point_mask: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None, *,
+                  cutoff: float = 15.0, thresholds=LDDT_THRESHOLDS, eps: float = 1e-10) -> torch.Tensor:
+    """K16.  Vector-Jacobian product of ``lddt(..., smooth=True)`` with respect to ``points`` in one launch that
+    recomputes the pairs: ``grad_points`` (B,M,3) fp32 from the upstream ``grad_S`` (B,M).  Every element is written;
+    masked points get exact zeros and NaN there never reaches the result; a prediction equal to its target has an exactly
+    zero gradient; the target gets no gradient; deterministic (include/protstruc_hip.h).  Keep ``eps > 0``: with
+    ``eps = 0`` two coincident predicted points that count for each other have no derivative (NaN, as under autograd)."""
+    check_lddt_shapes(points, target_points, point_mask, groups, cutoff, thresholds, eps, grad_S)
+    x, t, pm, gr, thr = _lddt_operands(points, target_points, point_mask, groups, thresholds)
+    g = _f32c(grad_S, "grad_S")
+    B, M = x.shape[:2]
+    with _on(x.device):
+        if B == 0 or M == 0:
+            return torch.zeros(B, M, 3, dtype=torch.float32, device=x.device)
+        out = torch.empty(B, M, 3, dtype=torch.float32, device=x.device)
+        _launch("ps_lddt_backward_f32", _ptr(x), _ptr(t), _ptr(pm), _ptr(gr), float(cutoff), thr, len(thr), float(eps),
+                _ptr(g), _ptr(out), B, M, _stream(x))
+    return out
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -365,6 +365,60 @@ class StructureBatch:
                                                   txyz.reshape(B, N * A, 3), frame_mask, present.reshape(B, N * A),
                                                   clamp=clamp, scale=scale, eps=eps)
 
+    def lddt(self, target: "StructureBatch", atoms=("CA",), cutoff: float = 15.0, per_residue: bool = True,
+             smooth: bool = False) -> torch.Tensor:
+        """lDDT of this batch against ``target`` (``geometry.lddt``) over the named ``atoms`` of every residue
+        (``atoms="all"``: every atom slot), with the default thresholds 0.5, 1, 2 and 4: per residue, (B,N), the counted
+        pairs of a residue's atoms pooled before the division (``per_residue=True``), or per structure, (B,), over all
+        counted pairs.  A point counts where its atom is present in both batches and its residue is in both residue
+        masks; with more than one atom per residue, pairs inside a residue are excluded (they are rigid).  One atom per
+        residue reaches the kernel as the slot's (B,N,3) view of the coordinates; several as the (B, N*A, 3) view with
+        the selection folded into the point mask and the residue index as the group -- no gather.  A single-structure
+        target serves the whole batch.  A residue (a structure) without a counted pair scores 0.
+
+        ``smooth=False`` is the metric and carries no ``grad_fn``: per residue it is the training target of a pLDDT
+        head.  ``smooth=True`` is the sigmoid form, differentiable with respect to this batch's coordinates where they
+        require grad (HIP kernels forwards and backwards); the target is a constant.  NaN coordinates of missing atoms
+        never reach the score or the gradient."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        if target.get_batch_size() != 1 and B != target.get_batch_size():
+            raise ValueError("Batch size of the two structures must be the same.")
+        txyz = target.get_xyz().detach().to(self.device)
+        if tuple(txyz.shape[1:]) != (N, A, 3):
+            raise ValueError(f"target coordinates {tuple(txyz.shape)} do not match this batch's {tuple(self.xyz.shape)}")
+        if isinstance(atoms, str) and atoms == "all":
+            slots = list(range(A))
+        else:
+            for atom in atoms:
+                if not ATOM.is_valid(atom):
+                    raise ValueError(f"Atom {atom} is not valid.")
+            slots = sorted({int(ATOM[a]) for a in atoms})
+            if not slots or slots[-1] >= A:
+                raise ValueError(f"atoms {tuple(atoms)} do not fit the {A} atom slots of this batch")
+        present = (self.residue_mask & target.residue_mask.to(self.device))[:, :, None].expand(B, N, A)
+        for m in (self.atom_mask, target.get_atom_mask()):
+            if m is not None:
+                present = present & (m.to(self.device) != 0)      # (1,N,A) of a single-structure target broadcasts
+        if txyz.shape[0] != B:
+            txyz = txyz.expand(B, N, A, 3)
+        if len(slots) == 1:
+            s = slots[0]
+            S, n = geometry.lddt(self.xyz[:, :, s], txyz[:, :, s], present[:, :, s], cutoff=cutoff, smooth=smooth,
+                                 reduction="none")
+        else:
+            chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+            chosen[slots] = True
+            groups = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
+            S, n = geometry.lddt(self.xyz.reshape(B, N * A, 3), txyz.reshape(B, N * A, 3),
+                                 (present & chosen).reshape(B, N * A), groups, cutoff=cutoff, smooth=smooth,
+                                 reduction="none")
+            S, n = S.reshape(B, N, A).sum(-1), n.reshape(B, N, A).sum(-1)
+        if per_residue:
+            return S / n.clamp(min=1)
+        return S.sum(-1) / n.sum(-1).clamp(min=1)
+
     # ------------------------------------------------------------------ A6-A8 inter-residue angles
     @staticmethod
     def _pairwise_atom_slots(atoms_i: List[str], atoms_j: List[str]):

@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 12
+#define PS_ABI_VERSION 13
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -492,6 +492,75 @@ int ps_lddt_f32(const float* pts_p, const float* pts_t, const uint8_t* point_mas
 int ps_lddt_backward_f32(const float* pts_p, const float* pts_t, const uint8_t* point_mask, const int32_t* groups,
                          float cutoff, const float* thresholds, int T, float eps,
                          const float* grad_S, float* grad_pts, int B, int M, void* stream);
+
+/*
+ * K17 (ABI 13) -- steric clash energy per point (AlphaFold 2 suppl. 1.9.11, eq. 46), fused: no (B,M,M) tensor exists.
+ * For structure b with points x_i, i < M (pts (B,M,3)), radius (B,M) fp32, p = point_mask (B,M), one byte each, NULL =
+ * all present, and groups, link (B,M) int32 on the device, NULL = none:
+ *   d_ij = sqrt(|x_i - x_j|^2 + eps)          s_ij = radius_i + radius_j - tolerance
+ *   c_ij = p_i p_j [i != j] [groups_i != groups_j, when given] [not (link_i == link_j and link_i >= 0), when given]
+ *   v_ij = max(0, s_ij - d_ij)
+ *   E[b][i] = sum_j c_ij v_ij                 count[b][i] = sum_j c_ij [v_ij > 0]
+ * E and count are (B,M) fp32; count is integer-valued.  Every clashing pair appears in both owners' sums.  link expresses
+ * covalent bonds between groups: two points that carry the same non-negative id never clash.  Whether a pair is evaluated
+ * at all is decided in fp32 without a square root, [s_ij > 0 and |x_i - x_j|^2 + eps < s_ij^2] (the same bits for (i, j)
+ * and (j, i)), so a pair within fp32 rounding of s_ij = d_ij may fall on either side -- its v is that small; the pairs
+ * that pass are evaluated in double (v is a difference of nearly equal numbers), E is accumulated in double and rounded
+ * once.  Masked points are dropped by selection -- they are compacted away while a tile is staged, NaN coordinates or
+ * radii there never reach an output -- and get E = count = 0.  pts may be any (B,M,3) view of coordinates, e.g. all N*A
+ * atom slots with the atom mask as point_mask and the residue index as groups.  Owner-computes, PS_CLASH_POINT_TILE
+ * points per workgroup; no atomics, fixed summation order: bit-for-bit repeatable.  Any M.  B <= 65535; M <= 2^30;
+ * tolerance finite; eps >= 0 and finite.
+ */
+#define PS_CLASH_POINT_TILE 64
+int ps_clash_f32(const float* pts, const float* radius, const uint8_t* point_mask, const int32_t* groups,
+                 const int32_t* link, float tolerance, float eps,
+                 float* E, float* count, int B, int M, void* stream);
+
+/*
+ * K18 (ABI 13) -- backward pass of ps_clash_f32 with respect to the points (the radii are constants), in one launch that
+ * recomputes every pair; nothing is saved from the forward.  With w = grad_E (B,M) = dL/dE:
+ *   grad_pts[b][i] = - sum_j c_ij [v_ij > 0] (w_i + w_j) (x_i - x_j) / d_ij
+ * with relu'(0) = 0, as under autograd.  c and the test are symmetric, so this is one row sweep per owner: no atomics,
+ * fixed summation order, bit-for-bit repeatable.  Every element of grad_pts (B,M,3) is written; masked points get exact
+ * zeros by selection (NaN coordinates, radii or grad_E there never reach an output).  Arguments and limits as
+ * ps_clash_f32.  With eps = 0 a counted pair of coincident points has d_ij = 0 and no derivative (0 / 0): its owners' rows
+ * come out NaN, as under autograd; keep eps > 0.
+ */
+int ps_clash_backward_f32(const float* pts, const float* radius, const uint8_t* point_mask, const int32_t* groups,
+                          const int32_t* link, float tolerance, float eps,
+                          const float* grad_E, float* grad_pts, int B, int M, void* stream);
+
+/*
+ * K19 (ABI 13) -- peptide-bond geometry at every junction r -> r+1 (AlphaFold 2 suppl. 1.9.11, eq. 44-45).  xyz
+ * (B,N,A,3); junction_mask (B,N), one byte each, entry r = the junction from residue r to residue r+1, NULL = every
+ * junction valid (entry N-1 is ignored and taken as 0); next_is_proline (B,N) bytes, entry r = residue r+1 is a proline,
+ * NULL = none (ignored where the mask is 0).  n_slot, ca_slot, c_slot: three different atom slots in [0, A).  constants:
+ * a HOST array of PS_PEPTIDE_BOND_CONSTANTS floats (l0, sigma_l, l0_pro, sigma_l_pro, cos_cacn, sigma_cacn, cos_cnca,
+ * sigma_cnca, tau, eps, 0, 0), all finite, the sigmas, tau and eps non-negative.  With C, CA of residue r, N', CA' of
+ * residue r+1 and unit(v) = v / sqrt(|v|^2 + eps):
+ *   l  = sqrt(|N' - C|^2 + eps)           viol[b][r][0] = max(0, |l  - l0|       - tau * sigma_l)
+ *   ca = unit(CA - C) . unit(N' - C)      viol[b][r][1] = max(0, |ca - cos_cacn| - tau * sigma_cacn)
+ *   cn = unit(C - N') . unit(CA' - N')    viol[b][r][2] = max(0, |cn - cos_cnca| - tau * sigma_cnca)
+ * with (l0_pro, sigma_l_pro) in place of (l0, sigma_l) where next_is_proline is set.  viol is (B,N,3) fp32, every element
+ * written; invalid junctions and row N-1 get exact zeros by selection, whatever NaN sits there.  One lane per junction,
+ * evaluated in double and rounded once.  B * N <= 2^31.
+ */
+#define PS_PEPTIDE_BOND_CONSTANTS 12
+int ps_peptide_bond_f32(const float* xyz, const uint8_t* junction_mask, const uint8_t* next_is_proline,
+                        int n_slot, int ca_slot, int c_slot, const float* constants,
+                        float* viol, int B, int N, int A, void* stream);
+
+/*
+ * K20 (ABI 13) -- backward pass of ps_peptide_bond_f32: grad_xyz (B,N,A,3) from grad_viol (B,N,3).  One lane per residue
+ * recomputes its two junctions (r-1 -> r and r -> r+1) and writes the residue's whole (A,3) row -- slots it does not read
+ * get zeros -- so there are no atomics and the result repeats bit for bit; correct at chain ends and at N = 1.  |.| and
+ * max(0, .) have derivative 0 at the kink.  An invalid junction contributes exact zeros, and neither the coordinates nor
+ * grad_viol are read there.  Arguments and limits as ps_peptide_bond_f32.
+ */
+int ps_peptide_bond_backward_f32(const float* xyz, const uint8_t* junction_mask, const uint8_t* next_is_proline,
+                                 int n_slot, int ca_slot, int c_slot, const float* constants,
+                                 const float* grad_viol, float* grad_xyz, int B, int N, int A, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

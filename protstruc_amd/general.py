@@ -34,3 +34,24 @@ class _AtomSlot(enum.IntEnum):
 # canonical member); an unknown name raises KeyError; int(ATOM.CB) == 4.
 ATOM = _AtomSlot("ATOM", [(spelling, slot) for slot, (canonical, others) in enumerate(_BACKBONE)
                           for spelling in (canonical,) + others])
+
+
+def vdw_radius_table():
+    """Van der Waals radius of every atom slot of every residue type: a (21, 15) float32 tensor indexed by
+    [``pdb.ONE_TO_INDEX`` code][slot], from ``pdb.ATOM_SLOT`` with the element taken as the first letter of the atom name
+    (``ops.VDW_RADII``), OXT in slot 14, and 0 where a type has no such atom (glycine's CB, the slots past a side chain's
+    end).  The unknown type X has N, CA, C, O, CB and OXT only."""
+    import torch
+
+    from .ops import VDW_RADII
+    from .pdb import ATOM_SLOT, ONE_TO_INDEX, THREE_TO_ONE
+
+    table = torch.zeros(len(ONE_TO_INDEX), MAX_N_ATOMS_PER_RESIDUE, dtype=torch.float32)
+    for three, one in THREE_TO_ONE.items():
+        slots = ATOM_SLOT.get(three)
+        if slots is None:   # X: the slots every residue type with a side chain shares
+            slots = {name: k for k, (name, _) in enumerate(_BACKBONE)}
+            slots["OXT"] = MAX_N_ATOMS_PER_RESIDUE - 1
+        for name, slot in slots.items():
+            table[ONE_TO_INDEX[one], slot] = VDW_RADII[name[0]]
+    return table

@@ -10,7 +10,8 @@ one HIP kernel, ``ops.inter_residue_geometry_backward``); ``backbone_from_dihedr
 differentiable function of the dihedrals, bond angles and bond lengths (``ops.backbone_from_dihedrals_backward``);
 ``frame_aligned_point_error`` is the fused FAPE loss (``ops.fape`` / ``ops.fape_backward``) and ``backbone_frames`` the
 per-residue frames as a differentiable function of the coordinates (``ops.frames_backward``); ``lddt`` is the fused lDDT,
-hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward``).
+hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward``); ``steric_clash`` and
+``peptide_bond_violations`` are the structural-violation terms (``ops.clash`` / ``ops.peptide_bond`` and their backwards).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -350,6 +351,87 @@ def lddt(points, target_points, point_mask=None, groups=None, cutoff=15.0, thres
     if reduction == "point":
         return S / n.clamp(min=1)
     return S.sum(-1) / n.sum(-1).clamp(min=1)
+
+
+class _StericClash(torch.autograd.Function):
+    """ops.clash with ops.clash_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, points, radius, point_mask, groups, link, tolerance, eps):
+        E, n = ops.clash(points, radius, point_mask, groups, link, tolerance=tolerance, eps=eps)
+        # nothing of the forward's arithmetic is kept: the backward kernel recomputes the pairs from the inputs
+        ctx.save_for_backward(points, radius, point_mask, groups, link)
+        ctx.scalars = (tolerance, eps)
+        ctx.dtype = points.dtype
+        ctx.mark_non_differentiable(n)
+        return E, n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_E, _grad_n):
+        points, radius, point_mask, groups, link = ctx.saved_tensors
+        tolerance, eps = ctx.scalars
+        grad = ops.clash_backward(points, radius, grad_E, point_mask, groups, link, tolerance=tolerance, eps=eps)
+        return (grad.to(ctx.dtype),) + (None,) * 6
+
+
+def steric_clash(points, radius, point_mask=None, groups=None, link=None, tolerance=ops.CLASH_TOLERANCE, eps=1e-10,
+                 reduction="point"):
+    """Steric clash energy of ``points`` (B,M,3) with van der Waals ``radius`` (B,M) (AlphaFold 2 suppl. 1.9.11, eq. 46):
+    for every point the sum, over the other points (points outside ``point_mask`` (B,M), points of its own group where
+    ``groups`` (B,M; integers) are given, and points that carry the same non-negative ``link`` (B,M; integers: a covalent
+    bond between two groups) excluded), of ``max(0, radius_i + radius_j - tolerance - |x_i - x_j|)``.  Every clashing pair
+    appears in both points' sums.  ``reduction="point"`` returns ``E`` (B,M); ``"structure"`` returns
+    ``sum_i E_i / max(number of valid points, 1)``, (B,); ``"none"`` returns the kernel's ``(E, n)`` with ``n`` the number
+    of points each point overlaps.
+
+    Differentiable with respect to ``points`` (the radii are constants).  Forward and backward are one fused HIP kernel
+    each (``ops.clash``, ``ops.clash_backward``): nothing of size M^2 is ever built.  Masked points get exact zeros
+    (energy and gradient), and NaN there (missing atoms) never reaches a result.  No double backward."""
+    if reduction not in ("point", "structure", "none"):
+        raise ValueError(f"reduction must be 'point', 'structure' or 'none', got {reduction!r}")
+    E, n = _StericClash.apply(points, radius.detach(), point_mask, groups, link, float(tolerance), float(eps))
+    if reduction == "none":
+        return E, n
+    if reduction == "point":
+        return E
+    B, M = E.shape
+    valid = (point_mask != 0).sum(-1) if point_mask is not None else torch.full((B,), M, device=E.device)
+    return E.sum(-1) / valid.clamp(min=1).to(E.dtype)
+
+
+class _PeptideBond(torch.autograd.Function):
+    """ops.peptide_bond with ops.peptide_bond_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, xyz, junction_mask, next_is_proline, slots, eps, constants):
+        n_slot, ca_slot, c_slot = slots
+        ctx.kwargs = dict(n_slot=n_slot, ca_slot=ca_slot, c_slot=c_slot, eps=eps, **dict(constants))
+        ctx.save_for_backward(xyz, junction_mask, next_is_proline)
+        ctx.dtype = xyz.dtype
+        return ops.peptide_bond(xyz, junction_mask, next_is_proline, **ctx.kwargs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_viol):
+        xyz, junction_mask, next_is_proline = ctx.saved_tensors
+        grad = ops.peptide_bond_backward(xyz, grad_viol, junction_mask, next_is_proline, **ctx.kwargs)
+        return (grad.to(ctx.dtype),) + (None,) * 5
+
+
+def peptide_bond_violations(xyz, junction_mask=None, next_is_proline=None, n_slot=0, ca_slot=1, c_slot=2, eps=1e-10,
+                            **constants):
+    """Peptide-bond violations of ``xyz`` (B,N,A,3) at every junction r -> r+1 (AlphaFold 2 suppl. 1.9.11, eq. 44-45),
+    (B,N,3): how far the bond length |C - N'|, the cosine of the angle CA-C-N' and the cosine of the angle C-N'-CA' lie
+    outside ``tau`` standard deviations around their ideal values -- ``max(0, |value - ideal| - tau * sigma)`` each, with
+    the constants of ``ops.PEPTIDE_BOND`` (``tau=12.0``; any of them may be overridden by keyword).  ``junction_mask``
+    (B,N): entry r is the junction from residue r to residue r+1 (None = all; entry N-1 is ignored); ``next_is_proline``
+    (B,N): residue r+1 is a proline.  Invalid junctions and row N-1 are exact zeros, value and gradient, whatever NaN sits
+    there.  Differentiable with respect to ``xyz``; one HIP kernel forwards (``ops.peptide_bond``) and one backwards
+    (``ops.peptide_bond_backward``).  No double backward."""
+    ops.check_peptide_bond_shapes(xyz, junction_mask, next_is_proline, n_slot, ca_slot, c_slot, eps, **constants)
+    return _PeptideBond.apply(xyz, junction_mask, next_is_proline, (int(n_slot), int(ca_slot), int(c_slot)), float(eps),
+                              tuple(sorted((k, float(v)) for k, v in constants.items())))
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

@@ -1238,6 +1238,186 @@ def lddt_backward(points: torch.Tensor, target_points: torch.Tensor, grad_S: tor
     return out
 
 
+VDW_RADII = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}   # van der Waals radii by element (AlphaFold 2 suppl. 1.9.11)
+CLASH_TOLERANCE = 1.5
+# ideal peptide-bond geometry and its standard deviations (AlphaFold 2 suppl. 1.9.11; Engh & Huber 2001), and the
+# tolerance factor tau: a deviation of up to tau standard deviations is no violation
+PEPTIDE_BOND = dict(l0=1.329, sigma_l=0.014, l0_pro=1.341, sigma_l_pro=0.016, cos_cacn=-0.4473, sigma_cacn=0.0311,
+                    cos_cnca=-0.5203, sigma_cnca=0.0353, tau=12.0)
+PEPTIDE_BOND_CONSTANTS = 12   # PS_PEPTIDE_BOND_CONSTANTS of include/protstruc_hip.h
+
+
+def _is_integer_tensor(t) -> bool:
+    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+
+
+def check_clash_shapes(points, radius, point_mask=None, groups=None, link=None, tolerance=CLASH_TOLERANCE, eps=1e-10,
+                       grad_E=None) -> None:
+    """Shape rules of ``clash`` / ``clash_backward``, on shapes, dtypes, devices and the scalars only (no launch):
+    ValueError.  ``groups`` and ``link`` are integer tensors; ``tolerance`` finite; ``eps`` non-negative and finite."""
+    shape = tuple(points.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
+    B, M = shape[:2]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if M > 2 ** 30:
+        raise ValueError(f"at most 2^30 points per structure, got {M}")
+    _check_float_tensor(points, shape, "points", f"points {shape}")
+    _check_float_tensor(radius, (B, M), "radius", f"points {shape}")
+    if point_mask is not None and tuple(point_mask.shape) != (B, M):
+        raise ValueError(f"point_mask must have shape {(B, M)}, got {tuple(point_mask.shape)}")
+    for name, t in (("groups", groups), ("link", link)):
+        if t is None:
+            continue
+        if tuple(t.shape) != (B, M):
+            raise ValueError(f"{name} must have shape {(B, M)}, got {tuple(t.shape)}")
+        if not _is_integer_tensor(t):
+            raise ValueError(f"{name} must be an integer tensor, got {t.dtype}")
+    if not abs(float(tolerance)) < float("inf"):
+        raise ValueError(f"tolerance must be finite, got {tolerance}")
+    if not (float(eps) >= 0 and float(eps) != float("inf")):
+        raise ValueError(f"eps must be non-negative and finite, got {eps}")
+    if grad_E is not None:
+        _check_float_tensor(grad_E, (B, M), "grad_E", f"points {shape}")
+    _same_device(points, radius=radius, point_mask=point_mask, groups=groups, link=link, grad_E=grad_E)
+
+
+def _clash_operands(points, radius, point_mask, groups, link):
+    return (_f32c(points, "points"), _f32c(radius, "radius"), _u8c(point_mask, "point_mask"), _i32c(groups, "groups"),
+            _i32c(link, "link"))
+
+
+def clash(points: torch.Tensor, radius: torch.Tensor, point_mask: Optional[torch.Tensor] = None,
+          groups: Optional[torch.Tensor] = None, link: Optional[torch.Tensor] = None, *,
+          tolerance: float = CLASH_TOLERANCE, eps: float = 1e-10):
+    """K17.  Steric clash energy per point, fused: ``(E (B,M), n (B,M))`` fp32 with ``E_i`` the sum over the points j
+    that count for point i -- both in ``point_mask`` (None = all), ``j != i``, in another group where ``groups`` (B,M;
+    integers) are given, and not carrying the same non-negative ``link`` (B,M; integers: a covalent bond between groups)
+    -- of ``max(0, radius_i + radius_j - tolerance - sqrt(|x_i - x_j|^2 + eps))``, and ``n_i`` the number of them that
+    overlap.  Every clashing pair appears in both owners' sums.  ``points`` may be the (B, N*A, 3) view of coordinates
+    with the atom mask as ``point_mask`` and the residue index as ``groups``.  Nothing of size M^2 is built; masked
+    points get zeros and NaN there (coordinates or radii) never reaches the result; deterministic
+    (include/protstruc_hip.h)."""
+    check_clash_shapes(points, radius, point_mask, groups, link, tolerance, eps)
+    x, r, pm, gr, lk = _clash_operands(points, radius, point_mask, groups, link)
+    B, M = x.shape[:2]
+    with _on(x.device):
+        if B == 0 or M == 0:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            return torch.zeros(B, M, dtype=torch.float32, device=x.device), torch.zeros(B, M, dtype=torch.float32, device=x.device)
+        E = torch.empty(B, M, dtype=torch.float32, device=x.device)
+        n = torch.empty(B, M, dtype=torch.float32, device=x.device)
+        _launch("ps_clash_f32", _ptr(x), _ptr(r), _ptr(pm), _ptr(gr), _ptr(lk), float(tolerance), float(eps), _ptr(E),
+                _ptr(n), B, M, _stream(x))
+    return E, n
+
+
+def clash_backward(points: torch.Tensor, radius: torch.Tensor, grad_E: torch.Tensor,
+                   point_mask: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None,
+                   link: Optional[torch.Tensor] = None, *, tolerance: float = CLASH_TOLERANCE,
+                   eps: float = 1e-10) -> torch.Tensor:
+    """K18.  Vector-Jacobian product of ``clash`` with respect to ``points`` in one launch that recomputes the pairs:
+    ``grad_points`` (B,M,3) fp32 from the upstream ``grad_E`` (B,M).  Every element is written; masked points get exact
+    zeros and NaN there never reaches the result; the radii get no gradient; deterministic (include/protstruc_hip.h).
+    Keep ``eps > 0``: with ``eps = 0`` two coincident points that count for each other have no derivative (NaN, as under
+    autograd)."""
+    check_clash_shapes(points, radius, point_mask, groups, link, tolerance, eps, grad_E)
+    x, r, pm, gr, lk = _clash_operands(points, radius, point_mask, groups, link)
+    g = _f32c(grad_E, "grad_E")
+    B, M = x.shape[:2]
+    with _on(x.device):
+        if B == 0 or M == 0:
+            return torch.zeros(B, M, 3, dtype=torch.float32, device=x.device)
+        out = torch.empty(B, M, 3, dtype=torch.float32, device=x.device)
+        _launch("ps_clash_backward_f32", _ptr(x), _ptr(r), _ptr(pm), _ptr(gr), _ptr(lk), float(tolerance), float(eps),
+                _ptr(g), _ptr(out), B, M, _stream(x))
+    return out
+
+
+def _peptide_bond_constants(eps, constants):
+    """The twelve floats of the C ABI from ``PEPTIDE_BOND`` overridden by ``constants``; ValueError for an unknown name,
+    a value that is not finite, or a negative sigma, tau or eps."""
+    unknown = set(constants) - set(PEPTIDE_BOND)
+    if unknown:
+        raise ValueError(f"unknown peptide-bond constants {sorted(unknown)}; the names are {sorted(PEPTIDE_BOND)}")
+    k = {name: float(value) for name, value in {**PEPTIDE_BOND, **constants}.items()}
+    k["eps"] = float(eps)
+    for name, value in k.items():
+        if not abs(value) < float("inf"):
+            raise ValueError(f"{name} must be finite, got {value}")
+        if (name.startswith("sigma") or name in ("tau", "eps")) and value < 0:
+            raise ValueError(f"{name} must be non-negative, got {value}")
+    order = ("l0", "sigma_l", "l0_pro", "sigma_l_pro", "cos_cacn", "sigma_cacn", "cos_cnca", "sigma_cnca", "tau", "eps")
+    return [k[name] for name in order] + [0.0] * (PEPTIDE_BOND_CONSTANTS - len(order))
+
+
+def check_peptide_bond_shapes(xyz, junction_mask=None, next_is_proline=None, n_slot: int = 0, ca_slot: int = 1,
+                              c_slot: int = 2, eps=1e-10, grad_viol=None, **constants) -> None:
+    """Shape rules of ``peptide_bond`` / ``peptide_bond_backward``, on shapes, dtypes, devices, slots and the constants
+    only (no launch): ValueError.  The three slots differ; ``constants`` are names of ``PEPTIDE_BOND``."""
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    if not xyz.dtype.is_floating_point:
+        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
+    B, N, A = shape[:3]
+    if B * N > 2 ** 31:
+        raise ValueError(f"at most 2^31 residues per call, got {B * N}")
+    _check_atom_slots(A, n_slot, ca_slot, c_slot)
+    if len({int(n_slot), int(ca_slot), int(c_slot)}) != 3:
+        raise ValueError(f"the N, CA and C slots must differ, got {(n_slot, ca_slot, c_slot)}")
+    for name, t in (("junction_mask", junction_mask), ("next_is_proline", next_is_proline)):
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{name} must have shape {(B, N)} to match xyz {shape}, got {tuple(t.shape)}")
+    _peptide_bond_constants(eps, constants)
+    if grad_viol is not None:
+        _check_float_tensor(grad_viol, (B, N, 3), "grad_viol", f"xyz {shape}")
+    _same_device(xyz, junction_mask=junction_mask, next_is_proline=next_is_proline, grad_viol=grad_viol)
+
+
+def peptide_bond(xyz: torch.Tensor, junction_mask: Optional[torch.Tensor] = None,
+                 next_is_proline: Optional[torch.Tensor] = None, *, n_slot: int = 0, ca_slot: int = 1, c_slot: int = 2,
+                 eps: float = 1e-10, **constants) -> torch.Tensor:
+    """K19.  Peptide-bond violations at every junction r -> r+1: ``viol`` (B,N,3) fp32 = how far the bond length
+    |C - N'|, the cosine of the angle CA-C-N' and the cosine of the angle C-N'-CA' lie outside ``tau`` standard deviations
+    around their ideal values (``PEPTIDE_BOND``; any of its names may be overridden by keyword).  ``junction_mask`` (B,N):
+    entry r is the junction from residue r to r+1 (None = all valid; entry N-1 is ignored); ``next_is_proline`` (B,N):
+    residue r+1 is a proline, which has its own ideal bond length (None = none).  Invalid junctions and row N-1 get exact
+    zeros, whatever NaN sits there (include/protstruc_hip.h)."""
+    check_peptide_bond_shapes(xyz, junction_mask, next_is_proline, n_slot, ca_slot, c_slot, eps, **constants)
+    k = (ctypes.c_float * PEPTIDE_BOND_CONSTANTS)(*_peptide_bond_constants(eps, constants))   # a host array
+    x, jm, pro = _f32c(xyz, "xyz"), _u8c(junction_mask, "junction_mask"), _u8c(next_is_proline, "next_is_proline")
+    B, N, A = x.shape[:3]
+    with _on(x.device):
+        if B == 0 or N == 0:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            return torch.zeros(B, N, 3, dtype=torch.float32, device=x.device)
+        viol = torch.empty(B, N, 3, dtype=torch.float32, device=x.device)
+        _launch("ps_peptide_bond_f32", _ptr(x), _ptr(jm), _ptr(pro), int(n_slot), int(ca_slot), int(c_slot), k, _ptr(viol),
+                B, N, A, _stream(x))
+    return viol
+
+
+def peptide_bond_backward(xyz: torch.Tensor, grad_viol: torch.Tensor, junction_mask: Optional[torch.Tensor] = None,
+                          next_is_proline: Optional[torch.Tensor] = None, *, n_slot: int = 0, ca_slot: int = 1,
+                          c_slot: int = 2, eps: float = 1e-10, **constants) -> torch.Tensor:
+    """K20.  Vector-Jacobian product of ``peptide_bond`` in one launch: ``grad_xyz`` (B,N,A,3) fp32 from the upstream
+    ``grad_viol`` (B,N,3).  Every element is written: slots other than N, CA and C, and the atoms of invalid junctions,
+    are exact zeros, and neither coordinates nor ``grad_viol`` are read at an invalid junction; no atomics, deterministic
+    (include/protstruc_hip.h)."""
+    check_peptide_bond_shapes(xyz, junction_mask, next_is_proline, n_slot, ca_slot, c_slot, eps, grad_viol, **constants)
+    k = (ctypes.c_float * PEPTIDE_BOND_CONSTANTS)(*_peptide_bond_constants(eps, constants))
+    x, jm, pro = _f32c(xyz, "xyz"), _u8c(junction_mask, "junction_mask"), _u8c(next_is_proline, "next_is_proline")
+    g = _f32c(grad_viol, "grad_viol")
+    B, N, A = x.shape[:3]
+    with _on(x.device):
+        if B == 0 or N == 0:
+            return torch.zeros(B, N, A, 3, dtype=torch.float32, device=x.device)
+        out = torch.empty(B, N, A, 3, dtype=torch.float32, device=x.device)
+        _launch("ps_peptide_bond_backward_f32", _ptr(x), _ptr(jm), _ptr(pro), int(n_slot), int(ca_slot), int(c_slot), k,
+                _ptr(g), _ptr(out), B, N, A, _stream(x))
+    return out
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -43,6 +43,41 @@ def _default_device() -> torch.device:
     return torch.device("cpu")
 
 
+def valid_junctions(present: torch.Tensor, chain_idx: torch.Tensor, residue_idx: Optional[torch.Tensor] = None,
+                    n_slot: int = 0, ca_slot: int = 1, c_slot: int = 2) -> torch.Tensor:
+    """(B,N) bool, entry r = the junction from residue r to residue r+1 is a peptide bond: C and CA of r and N and CA of
+    r+1 are ``present`` (B,N,A; a residue outside the residue mask has no atom present), both residues carry the same
+    ``chain_idx`` (NaN, the padding, equals nothing) and, where ``residue_idx`` (B,N) is given, r+1 follows r.  Entry N-1
+    is False.  Plain tensor arithmetic on the inputs' device."""
+    B, N = present.shape[:2]
+    ok = torch.zeros(B, N, dtype=torch.bool, device=present.device)
+    if N < 2:
+        return ok
+    here = present[:, :-1, c_slot] & present[:, :-1, ca_slot]
+    there = present[:, 1:, n_slot] & present[:, 1:, ca_slot]
+    ok[:, :-1] = here & there & (chain_idx[:, :-1] == chain_idx[:, 1:])
+    if residue_idx is not None:
+        ok[:, :-1] &= (residue_idx[:, 1:] - residue_idx[:, :-1]) == 1
+    return ok
+
+
+def clash_links(junctions: torch.Tensor, A: int, is_cys: Optional[torch.Tensor] = None, n_slot: int = 0, c_slot: int = 2,
+                sg_slot: int = 5) -> torch.Tensor:
+    """(B, N*A) int32 ``link`` of ``geometry.steric_clash`` for all atom slots: C of residue r and N of residue r+1 share
+    the id r at every valid junction (the peptide bond is no clash), every SG of a cysteine (``is_cys`` (B,N) bool)
+    carries the id N (nor is a disulphide bridge), every other atom -1."""
+    B, N = junctions.shape
+    link = torch.full((B, N, A), -1, dtype=torch.int32, device=junctions.device)
+    ids = torch.arange(N, dtype=torch.int32, device=junctions.device).expand(B, N)
+    none = torch.full_like(ids, -1)
+    link[:, :, c_slot] = torch.where(junctions, ids, none)
+    if N > 1:
+        link[:, 1:, n_slot] = torch.where(junctions[:, :-1], ids[:, :-1], none[:, :-1])
+    if is_cys is not None and sg_slot < A:
+        link[:, :, sg_slot] = torch.where(is_cys, torch.full_like(ids, N), none)
+    return link.reshape(B, N * A)
+
+
 class StructureBatch:
     """A padded batch of protein structures: ``xyz (B, N_res, N_atom, 3)`` + masks."""
 
@@ -418,6 +453,107 @@ class StructureBatch:
         if per_residue:
             return S / n.clamp(min=1)
         return S.sum(-1) / n.sum(-1).clamp(min=1)
+
+    # ------------------------------------------------------------------ structural violations
+    def _present_atoms(self) -> torch.Tensor:
+        """(B,N,A) bool: the atom is there and its residue is in the residue mask."""
+        B, N, A = self.xyz.shape[:3]
+        present = self.residue_mask[:, :, None].expand(B, N, A)
+        if self.atom_mask is not None:
+            present = present & (self.atom_mask != 0)
+        return present
+
+    def _valid_junctions(self) -> torch.Tensor:
+        return valid_junctions(self._present_atoms(), self.chain_idx,
+                               None if self.residue_idx is None else _always_tensor(self.residue_idx).to(self.device))
+
+    def _atom_slots(self, atoms) -> List[int]:
+        A = self.max_n_atoms_per_residue
+        if isinstance(atoms, str) and atoms == "all":
+            return list(range(A))
+        for atom in atoms:
+            if not ATOM.is_valid(atom):
+                raise ValueError(f"Atom {atom} is not valid.")
+        slots = sorted({int(ATOM[a]) for a in atoms})
+        if not slots or slots[-1] >= A:
+            raise ValueError(f"atoms {tuple(atoms)} do not fit the {A} atom slots of this batch")
+        return slots
+
+    def steric_clashes(self, atoms="all", tolerance: float = 1.5, radii: Optional[torch.Tensor] = None,
+                       per_residue: bool = True) -> torch.Tensor:
+        """Steric clash energy (``geometry.steric_clash``; AlphaFold 2 suppl. 1.9.11) between the named ``atoms`` of
+        different residues (``atoms="all"``: every atom slot): per residue, (B,N), the sum over the residue's atoms
+        (``per_residue=True``), or per structure, (B,), the mean over the atoms that take part.  Two atoms clash where
+        they are closer than the sum of their van der Waals radii minus ``tolerance``; every clashing pair counts for
+        both of its atoms.  The radii come from the sequence (``general.vdw_radius_table``) or from ``radii`` (B,N,A);
+        a batch without a sequence knows the elements of N, CA, C, O and CB only, so any other selection needs ``radii``
+        (ValueError).  Atoms without a radius (0) take no part.  The peptide bond C(r) - N(r+1) at a valid junction is no
+        clash, nor are two cysteine SG atoms (a disulphide bridge).  The points reach the kernel as the (B, N*A, 3) view of
+        the coordinates with the selection folded into the point mask and the residue index as the group -- no gather.
+        Differentiable with respect to this batch's coordinates where they require grad (HIP kernels forwards and
+        backwards); NaN coordinates of missing atoms never reach the energy or the gradient."""
+        from . import geometry
+        from .general import vdw_radius_table
+        from .pdb import ONE_TO_INDEX
+
+        B, N, A = self.xyz.shape[:3]
+        slots = self._atom_slots(atoms)
+        seq_idx = None if self.seq is None or self.chain_ids is None else self.get_seq_idx()
+        if radii is not None:
+            radius = _always_tensor(radii).to(device=self.device, dtype=torch.float32)
+            if tuple(radius.shape) != (B, N, A):
+                raise ValueError(f"radii must have shape {(B, N, A)}, got {tuple(radius.shape)}")
+        else:
+            table = vdw_radius_table().to(self.device)
+            if seq_idx is None and slots[-1] > int(ATOM.CB):
+                raise ValueError("without a sequence only the elements of N, CA, C, O and CB are known: pass `radii` "
+                                 "(B,N,A), or restrict `atoms` to those five")
+            if A > table.shape[1] and slots[-1] >= table.shape[1]:
+                raise ValueError(f"the radius table covers {table.shape[1]} atom slots; pass `radii` for {A}")
+            rows = table[seq_idx] if seq_idx is not None else table[ONE_TO_INDEX["X"]].expand(B, N, -1)
+            radius = torch.zeros(B, N, A, dtype=torch.float32, device=self.device)
+            width = min(A, table.shape[1])
+            radius[:, :, :width] = rows[:, :, :width]
+        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+        chosen[slots] = True
+        takes_part = self._present_atoms() & chosen & (radius > 0)      # NaN radii compare false
+        groups = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
+        is_cys = None if seq_idx is None else seq_idx == ONE_TO_INDEX["C"]
+        link = clash_links(self._valid_junctions(), A, is_cys)
+        E, _ = geometry.steric_clash(self.xyz.reshape(B, N * A, 3), radius.reshape(B, N * A), takes_part.reshape(B, N * A),
+                                     groups, link, tolerance=tolerance, reduction="none")
+        if per_residue:
+            return E.reshape(B, N, A).sum(-1)
+        return E.sum(-1) / takes_part.reshape(B, N * A).sum(-1).clamp(min=1)
+
+    def peptide_bond_violations(self, **constants) -> torch.Tensor:
+        """Peptide-bond violations at every junction r -> r+1, (B,N,3): bond length |C - N'|, cos of CA-C-N', cos of
+        C-N'-CA' (``geometry.peptide_bond_violations``; ``tau=12.0`` and the other constants of ``ops.PEPTIDE_BOND`` by
+        keyword).  A junction is valid where both residues are in the residue mask and of the same chain, C, CA, N' and CA'
+        are present and, where ``residue_idx`` is given, the two residues are consecutive; invalid junctions and the last
+        row are exact zeros.  Prolines (from the sequence, where there is one) have their own ideal bond length.
+        Differentiable with respect to this batch's coordinates where they require grad."""
+        from . import geometry
+        from .pdb import ONE_TO_INDEX
+
+        next_is_proline = None
+        if self.seq is not None and self.chain_ids is not None:
+            next_is_proline = torch.roll(self.get_seq_idx() == ONE_TO_INDEX["P"], -1, dims=1)   # entry N-1 is ignored
+        return geometry.peptide_bond_violations(self.xyz, self._valid_junctions(), next_is_proline, int(ATOM.N),
+                                                int(ATOM.CA), int(ATOM.C), **constants)
+
+    def structural_violation_loss(self, tolerance: float = 1.5, tau: float = 12.0) -> torch.Tensor:
+        """The structural-violation loss of AlphaFold 2 (suppl. 1.9.11, without the within-residue term) per structure,
+        (B,): the mean over the valid junctions of each of the three peptide-bond violations
+        (:meth:`peptide_bond_violations`), plus the mean clash energy per atom (:meth:`steric_clashes`; every atom slot
+        where the batch has a sequence, N, CA, C, O and CB where it has none).  Differentiable with respect to this
+        batch's coordinates where they require grad -- HIP kernels on both passes -- so also with respect to the angles
+        the coordinates were built from (:meth:`from_backbone_dihedrals`)."""
+        viol = self.peptide_bond_violations(tau=tau)
+        junctions = self._valid_junctions().sum(-1).clamp(min=1)
+        has_seq = self.seq is not None and self.chain_ids is not None
+        atoms = "all" if has_seq else tuple(a for a in ("N", "CA", "C", "O", "CB") if int(ATOM[a]) < self.max_n_atoms_per_residue)
+        return viol.sum(dim=(1, 2)) / junctions + self.steric_clashes(atoms=atoms, tolerance=tolerance, per_residue=False)
 
     # ------------------------------------------------------------------ A6-A8 inter-residue angles
     @staticmethod

@@ -7,9 +7,7 @@ profiles/fape_time.json and profiles/fape_error.json.
 Shapes: B = 128, N = 512 with the backbone atoms as points (M = 1536) -- timed twice, as the gathered (B, 1536, 3) tensor
 and as the (B, 7680, 3) view of all 15 slots with the other twelve masked -- and B = 16, N = 512 with all 15 slots under a
 p = 0.9 atom mask (M = 7680 passed, ~6950 valid).
-The orchestrator never touches the GPU itself: every GPU step is a fresh child process of this file under its own
-``timeout``, and the steps are chained -- the first one that fails, faults or runs out of time ends the run, and nothing
-more is started on the card.
+Each step below runs as a child process of this file under its own ``timeout``; the first to fail ends the run (tools/steps.py).
 
   events  HIP events around each call (3 warm-ups, median / min of 20): forward, backward (all three gradients, the frame
           side alone, the point side alone), K4 and its backward
@@ -22,16 +20,13 @@ Reported per shape: the times, the ratio to composed torch, and pairs per second
 quotes for K3 (2.08 ns per wave instruction per SIMD on 256 CUs x 4 SIMDs), with the instructions per pair counted in the
 kernels' inner loops (FWD_VALU_PER_PAIR, BWD_*_VALU_PER_PAIR below).
 """
-import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.steps import kernel_stats, largest_batch_that_fits, main, timed
 
 SHAPES = [(128, 512, 3), (16, 512, 15)]       # B, N, atom slots used as points (composed torch and the trace)
 # the timed calls: (name, B, N, slots used, points passed as the 15-slot view + mask / gathered without a mask)
@@ -69,20 +64,6 @@ def operands(xyz, target, atom_mask, gather=0):
     trot, ttrans = ops.frames(target, 0, 1, 2, 1)
     return ([rot, trans, xyz.reshape(B, N * A, 3), trot, ttrans, target.reshape(B, N * A, 3)],
             None if atom_mask is None else atom_mask.reshape(B, N * A))
-
-
-def timed(fn, warmup=3, reps=20):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); e1.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3)
-    ts.sort()
-    return {"median_us": ts[len(ts) // 2], "min_us": ts[0], "reps": reps, "warmup": warmup}
 
 
 def step_events(outdir):
@@ -129,34 +110,25 @@ def step_torch(outdir):
     from tests import fape_ref as R
     out = []
     for B, N, A in SHAPES:
-        b, entry = B, {"B": B, "N": N, "M": N * A, "points": "the first A slots gathered, every one of them valid (no mask)", "batch": 0}
-        while b >= 1:
-            try:
-                torch.cuda.synchronize()
-                torch.cuda.empty_cache()
-                torch.cuda.reset_peak_memory_stats()
-                before = torch.cuda.memory_allocated()
-                xyz, target, atom_mask = inputs(b, N, A)
-                # composed torch gathers the valid slots first: it has no use for masked points
-                x, t = xyz[:, :, :A].contiguous(), target[:, :, :A].contiguous()
-                args = [a.clone() for a in operands(x, t, atom_mask[:, :, :A].contiguous())[0]]
-                leaves = [a.requires_grad_(True) for a in args[:3]]
+        def measure(b):
+            xyz, target, atom_mask = inputs(b, N, A)
+            # composed torch gathers the valid slots first: it has no use for masked points
+            x, t = xyz[:, :, :A].contiguous(), target[:, :, :A].contiguous()
+            args = [a.clone() for a in operands(x, t, atom_mask[:, :, :A].contiguous())[0]]
+            leaves = [a.requires_grad_(True) for a in args[:3]]
 
-                def both():
-                    loss, _ = R.fape(*leaves, *args[3:])
-                    return torch.autograd.grad(loss.sum(), leaves)
+            def both():
+                loss, _ = R.fape(*leaves, *args[3:])
+                return torch.autograd.grad(loss.sum(), leaves)
 
-                def forward():
-                    with torch.no_grad():
-                        return R.fape(*args)
+            def forward():
+                with torch.no_grad():
+                    return R.fape(*args)
 
-                entry.update(batch=b, forward=timed(forward, 2, 5), forward_and_backward=timed(both, 2, 5),
-                             peak_bytes_allocated=torch.cuda.max_memory_allocated() - before, measured_at_full_batch=b == B)
-                break
-            except torch.cuda.OutOfMemoryError:
-                xyz = target = atom_mask = x = t = args = leaves = None
-                torch.cuda.empty_cache()
-                b //= 2
+            return {"forward": timed(forward, 2, 5), "forward_and_backward": timed(both, 2, 5)}
+
+        entry = {"B": B, "N": N, "M": N * A, "points": "the first A slots gathered, every one of them valid (no mask)",
+                 **largest_batch_that_fits(B, measure)}
         out.append(entry)
         print(json.dumps(entry), flush=True)
     with open(os.path.join(outdir, "fape_time_torch.json"), "w") as f:
@@ -196,46 +168,25 @@ STEPS = {"events": step_events, "trace": step_trace, "torch": step_torch, "error
 
 
 def kernel_trace_times(tracedir):
-    """kernel name -> {calls, average_us} from rocprofv3's kernel_stats csv (wherever under ``tracedir`` it wrote it)."""
+    """kernel name -> {calls, average_us} from rocprofv3's kernel statistics under ``tracedir``, in either of the column
+    spellings rocprofv3 has used."""
     out = {}
-    for path in glob.glob(os.path.join(tracedir, "**", "*kernel_stats.csv"), recursive=True):
-        with open(path, newline="") as f:
-            for row in csv.DictReader(f):
-                row = {k.lower(): v for k, v in row.items()}
-                name = row.get("name", "")
-                for key in ("k_fape_forward", "k_fape_finish", "k_fape_backward", "k4_frames"):
-                    if key + "(" in name or name.endswith(key):
-                        calls = int(row.get("total_calls") or row.get("calls"))
-                        total_ns = float(row.get("total_duration") or row.get("totaldurationns"))
-                        out[key] = {"calls": calls, "average_us": total_ns / calls / 1e3}
+    header, *rows = kernel_stats(tracedir) or [[]]
+    for row in (dict(zip(header, r)) for r in rows):
+        name = row.get("name", "")
+        for key in ("k_fape_forward", "k_fape_finish", "k_fape_backward", "k4_frames"):
+            if key + "(" in name or name.endswith(key):
+                calls = int(row.get("total_calls") or row.get("calls"))
+                total_ns = float(row.get("total_duration") or row.get("totaldurationns"))
+                out[key] = {"calls": calls, "average_us": total_ns / calls / 1e3}
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--outdir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--step", choices=sorted(STEPS))
-    args = ap.parse_args()
-    os.makedirs(args.outdir, exist_ok=True)
-    if args.step:
-        import torch
-        assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to report without one"
-        STEPS[args.step](args.outdir)
-        return
-    me = [sys.executable, os.path.abspath(__file__), "--outdir", args.outdir, "--step"]
-    tracedir = os.path.join(args.outdir, "fape_trace")
-    for step in ("events", "trace", "torch", "errors"):
-        cmd = me + [step]
-        if step == "trace":
-            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tracedir, "-o", "fape", "--"] + cmd
-        cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step])] + cmd
-        print("[fape_time]", " ".join(cmd), flush=True)
-        rc = subprocess.run(cmd, cwd=ROOT).returncode
-        if rc != 0:
-            sys.exit(f"[fape_time] step {step} ended with status {rc}: nothing more is started on the GPU")
-    with open(os.path.join(args.outdir, "fape_time_events.json")) as f:
+def finish(outdir):
+    tracedir = os.path.join(outdir, "fape_trace")
+    with open(os.path.join(outdir, "fape_time_events.json")) as f:
         report = json.load(f)
-    with open(os.path.join(args.outdir, "fape_time_torch.json")) as f:
+    with open(os.path.join(outdir, "fape_time_torch.json")) as f:
         composed = json.load(f)
     report["kernel_trace"] = {"method": "rocprofv3 --kernel-trace --stats over 10 forward + 10 backward calls per shape; the "
                                         "average is over both shapes' launches", **kernel_trace_times(tracedir)}
@@ -254,12 +205,12 @@ def main():
             t = e[key]["median_us"] * 1e-6
             e[key + "_pairs_per_s"] = pairs * sweeps / t
             e[key + "_fraction_of_valu_issue_bound"] = pairs * valu / 64 / WAVE_INSTRUCTIONS_PER_S / t
-    os.remove(os.path.join(args.outdir, "fape_time_events.json"))
-    os.remove(os.path.join(args.outdir, "fape_time_torch.json"))
-    with open(os.path.join(args.outdir, "fape_time.json"), "w") as f:
+    os.remove(os.path.join(outdir, "fape_time_events.json"))
+    os.remove(os.path.join(outdir, "fape_time_torch.json"))
+    with open(os.path.join(outdir, "fape_time.json"), "w") as f:
         json.dump(report, f, indent=1)
     print(json.dumps(report))
 
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, ("events", "trace", "torch", "errors"), STEP_TIMEOUT_S, finish, trace_step="trace", trace_name="fape")

@@ -8,9 +8,7 @@ Shapes: B = 128, M = 512 (one CA per residue) and B = 8, M = 512 * 14 (all atoms
 composed version runs at the largest batch (B, B / 2, ...) that fits and the report says which.  Inputs are those of the
 tests: a centred random walk with 3.8 A steps (for the all-atom shape each residue's 14 atoms are the walk's point plus
 1.5 A of Gaussian scatter) and a prediction 1 A of Gaussian noise away.
-The orchestrator never touches the GPU itself: every GPU step is a fresh child process of this file under its own
-``timeout``, and the steps are chained -- the first one that fails, faults or runs out of time ends the run, and nothing
-more is started on the card.
+Each step below runs as a child process of this file under its own ``timeout``; the first to fail ends the run (tools/steps.py).
 
   events  HIP events around each call (3 warm-ups, median / min of 20)
   trace   the same launches under ``rocprofv3 --kernel-trace --stats``: the kernels' own times, without launch overhead
@@ -23,17 +21,15 @@ v_rcp_f32) retires 16 lanes per cycle per SIMD, on 256 CUs x 4 SIMDs at 2.4 GHz;
 (two square roots, one exponential, T reciprocals), and only the (64-owner wave, column) combinations in which some
 owner counts the column execute them at all -- counted on the host from the first structure's target and scaled by B.
 """
-import argparse
 import csv
-import glob
 import json
 import os
 import shutil
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.steps import kernel_stats, largest_batch_that_fits, main, timed
 
 SHAPES = [("ca", 128, 512, 1), ("all_atoms", 8, 512, 14)]     # name, B, residues, atoms per residue
 STEP_TIMEOUT_S = {"events": 180, "trace": 240, "torch": 300}
@@ -51,20 +47,6 @@ def inputs(B, N, A, seed=1):
     points = target + 1.0 * torch.randn(target.shape, generator=g)
     groups = None if A == 1 else torch.arange(N, dtype=torch.int32).repeat_interleave(A).expand(B, N * A).contiguous()
     return points.cuda(), target.cuda(), None if groups is None else groups.cuda()
-
-
-def timed(fn, warmup=3, reps=20):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); e1.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3)
-    ts.sort()
-    return {"median_us": ts[len(ts) // 2], "min_us": ts[0], "reps": reps, "warmup": warmup}
 
 
 def executed_pair_slots(target, groups, cutoff=15.0):
@@ -124,36 +106,26 @@ def step_torch(outdir):
     from tests import lddt_ref as R
     out = []
     for name, B, N, A in SHAPES:
-        b, entry = B, {"shape": name, "B": B, "M": N * A, "batch": 0}
-        while b >= 1:
-            try:
-                torch.cuda.synchronize()
-                torch.cuda.empty_cache()
-                torch.cuda.reset_peak_memory_stats()
-                before = torch.cuda.memory_allocated()
-                x, t, groups = inputs(b, N, A)
-                leaf = x.clone().requires_grad_(True)
+        def measure(b):
+            x, t, groups = inputs(b, N, A)
+            leaf = x.clone().requires_grad_(True)
 
-                def hard():
-                    with torch.no_grad():
-                        return R.lddt(x, t, None, groups)
+            def hard():
+                with torch.no_grad():
+                    return R.lddt(x, t, None, groups)
 
-                def smooth():
-                    with torch.no_grad():
-                        return R.lddt(x, t, None, groups, smooth=True)
+            def smooth():
+                with torch.no_grad():
+                    return R.lddt(x, t, None, groups, smooth=True)
 
-                def both():
-                    S, _ = R.lddt(leaf, t, None, groups, smooth=True)
-                    return torch.autograd.grad(S.sum(), leaf)
+            def both():
+                S, _ = R.lddt(leaf, t, None, groups, smooth=True)
+                return torch.autograd.grad(S.sum(), leaf)
 
-                entry.update(batch=b, hard_forward=timed(hard, 1, 3), smooth_forward=timed(smooth, 1, 3),
-                             smooth_forward_and_backward=timed(both, 1, 3),
-                             peak_bytes_allocated=torch.cuda.max_memory_allocated() - before, measured_at_full_batch=b == B)
-                break
-            except torch.cuda.OutOfMemoryError:
-                x = t = groups = leaf = None
-                torch.cuda.empty_cache()
-                b //= 2
+            return {"hard_forward": timed(hard, 1, 3), "smooth_forward": timed(smooth, 1, 3),
+                    "smooth_forward_and_backward": timed(both, 1, 3)}
+
+        entry = {"shape": name, "B": B, "M": N * A, **largest_batch_that_fits(B, measure)}
         out.append(entry)
         print(json.dumps(entry), flush=True)
     with open(os.path.join(outdir, "lddt_time_torch.json"), "w") as f:
@@ -163,45 +135,17 @@ def step_torch(outdir):
 STEPS = {"events": step_events, "trace": step_trace, "torch": step_torch}
 
 
-def copy_kernel_stats(tracedir, dest):
-    """rocprofv3's kernel_stats csv (wherever under ``tracedir`` it wrote it), reduced to the lDDT kernels' rows."""
-    for path in glob.glob(os.path.join(tracedir, "**", "*kernel_stats.csv"), recursive=True):
-        with open(path, newline="") as f:
-            rows = list(csv.reader(f))
-        keep = [rows[0]] + [r for r in rows[1:] if any("k_lddt" in c for c in r)]
-        with open(dest, "w", newline="") as f:
-            csv.writer(f).writerows(keep)
-        return True
-    return False
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--outdir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--step", choices=sorted(STEPS))
-    args = ap.parse_args()
-    os.makedirs(args.outdir, exist_ok=True)
-    if args.step:
-        import torch
-        assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to report without one"
-        STEPS[args.step](args.outdir)
-        return
-    me = [sys.executable, os.path.abspath(__file__), "--outdir", args.outdir, "--step"]
-    tracedir = os.path.join(args.outdir, "lddt_trace")
-    for step in ("events", "trace", "torch"):
-        cmd = me + [step]
-        if step == "trace":
-            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tracedir, "-o", "lddt", "--"] + cmd
-        cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step])] + cmd
-        print("[lddt_time]", " ".join(cmd), flush=True)
-        rc = subprocess.run(cmd, cwd=ROOT).returncode
-        if rc != 0:
-            sys.exit(f"[lddt_time] step {step} ended with status {rc}: nothing more is started on the GPU")
-    with open(os.path.join(args.outdir, "lddt_time_events.json")) as f:
+def finish(outdir):
+    tracedir = os.path.join(outdir, "lddt_trace")
+    with open(os.path.join(outdir, "lddt_time_events.json")) as f:
         report = json.load(f)
-    with open(os.path.join(args.outdir, "lddt_time_torch.json")) as f:
+    with open(os.path.join(outdir, "lddt_time_torch.json")) as f:
         composed = {c["shape"]: c for c in json.load(f)}
-    report["kernel_stats"] = "lddt_kernel_stats.csv" if copy_kernel_stats(tracedir, os.path.join(args.outdir, "lddt_kernel_stats.csv")) else None
+    rows = kernel_stats(tracedir)
+    if rows:    # reduced to the lDDT kernels' rows
+        with open(os.path.join(outdir, "lddt_kernel_stats.csv"), "w", newline="") as f:
+            csv.writer(f).writerows(rows[:1] + [r for r in rows[1:] if any("k_lddt" in c for c in r)])
+    report["kernel_stats"] = "lddt_kernel_stats.csv" if rows else None
     shutil.rmtree(tracedir, ignore_errors=True)
     for e in report["shapes"]:
         c = composed[e["shape"]]
@@ -214,12 +158,12 @@ def main():
                 e["smooth_forward"]["median_us"] + e["smooth_backward"]["median_us"])
         t = e["smooth_forward"]["median_us"] * 1e-6
         e["smooth_forward_fraction_of_transcendental_issue_rate"] = e["executed_pair_slots"] * (3 + T) / TRANSCENDENTAL_LANES_PER_S / t
-    os.remove(os.path.join(args.outdir, "lddt_time_events.json"))
-    os.remove(os.path.join(args.outdir, "lddt_time_torch.json"))
-    with open(os.path.join(args.outdir, "lddt_time.json"), "w") as f:
+    os.remove(os.path.join(outdir, "lddt_time_events.json"))
+    os.remove(os.path.join(outdir, "lddt_time_torch.json"))
+    with open(os.path.join(outdir, "lddt_time.json"), "w") as f:
         json.dump(report, f, indent=1)
     print(json.dumps(report))
 
 
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, ("events", "trace", "torch"), STEP_TIMEOUT_S, finish, trace_step="trace", trace_name="lddt")

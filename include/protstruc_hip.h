@@ -713,6 +713,13 @@ int ps_mds_backbone_finish_f32(const float* X, const int* lengths, int B, int L,
  * geometry.kabsch (protstruc.py:880-918, geometry.py:442-480): R[b] (3x3), t[b] (3) minimising the RMSD of
  * R a + t against b over the atoms with atom_mask != 0.  src/dst are (B, n_atoms, 3); dst_is_shared /
  * mask_is_shared = 1 when one target / one mask serves every structure.  Apply with ps_rigid_f32.
+ * The contract, for every selection with at least one atom: R is always a proper rotation (R R^T = I and
+ * det R = +1 to float32 rounding; a mirror-image target gets the best rotation, never the reflection) and
+ * reaches the optimal RMSD.  Where the covariance is rank-deficient (two atoms, collinear atoms) the optimum
+ * is one of a family -- any turn about the line fits as well -- and R is one member of it.  One selected atom,
+ * or coincident selected atoms: R = I exactly and t = b - a (the reference's SVD of the zero matrix).  No
+ * selected atom (an all-zero mask, or n_atoms = 0): R and t are NaN, the reference's 0 / 0.  Atoms with
+ * atom_mask = 0 are never read, so NaN may sit there.  The 3x3 solve is csrc/kabsch_solve.hpp.
  */
 int ps_kabsch_f32(const float* src_xyz, const float* dst_xyz, const uint8_t* atom_mask, float* R, float* t,
                   int B, int n_atoms, int dst_is_shared, int mask_is_shared, void* stream);
@@ -720,6 +727,8 @@ int ps_kabsch_f32(const float* src_xyz, const float* dst_xyz, const uint8_t* ato
 /*
  * Distance of one atom slot of every residue of ONE structure to its nearest query point -- the distance
  * part of StructureBatch.get_topk_nearest_residue_mask (protstruc.py:844-849).  xyz (N,A,3), query (n_query,3).
+ * A NaN query point turns every output NaN, a NaN atom its own output.  n_query = 0 is hipErrorInvalidValue
+ * before any launch (the reference's min over no point raises as well); ops.min_dist_to_points raises ValueError.
  */
 int ps_min_dist_to_points_f32(const float* xyz, const float* query, float* out, int N, int A, int atom,
                               int n_query, void* stream);

@@ -136,7 +136,11 @@ def place_fourth_atom(a, b, c, length, planar, dihedral):
 
 def kabsch(a, b):
     """Rotation (3,3) and translation (3,) minimising the RMSD of ``R a + t`` against ``b`` for point sets
-    (n,3) (reference geometry.py:442-480); evaluated by the batched Kabsch kernel with a batch of one."""
+    (n,3) (reference geometry.py:442-480); evaluated by the batched Kabsch kernel with a batch of one.
+
+    R is always a proper rotation (det +1), also for a mirror-image target.  Two points or collinear points leave a
+    family of optimal rotations and R is one member of it; one point, or coincident points, give R = I and t = b - a;
+    no point gives NaN (``ops.kabsch``)."""
     (a, b), ft = _prep([a, b])
     mask = torch.ones(1, a.shape[0], dtype=torch.bool, device=a.device)
     R, t = ops.kabsch(a.reshape(1, -1, 1, 3).contiguous(), b.reshape(1, -1, 1, 3).contiguous(), mask)

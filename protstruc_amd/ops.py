@@ -1516,33 +1516,43 @@ def affine_(xyz: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torc
     return xyz
 
 
-def rigid(xyz: torch.Tensor, R: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, *,
-          transpose: bool = False, inplace: bool = False) -> torch.Tensor:
-    """x' = R x + t (or R^T x + t).  R: (3,3) | (B,3,3) | (B,N,3,3);  t: (3,) | (B,3) | (B,N,3) | (B,1,3) | (B,N,A,3)."""
-    _require_f32c(xyz, "xyz", "rigid needs a contiguous float32 xyz")
-    B, N, A = xyz.shape[:3]
+def check_rigid_shapes(xyz, R=None, t=None) -> Tuple[int, int]:
+    """Shape rules of ``rigid``, on shapes only (no launch): ValueError.  Returns the kernel's (r_mode, t_mode)."""
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    B, N, A = shape[:3]
     r_mode = t_mode = 0
     if R is not None:
-        R = _f32c(R, "rotation")
         r_mode = {2: 1, 3: 2, 4: 3}.get(R.ndim, -1)
-        ok = R.shape[-2:] == (3, 3) and (r_mode == 1 or (R.shape[0] == B and (r_mode == 2 or R.shape[1] == N)))
+        ok = tuple(R.shape[-2:]) == (3, 3) and (r_mode == 1 or (R.shape[0] == B and (r_mode == 2 or R.shape[1] == N)))
         if r_mode < 0 or not ok:
             raise ValueError(f"rotation must be (3,3), ({B},3,3) or ({B},{N},3,3), got {tuple(R.shape)}")
     if t is not None:
-        t = _f32c(t, "translation")
-        if t.shape == (3,):
+        t_shape = tuple(t.shape)
+        if t_shape == (3,) or t_shape == (1, 3):
             t_mode = 1
-        elif t.shape == (B, 3) or t.shape == (B, 1, 3):
+        elif t_shape == (B, 3) or t_shape == (B, 1, 3):
             t_mode = 2
-        elif t.shape == (B, N, 3):
+        elif t_shape == (B, N, 3):
             t_mode = 3
-        elif t.shape == (B, N, A, 3):
+        elif t_shape == (B, N, A, 3):
             t_mode = 4
-        elif t.shape == (1, 3):
-            t, t_mode = t.reshape(3), 1
         else:
-            raise ValueError(f"translation shape {tuple(t.shape)} does not broadcast against xyz {tuple(xyz.shape)}")
-        t = t.contiguous()
+            raise ValueError(f"translation shape {t_shape} does not broadcast against xyz {shape}")
+    return r_mode, t_mode
+
+
+def rigid(xyz: torch.Tensor, R: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, *,
+          transpose: bool = False, inplace: bool = False) -> torch.Tensor:
+    """x' = R x + t (or R^T x + t).  R: (3,3) | (B,3,3) | (B,N,3,3);  t: (3,) | (1,3) | (B,3) | (B,1,3) | (B,N,3) | (B,N,A,3)."""
+    r_mode, t_mode = check_rigid_shapes(xyz, R, t)
+    _require_f32c(xyz, "xyz", "rigid needs a contiguous float32 xyz")
+    B, N, A = xyz.shape[:3]
+    if R is not None:
+        R = _f32c(R, "rotation")
+    if t is not None:
+        t = _f32c(t, "translation")
     with _on(xyz.device):
         out = xyz if inplace else torch.empty_like(xyz)
         if not (xyz.numel() == 0):   # empty input: nothing to launch (an empty tensor has no device pointer)
@@ -1552,7 +1562,12 @@ def rigid(xyz: torch.Tensor, R: Optional[torch.Tensor] = None, t: Optional[torch
 
 
 def center_of_mass(xyz: torch.Tensor, atom: int = 1) -> torch.Tensor:
-    """(B,3) nanmean over residues of one atom slot."""
+    """(B,3) nanmean over residues of one atom slot, per component (a residue with a NaN y still counts for x and z);
+    NaN where no residue has the component.  Accumulated in double and rounded once."""
+    if xyz.ndim != 4 or xyz.shape[3] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {tuple(xyz.shape)}")
+    if xyz.shape[2]:
+        _check_atom_slots(xyz.shape[2], atom)
     xyz = _f32c(xyz, "xyz")
     B, N, A = xyz.shape[:3]
     with _on(xyz.device):
@@ -1580,33 +1595,77 @@ def frames_to_backbone(rot: torch.Tensor, trans: torch.Tensor, ideal: torch.Tens
     return xyz
 
 
+def check_kabsch_shapes(src, dst, atom_mask) -> Tuple[int, int, bool, bool]:
+    """Shape rules of ``kabsch``, on shapes only (no launch): ValueError.  ``src`` is (B, ..., 3) with n = the product of
+    the middle axes atoms per structure, ``dst`` (B or 1, ..., 3) with the same n, ``atom_mask`` any shape of B n or n
+    entries.  Returns (B, n, one target for all, one mask for all)."""
+    for name, x in (("source", src), ("target", dst)):
+        if x.ndim < 2 or x.shape[-1] != 3:
+            raise ValueError(f"{name} xyz must have shape (batch, ..., 3), got {tuple(x.shape)}")
+    B = src.shape[0]
+    n_atoms = int(np.prod(src.shape[1:-1], dtype=np.int64))
+    if int(np.prod(dst.shape[1:-1], dtype=np.int64)) != n_atoms:
+        raise ValueError(f"source and target must have the same number of atoms per structure, got {tuple(src.shape)} "
+                         f"and {tuple(dst.shape)}")
+    if dst.shape[0] not in (1, B):
+        raise ValueError(f"the target must have the batch size of the source ({B}) or 1, got {dst.shape[0]}")
+    count = atom_mask.numel()
+    if count not in (n_atoms, B * n_atoms):
+        if n_atoms and count and count % n_atoms == 0:
+            raise ValueError(f"atom_mask must have the batch size of the source ({B}) or 1, got {count // n_atoms}")
+        raise ValueError(f"atom_mask must have {n_atoms} entries per structure, got {tuple(atom_mask.shape)} against "
+                         f"source {tuple(src.shape)}")
+    return B, n_atoms, dst.shape[0] == 1 and B > 1, count == n_atoms and B > 1
+
+
 def kabsch(src: torch.Tensor, dst: torch.Tensor, atom_mask: torch.Tensor):
-    """Per-structure optimal (R (B,3,3), t (B,3)) taking ``src`` (B,N,A,3) onto ``dst`` ((B|1),N,A,3) over masked atoms."""
+    """Per-structure optimal (R (B,3,3), t (B,3)) taking ``src`` (B,N,A,3) onto ``dst`` ((B|1),N,A,3) over masked atoms.
+
+    R is always a proper rotation (R R^T = I, det R = +1), whatever the selection: a mirror-image target gets the best
+    rotation, not the reflection.  Where the covariance is rank-deficient (two atoms, collinear atoms) the optimum is a
+    family and R is one member of it, with the optimal RMSD.  One selected atom, or coincident selected atoms: R = I and
+    t = b - a (the reference's result).  No selected atom (an empty mask, or no atoms at all): R and t are NaN, the
+    reference's 0 / 0.  Masked-out atoms are never read (include/protstruc_hip.h)."""
+    B, n_atoms, dst_shared, mask_shared = check_kabsch_shapes(src, dst, atom_mask)
     src = _f32c(src, "source xyz")
     dst = _f32c(dst.to(src.device), "target xyz")
-    B = src.shape[0]
-    n_atoms = src[0].numel() // 3
-    if dst[0].numel() // 3 != n_atoms or dst.shape[0] not in (1, B):
-        raise ValueError("source and target must have the same number of atoms per structure")
-    m = _u8c(atom_mask.to(src.device), "atom_mask").reshape(-1, n_atoms)
-    if m.shape[0] not in (1, B):
-        raise ValueError("atom_mask must have the batch size of the source (or 1)")
+    m = _u8c(atom_mask.to(src.device), "atom_mask")
     dev = src.device
     with _on(dev):
+        if B == 0 or n_atoms == 0:   # nothing to launch (an empty tensor has no device pointer): no atom is selected
+            return (torch.full((B, 3, 3), float("nan"), dtype=torch.float32, device=dev),
+                    torch.full((B, 3), float("nan"), dtype=torch.float32, device=dev))
         R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
         t = torch.empty(B, 3, dtype=torch.float32, device=dev)
         _launch("ps_kabsch_f32", _ptr(src), _ptr(dst), _ptr(m), _ptr(R), _ptr(t), B, n_atoms,
-                int(dst.shape[0] == 1 and B > 1), int(m.shape[0] == 1 and B > 1), _stream(src))
+                int(dst_shared), int(mask_shared), _stream(src))
     return R, t
 
 
+def check_min_dist_shapes(xyz_one, query, atom: int = 1) -> Tuple[int, int, int]:
+    """Shape rules of ``min_dist_to_points``, on shapes only (no launch): ValueError.  ``xyz_one`` is ONE structure
+    (N,A,3), ``query`` (..., 3) with at least one point -- the reference's min over no point raises as well -- and
+    ``atom`` a slot of xyz_one.  Returns (N, A, query points)."""
+    shape = tuple(xyz_one.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"xyz must be one structure of shape (residues, atoms, 3), got {shape}")
+    if query.ndim < 1 or query.shape[-1] != 3:
+        raise ValueError(f"query_xyz must have shape (..., 3), got {tuple(query.shape)}")
+    if query.numel() == 0:
+        raise ValueError("query_xyz holds no point: the nearest of no points is undefined")
+    _check_atom_slots(shape[1], atom)
+    return shape[0], shape[1], query.numel() // 3
+
+
 def min_dist_to_points(xyz_one: torch.Tensor, query: torch.Tensor, atom: int = 1) -> torch.Tensor:
-    """(N,) distance from atom slot ``atom`` of each residue of one structure (N,A,3) to its nearest query point."""
+    """(N,) distance from atom slot ``atom`` of each residue of one structure (N,A,3) to its nearest query point.  A NaN
+    query point turns every entry NaN, a NaN atom its own entry; zero query points raise ValueError."""
+    N, A, n_query = check_min_dist_shapes(xyz_one, query, atom)
     xyz_one = _f32c(xyz_one, "xyz")
     query = _f32c(query.to(xyz_one.device), "query_xyz").reshape(-1, 3)
-    N, A = xyz_one.shape[:2]
     with _on(xyz_one.device):
         out = torch.empty(N, dtype=torch.float32, device=xyz_one.device)
-        _launch("ps_min_dist_to_points_f32", _ptr(xyz_one), _ptr(query), _ptr(out), N, A, int(atom), query.shape[0],
-                _stream(xyz_one))
+        if N:   # no residue: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_min_dist_to_points_f32", _ptr(xyz_one), _ptr(query), _ptr(out), N, A, int(atom), n_query,
+                    _stream(xyz_one))
     return out

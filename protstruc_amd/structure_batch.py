@@ -645,7 +645,12 @@ class StructureBatch:
         coordinates (reference protstruc.py:880-918).  One batched launch instead of the reference's Python
         loop + SVD per structure.  A single-structure target serves the whole batch (the reference's loop
         stops after the first structure in that case and applies its rotation to all).  Returns the
-        rotations (B,3,3) (the reference documents that but returns None)."""
+        rotations (B,3,3) (the reference documents that but returns None).
+
+        Every rotation is a proper one (det +1), so the structures keep their shape whatever the selection.  Two
+        selected atoms or collinear ones leave a family of optimal rotations, of which one is applied; one selected
+        atom moves the structure by b - a without turning it; a structure without a selected atom becomes NaN, as in
+        the reference (``ops.kabsch``)."""
         if target.get_batch_size() != 1 and self.batch_size != target.get_batch_size():
             raise ValueError("Batch size of the two structures must be the same.")
         if atom_mask is None:

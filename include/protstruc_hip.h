@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 13
+#define PS_ABI_VERSION 14
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -561,6 +561,52 @@ int ps_peptide_bond_f32(const float* xyz, const uint8_t* junction_mask, const ui
 int ps_peptide_bond_backward_f32(const float* xyz, const uint8_t* junction_mask, const uint8_t* next_is_proline,
                                  int n_slot, int ca_slot, int c_slot, const float* constants,
                                  const float* grad_viol, float* grad_xyz, int B, int N, int A, void* stream);
+
+/*
+ * K21 (ABI 14) -- backbone hydrogen bonds of DSSP (Kabsch & Sander 1983, with the two-best-partners rule of the DSSP
+ * programs), fused: no (B,N,N) tensor exists.  xyz (B,N,A,3); complete, junction, donor (B,N), one byte each: complete[r]
+ * = residue r has its N, CA, C and O and is in the residue mask; junction[r] = r -> r+1 is a peptide bond between two
+ * complete residues (entry N-1 is ignored and taken as 0); donor[r] =
+ * residue r can donate its amide hydrogen (0 for proline), NULL = every residue.  n_slot, ca_slot, c_slot, o_slot: four
+ * different atom slots in [0, A).  Residue j has an amide hydrogen iff junction[j-1], complete[j] and donor[j]:
+ *   H_j = N_j + (C_{j-1} - O_{j-1}) / |C_{j-1} - O_{j-1}|
+ * For the acceptor C=O of residue i and the donor N-H of residue j, both complete, j with an H, i != j, j != i+1 and
+ * |CA_i - CA_j| < 9:
+ *   E(i,j) = 27.888 (1/d(O_i,N_j) + 1/d(C_i,H_j) - 1/d(O_i,H_j) - 1/d(C_i,N_j))  kcal/mol
+ * and E = -9.9 where one of the four distances is below 0.5.  Energies are not rounded to 0.001.  Every donor keeps its two
+ * lowest energies among those below -0.5, ties to the lower acceptor index: acceptor_idx[b][j][0..1] (int32) and
+ * acceptor_energy[b][j][0..1] (fp32); every acceptor likewise its two best donors: donor_idx[b][i][0..1], donor_energy.
+ * An empty slot holds index -1 and energy 0; every element of the four (B,N,2) outputs is written.  The CA test is taken
+ * in fp32 on the squared distance; the pairs that pass are evaluated in double (the coordinates are fp32 values, so their
+ * differences are exact; H is computed in double) and rounded to fp32 once.  Incomplete residues are compacted away while
+ * a tile is staged: NaN coordinates there never reach arithmetic.  Owner-computes, PS_DSSP_RESIDUE_TILE residues per
+ * workgroup; no atomics, one fixed order per list: bit-for-bit repeatable.  B <= 65535; N <= 2^24; A >= 4.
+ */
+#define PS_DSSP_RESIDUE_TILE 64
+int ps_backbone_hbonds_f32(const float* xyz, const uint8_t* complete, const uint8_t* junction, const uint8_t* donor,
+                           int n_slot, int ca_slot, int c_slot, int o_slot,
+                           int32_t* acceptor_idx, float* acceptor_energy, int32_t* donor_idx, float* donor_energy,
+                           int B, int N, int A, void* stream);
+
+/*
+ * K22 (ABI 14) -- DSSP secondary-structure labels from the kept hydrogen bonds: codes (B,N) int8, indices into "-HBEGITS".
+ * acceptor_idx (B,N,2) int32 as ps_backbone_hbonds_f32 writes it (an index outside [0, N) is no partner); xyz, complete
+ * and junction as there; only the CA slot of xyz is read.  With hb(i,j) = "i is in donor j's kept list" and cont(i,k) =
+ * "junction[i .. i+k-1] are all set":
+ *   n-turn at i (n = 3, 4, 5): cont(i,n) and hb(i,i+n)
+ *   G, H, I on residues i .. i+n-1 where an n-turn sits at both i-1 and i;  T on i+1 .. i+n-1 of any n-turn
+ *   bridge(i,j): |i-j| >= 3, cont(i-1,2), cont(j-1,2) and
+ *     parallel [hb(i-1,j) and hb(j,i+1)] or [hb(j-1,i) and hb(i,j+1)], or
+ *     antiparallel [hb(i,j) and hb(j,i)] or [hb(i-1,j+1) and hb(j-1,i+1)]
+ *   E: residue i has a bridge (i,j) whose neighbour pair -- (i-1,j-1) or (i+1,j+1) for parallel, (i-1,j+1) or (i+1,j-1) for
+ *   antiparallel -- is a bridge of the same type;  B: a bridge and not E;  ladders are not joined across beta-bulges
+ *   S: cont(i-2,4) and the angle between CA_i - CA_{i-2} and CA_{i+2} - CA_i above 70 degrees
+ * The label is the first of H, B, E, G, I, T, S that holds (a pure per-residue priority), else '-'; incomplete residues
+ * get 0.  One workgroup per structure with the lists and flags in LDS, O(N): N <= PS_DSSP_MAX_RESIDUES; B * N <= 2^31.
+ */
+#define PS_DSSP_MAX_RESIDUES 2048
+int ps_dssp_assign(const float* xyz, const uint8_t* complete, const uint8_t* junction, const int32_t* acceptor_idx,
+                   int ca_slot, int8_t* codes, int B, int N, int A, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

@@ -20,6 +20,8 @@
 // 12: ps_lddt_f32 / ps_lddt_backward_f32 (K15 / K16, lDDT per point, hard and smooth, and the smooth form's gradient).
 // 13: ps_clash_f32 / ps_clash_backward_f32 (K17 / K18, steric clash energy per point and its gradient),
 //     ps_peptide_bond_f32 / ps_peptide_bond_backward_f32 (K19 / K20, peptide-bond violations and their gradient).
+// 14: ps_backbone_hbonds_f32 (K21, the two best backbone hydrogen bonds of every residue, DSSP energies),
+//     ps_dssp_assign (K22, DSSP secondary-structure labels from them).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

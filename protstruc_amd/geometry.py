@@ -11,7 +11,9 @@ differentiable function of the dihedrals, bond angles and bond lengths (``ops.ba
 ``frame_aligned_point_error`` is the fused FAPE loss (``ops.fape`` / ``ops.fape_backward``) and ``backbone_frames`` the
 per-residue frames as a differentiable function of the coordinates (``ops.frames_backward``); ``lddt`` is the fused lDDT,
 hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward``); ``steric_clash`` and
-``peptide_bond_violations`` are the structural-violation terms (``ops.clash`` / ``ops.peptide_bond`` and their backwards).
+``peptide_bond_violations`` are the structural-violation terms (``ops.clash`` / ``ops.peptide_bond`` and their backwards);
+``backbone_hbonds`` and ``dssp`` are the DSSP hydrogen bonds and secondary-structure labels (``ops.backbone_hbonds`` /
+``ops.dssp_assign``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -20,6 +22,7 @@ moved to) the GPU; there is no CPU evaluation path.
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -436,6 +439,61 @@ def peptide_bond_violations(xyz, junction_mask=None, next_is_proline=None, n_slo
     ops.check_peptide_bond_shapes(xyz, junction_mask, next_is_proline, n_slot, ca_slot, c_slot, eps, **constants)
     return _PeptideBond.apply(xyz, junction_mask, next_is_proline, (int(n_slot), int(ca_slot), int(c_slot)), float(eps),
                               tuple(sorted((k, float(v)) for k, v in constants.items())))
+
+
+DSSP_CODES = "-HBEGITS"
+DSSP_REDUCED_CODES = "CHE"
+
+
+class BackboneHBonds(NamedTuple):
+    """The two best hydrogen-bond partners of every residue (``backbone_hbonds``), each (B,N,2); -1 / 0 where empty."""
+    acceptor_idx: torch.Tensor      # int32: the residues whose C=O accepts this residue's N-H
+    acceptor_energy: torch.Tensor   # fp32, kcal/mol
+    donor_idx: torch.Tensor         # int32: the residues whose N-H donate to this residue's C=O
+    donor_energy: torch.Tensor
+
+
+def backbone_hbonds(xyz, complete, junction, donor=None, n=0, ca=1, c=2, o=3) -> BackboneHBonds:
+    """The backbone hydrogen bonds of ``xyz`` (B,N,A,3) by the Kabsch-Sander energy of DSSP, with the two-best-partners
+    rule of the DSSP programs: for the C=O of residue i and the N-H of residue j, H placed 1 A from N along the previous
+    residue's O -> C, ``E = 27.888 (1/d(O,N) + 1/d(C,H) - 1/d(O,H) - 1/d(C,N))`` kcal/mol (-9.9 where a distance is below
+    0.5 A); a hydrogen bond is E < -0.5, and every N-H and every C=O keeps its two best.  ``complete`` (B,N): the residue
+    has N, CA, C and O and is in the residue mask; ``junction`` (B,N): r -> r+1 is a peptide bond between two complete
+    residues (``structure_batch.valid_junctions`` ANDed with ``complete`` of both); ``donor`` (B,N): False for proline
+    (None = every residue donates); ``n``, ``ca``, ``c``, ``o``: the atoms' slots.  Energies are not rounded to 0.001 as
+    the DSSP programs do.  One HIP kernel (``ops.backbone_hbonds``); no (B,N,N) tensor is built; not differentiable."""
+    return BackboneHBonds(*ops.backbone_hbonds(xyz, complete, junction, donor, n_slot=n, ca_slot=ca, c_slot=c, o_slot=o))
+
+
+def dssp(xyz, complete, junction, donor=None, reduced=False):
+    """DSSP secondary structure of ``xyz`` (B,N,A,3; N, CA, C, O in slots 0-3), (B,N) int8 indices into ``DSSP_CODES`` =
+    "-HBEGITS" -- or, ``reduced=True``, into ``DSSP_REDUCED_CODES`` = "CHE" (H, G, I -> H; E, B -> E; everything else ->
+    C).  Kabsch & Sander 1983 on the hydrogen bonds of ``backbone_hbonds`` (same ``complete``, ``junction``, ``donor``):
+    n-turns, the helices G / H / I from two consecutive turns, T, bridges and ladders (B / E) and the bend S.  Three
+    simplifications against the DSSP programs: energies are not rounded to 0.001, ladders are not joined across
+    beta-bulges, and the label is a pure per-residue priority H, B, E, G, I, T, S.  Incomplete and padded residues are 0.
+    Two HIP kernels (``ops.backbone_hbonds``, ``ops.dssp_assign``); at most ``ops.DSSP_MAX_RESIDUES`` residues per
+    structure; not differentiable."""
+    acceptor_idx = ops.backbone_hbonds(xyz, complete, junction, donor)[0]
+    codes = ops.dssp_assign(xyz, complete, junction, acceptor_idx)
+    if reduced:
+        table = torch.tensor([0, 1, 2, 2, 1, 1, 0, 0], dtype=torch.int8, device=codes.device)
+        codes = table[codes.long()]
+    return codes
+
+
+def dssp_strings(codes, lengths=None, reduced=False):
+    """The codes of ``dssp`` (B,N) as a list of B ``str`` over ``DSSP_CODES`` (``reduced=True``: over
+    ``DSSP_REDUCED_CODES``), each cut to its entry of ``lengths`` where given."""
+    alphabet = DSSP_REDUCED_CODES if reduced else DSSP_CODES
+    rows = torch.as_tensor(codes).cpu().tolist()
+    if lengths is None:
+        lengths = [len(row) for row in rows]
+    else:
+        lengths = [int(n) for n in torch.as_tensor(lengths).cpu().tolist()]
+        if len(lengths) != len(rows):
+            raise ValueError(f"lengths must have one entry per structure, got {len(lengths)} for {len(rows)}")
+    return ["".join(alphabet[k] for k in row[:n]) for row, n in zip(rows, lengths)]
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

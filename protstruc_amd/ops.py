@@ -1418,6 +1418,86 @@ def peptide_bond_backward(xyz: torch.Tensor, grad_viol: torch.Tensor, junction_m
     return out
 
 
+DSSP_MAX_RESIDUES = 2048   # PS_DSSP_MAX_RESIDUES of include/protstruc_hip.h: the assignment keeps a structure's lists in LDS
+
+
+def check_dssp_shapes(xyz, complete, junction, donor=None, n_slot: int = 0, ca_slot: int = 1, c_slot: int = 2,
+                      o_slot: int = 3, acceptor_idx=None) -> None:
+    """Shape rules of ``backbone_hbonds`` / ``dssp_assign``, on shapes, dtypes, devices and slots only (no launch):
+    ValueError.  The four slots differ; with ``acceptor_idx`` (the assignment) only ``ca_slot`` counts and a structure
+    has at most ``DSSP_MAX_RESIDUES`` residues."""
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    if not xyz.dtype.is_floating_point:
+        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
+    B, N, A = shape[:3]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if N > 2 ** 24:
+        raise ValueError(f"at most 2^24 residues per structure, got {N}")
+    if acceptor_idx is None:
+        if A < 4:
+            raise ValueError(f"xyz needs slots for N, CA, C and O, got {A} atoms per residue")
+        _check_atom_slots(A, n_slot, ca_slot, c_slot, o_slot)
+        if len({int(n_slot), int(ca_slot), int(c_slot), int(o_slot)}) != 4:
+            raise ValueError(f"the N, CA, C and O slots must differ, got {(n_slot, ca_slot, c_slot, o_slot)}")
+    else:
+        _check_atom_slots(A, ca_slot)
+    for name, t in (("complete", complete), ("junction", junction), ("donor", donor)):
+        if t is None and name != "donor":
+            raise ValueError(f"{name} is required")
+        if t is not None and tuple(t.shape) != (B, N):
+            raise ValueError(f"{name} must have shape {(B, N)} to match xyz {shape}, got {tuple(t.shape)}")
+    if acceptor_idx is not None:
+        if N > DSSP_MAX_RESIDUES:
+            raise ValueError(f"at most {DSSP_MAX_RESIDUES} residues per structure, got {N}")
+        if tuple(acceptor_idx.shape) != (B, N, 2) or not _is_integer_tensor(acceptor_idx):
+            raise ValueError(f"acceptor_idx must be an integer tensor of shape {(B, N, 2)}, got "
+                             f"{acceptor_idx.dtype} {tuple(acceptor_idx.shape)}")
+    _same_device(xyz, complete=complete, junction=junction, donor=donor, acceptor_idx=acceptor_idx)
+
+
+def backbone_hbonds(xyz: torch.Tensor, complete: torch.Tensor, junction: torch.Tensor,
+                    donor: Optional[torch.Tensor] = None, *, n_slot: int = 0, ca_slot: int = 1, c_slot: int = 2,
+                    o_slot: int = 3):
+    """K21.  The backbone hydrogen bonds of DSSP, fused: ``(acceptor_idx, acceptor_energy, donor_idx, donor_energy)``, each
+    (B,N,2), int32 indices and fp32 energies in kcal/mol.  ``acceptor_idx[b, j]`` are the two residues whose C=O accepts
+    the N-H of residue j at the lowest Kabsch-Sander energies below -0.5 (ties to the lower index), ``donor_idx[b, i]``
+    the two residues whose N-H donate to the C=O of residue i; an empty slot is index -1 and energy 0.  ``complete`` (B,N):
+    the residue has N, CA, C and O and is in the residue mask; ``junction`` (B,N): r -> r+1 is a peptide bond between two
+    complete residues; ``donor`` (B,N): the residue can donate (False for proline; None = all).  Pairs with CA atoms 9 A
+    or more apart are not evaluated; energies are not rounded to 0.001.  Nothing of size N^2 is built; incomplete residues
+    get empty lists and NaN there never reaches the result; deterministic (include/protstruc_hip.h)."""
+    check_dssp_shapes(xyz, complete, junction, donor, n_slot, ca_slot, c_slot, o_slot)
+    x, cm, jn, dn = _f32c(xyz, "xyz"), _u8c(complete, "complete"), _u8c(junction, "junction"), _u8c(donor, "donor")
+    B, N, A = x.shape[:3]
+    with _on(x.device):
+        idx = [torch.full((B, N, 2), -1, dtype=torch.int32, device=x.device) for _ in range(2)]
+        energy = [torch.zeros(B, N, 2, dtype=torch.float32, device=x.device) for _ in range(2)]
+        if B and N:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_backbone_hbonds_f32", _ptr(x), _ptr(cm), _ptr(jn), _ptr(dn), int(n_slot), int(ca_slot), int(c_slot),
+                    int(o_slot), _ptr(idx[0]), _ptr(energy[0]), _ptr(idx[1]), _ptr(energy[1]), B, N, A, _stream(x))
+    return idx[0], energy[0], idx[1], energy[1]
+
+
+def dssp_assign(xyz: torch.Tensor, complete: torch.Tensor, junction: torch.Tensor, acceptor_idx: torch.Tensor, *,
+                ca_slot: int = 1) -> torch.Tensor:
+    """K22.  DSSP secondary-structure labels from the kept hydrogen bonds: ``codes`` (B,N) int8, indices into
+    ``"-HBEGITS"``.  ``acceptor_idx`` (B,N,2) is ``backbone_hbonds``' first result; ``complete`` and ``junction`` as there;
+    only the CA slot of ``xyz`` is read (the bend S).  Ladders are not joined across beta-bulges and the label is a pure
+    per-residue priority H, B, E, G, I, T, S; incomplete residues get 0.  At most ``DSSP_MAX_RESIDUES`` residues per
+    structure (include/protstruc_hip.h)."""
+    check_dssp_shapes(xyz, complete, junction, ca_slot=ca_slot, acceptor_idx=acceptor_idx)
+    x, cm, jn, acc = _f32c(xyz, "xyz"), _u8c(complete, "complete"), _u8c(junction, "junction"), _i32c(acceptor_idx, "acceptor_idx")
+    B, N, A = x.shape[:3]
+    with _on(x.device):
+        codes = torch.zeros(B, N, dtype=torch.int8, device=x.device)
+        if B and N:
+            _launch("ps_dssp_assign", _ptr(x), _ptr(cm), _ptr(jn), _ptr(acc), int(ca_slot), _ptr(codes), B, N, A, _stream(x))
+    return codes
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -555,6 +555,54 @@ class StructureBatch:
         atoms = "all" if has_seq else tuple(a for a in ("N", "CA", "C", "O", "CB") if int(ATOM[a]) < self.max_n_atoms_per_residue)
         return viol.sum(dim=(1, 2)) / junctions + self.steric_clashes(atoms=atoms, tolerance=tolerance, per_residue=False)
 
+    # ------------------------------------------------------------------ hydrogen bonds and secondary structure
+    def _dssp_inputs(self):
+        """(complete, junction, donor) of ``geometry.backbone_hbonds`` / ``geometry.dssp``: a residue is complete where
+        its N, CA, C and O are present; a junction joins two complete residues (:meth:`_valid_junctions`); where there
+        is a sequence a proline donates no amide hydrogen."""
+        from .pdb import ONE_TO_INDEX
+
+        if self.max_n_atoms_per_residue <= int(ATOM.O):
+            raise ValueError(f"hydrogen bonds need the N, CA, C and O slots; this batch has "
+                             f"{self.max_n_atoms_per_residue} atoms per residue")
+        present = self._present_atoms()
+        complete = present[:, :, int(ATOM.N)] & present[:, :, int(ATOM.CA)] & present[:, :, int(ATOM.C)] & present[:, :, int(ATOM.O)]
+        junction = self._valid_junctions()
+        junction[:, :-1] &= complete[:, :-1] & complete[:, 1:]
+        donor = None
+        if self.seq is not None and self.chain_ids is not None:
+            donor = self.get_seq_idx() != ONE_TO_INDEX["P"]
+        return complete, junction, donor
+
+    def backbone_hbonds(self):
+        """The two best backbone hydrogen-bond partners of every residue by the Kabsch-Sander energy of DSSP
+        (``geometry.backbone_hbonds``): a named tuple ``(acceptor_idx, acceptor_energy, donor_idx, donor_energy)``, each
+        (B,N,2) -- the residues whose C=O accepts this residue's N-H, and the residues whose N-H donate to this residue's
+        C=O, lowest energy first, -1 / 0 where there is none.  A residue takes part where its N, CA, C and O are present and
+        it is in the residue mask; the amide hydrogen needs a valid junction to the residue before (same chain,
+        consecutive, both complete); prolines do not donate where the batch has a sequence.  NaN coordinates of missing
+        atoms never reach the result."""
+        from . import geometry
+
+        complete, junction, donor = self._dssp_inputs()
+        return geometry.backbone_hbonds(self.xyz, complete, junction, donor, int(ATOM.N), int(ATOM.CA), int(ATOM.C),
+                                        int(ATOM.O))
+
+    def secondary_structure(self, reduced: bool = False, as_strings: bool = False):
+        """DSSP secondary structure (``geometry.dssp``; Kabsch & Sander 1983 on :meth:`backbone_hbonds`): (B,N) int8
+        indices into ``geometry.DSSP_CODES`` = "-HBEGITS", or with ``reduced=True`` into ``geometry.DSSP_REDUCED_CODES`` =
+        "CHE" (H, G, I -> H; E, B -> E; everything else -> C); ``as_strings=True`` returns a list of B ``str`` instead,
+        each as long as its structure.  Incomplete and padded residues are 0.  Energies are not rounded to 0.001, ladders
+        are not joined across beta-bulges and the label is a pure per-residue priority, so single residues can differ from
+        the DSSP programs' output."""
+        from . import geometry
+
+        complete, junction, donor = self._dssp_inputs()
+        codes = geometry.dssp(self.xyz, complete, junction, donor, reduced=reduced)
+        if as_strings:
+            return geometry.dssp_strings(codes, self.get_total_lengths(), reduced=reduced)
+        return codes
+
     # ------------------------------------------------------------------ A6-A8 inter-residue angles
     @staticmethod
     def _pairwise_atom_slots(atoms_i: List[str], atoms_j: List[str]):

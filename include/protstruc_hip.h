@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 14
+#define PS_ABI_VERSION 15
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -607,6 +607,31 @@ int ps_backbone_hbonds_f32(const float* xyz, const uint8_t* complete, const uint
 #define PS_DSSP_MAX_RESIDUES 2048
 int ps_dssp_assign(const float* xyz, const uint8_t* complete, const uint8_t* junction, const int32_t* acceptor_idx,
                    int ca_slot, int8_t* codes, int B, int N, int A, void* stream);
+
+/*
+ * K23 (ABI 15) -- solvent-accessible surface area by Shrake & Rupley (1973), fused: no pair list and no (B,M,M) or
+ * (B,M,S) tensor exists.  points (B,M,3); radius (B,M); point_mask (B,M), one byte each, NULL = every point; isolate
+ * (B,M) int32, NULL = none: two points see each other only where their keys are equal (e.g. the chain index, to measure
+ * every chain alone); sphere (S,3): the directions of the test points, a DEVICE array (unit vectors; |u_k| need be 1
+ * only to rounding, and any other length is honoured as given); probe: the solvent radius.  With
+ * R_i = (double)radius_i + (double)probe:
+ *   p_ik = x_i + R_i u_k
+ *   buried(i,k) iff some j != i exists, i and j both in the mask, isolate_i == isolate_j when given, |p_ik - x_j|^2 < R_j^2
+ *   count[b][i] = the number of k that are not buried (int32)      area[b][i] = 4 pi R_i^2 count / S (fp32)
+ * Atoms of the same residue occlude each other: there are no group or link exclusions.  A pair is dropped in fp32 only
+ * where |x_i - x_j|^2 > (R_i + R_j)^2 (1 + 2^-20), which no pair that buries a point satisfies; the pairs that pass are
+ * evaluated in double as q = R_i u_k - (x_j - x_i), q.q < R_j^2 (the coordinates and radii are fp32 values, so the
+ * differences are exact; |u_k|^2 is carried, never taken as 1), and the area is computed in double and rounded once.
+ * Masked points are compacted away while a tile is staged -- NaN coordinates or radii there never reach arithmetic -- and
+ * get count = area = 0.  Owner-computes, PS_SASA_POINT_TILE points per workgroup, a mask of PS_SASA_MAX_SPHERE_POINTS
+ * bits per owner in registers; no atomics: bit-for-bit repeatable.  Any M.  B <= 65535; M <= 2^24; 1 <= S <=
+ * PS_SASA_MAX_SPHERE_POINTS; probe >= 0 and finite.
+ */
+#define PS_SASA_POINT_TILE 64
+#define PS_SASA_MAX_SPHERE_POINTS 256
+int ps_solvent_accessibility_f32(const float* points, const float* radius, const uint8_t* point_mask,
+                                 const int32_t* isolate, const float* sphere, float probe,
+                                 int32_t* count, float* area, int B, int M, int S, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

@@ -22,6 +22,7 @@
 //     ps_peptide_bond_f32 / ps_peptide_bond_backward_f32 (K19 / K20, peptide-bond violations and their gradient).
 // 14: ps_backbone_hbonds_f32 (K21, the two best backbone hydrogen bonds of every residue, DSSP energies),
 //     ps_dssp_assign (K22, DSSP secondary-structure labels from them).
+// 15: ps_solvent_accessibility_f32 (K23, Shrake-Rupley solvent-accessible surface area per point).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

@@ -55,3 +55,21 @@ def vdw_radius_table():
         for name, slot in slots.items():
             table[ONE_TO_INDEX[one], slot] = VDW_RADII[name[0]]
     return table
+
+
+# theoretical maximum solvent accessibility of a residue X in Gly-X-Gly, A^2 (Tien et al. 2013, PLoS ONE 8(11): e80635)
+_MAX_ACCESSIBILITY = dict(A=129.0, R=274.0, N=195.0, D=193.0, C=167.0, E=223.0, Q=225.0, G=104.0, H=224.0, I=197.0,
+                          L=201.0, K=236.0, M=224.0, F=240.0, P=159.0, S=155.0, T=172.0, W=285.0, Y=263.0, V=174.0)
+
+
+def max_accessibility_table():
+    """Theoretical maximum solvent-accessible surface area of every residue type (Tien et al. 2013), A^2: a (21,) float32
+    tensor indexed by ``pdb.ONE_TO_INDEX``; NaN for the unknown type X.  What relative accessibility divides by."""
+    import torch
+
+    from .pdb import ONE_TO_INDEX
+
+    table = torch.full((len(ONE_TO_INDEX),), float("nan"), dtype=torch.float32)
+    for one, value in _MAX_ACCESSIBILITY.items():
+        table[ONE_TO_INDEX[one]] = value
+    return table

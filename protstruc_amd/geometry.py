@@ -496,6 +496,59 @@ def dssp_strings(codes, lengths=None, reduced=False):
     return ["".join(alphabet[k] for k in row[:n]) for row, n in zip(rows, lengths)]
 
 
+class SolventAccessibility(NamedTuple):
+    """Shrake-Rupley accessibility of every point (``solvent_accessibility``), each (B,M); zeros at masked points."""
+    count: torch.Tensor   # int32: the test points of the atom that no other atom buries
+    area: torch.Tensor    # fp32, A^2: 4 pi (radius + probe)^2 count / S
+
+
+def sphere_points(n):
+    """``n`` directions spread over the unit sphere by the golden spiral, an (n,3) float32 CPU tensor: for k = 0 .. n-1
+    ``z = 1 - (2k+1)/n``, ``rho = sqrt(1 - z^2)``, ``phi = k pi (3 - sqrt 5)``, ``u_k = (rho cos phi, rho sin phi, z)``,
+    evaluated in float64 and rounded to float32 once -- so ``|u_k|`` is 1 to float32 rounding only, and everything that
+    uses the table takes it as it is."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"a sphere needs at least one point, got {n}")
+    k = np.arange(n, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / n
+    rho = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return torch.from_numpy(np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1).astype(np.float32))
+
+
+_SPHERES = {}   # (n, device) -> the table on that device
+
+
+def _sphere_on(n: int, device) -> torch.Tensor:
+    key = (n, torch.device(device))
+    table = _SPHERES.get(key)
+    if table is None:
+        table = _SPHERES[key] = sphere_points(n).to(device)
+    return table
+
+
+def solvent_accessibility(points, radius, point_mask=None, isolate=None, probe=1.4, n_points=96, sphere=None) -> SolventAccessibility:
+    """Solvent-accessible surface area of ``points`` (B,M,3) with van der Waals ``radius`` (B,M) by Shrake & Rupley (1973):
+    every atom carries ``n_points`` test points on the sphere of radius ``radius + probe`` around it -- the golden spiral
+    of ``sphere_points``, or the rows of ``sphere`` (S,3; float32 unit vectors) where given -- and a test point is buried
+    where it lies inside that sphere of another atom.  Returns ``(count, area)``, each (B,M): the test points left open
+    (int32) and ``4 pi (radius + probe)^2 count / S`` in A^2.  Points outside ``point_mask`` (B,M) neither occlude nor are
+    measured (zeros; NaN there never reaches a result); with ``isolate`` (B,M; integers) two points see each other only
+    where their keys are equal, which measures every chain, or every residue, alone.  Atoms of one residue occlude each
+    other.  At most ``ops.SASA_MAX_SPHERE_POINTS`` test points per atom.  One HIP kernel (``ops.solvent_accessibility``)
+    that decides in double on the float32 inputs; no (B,M,M) or (B,M,S) tensor is built.  Not differentiable: the
+    result is a count."""
+    if sphere is None:
+        n = int(n_points)
+        if not 1 <= n <= ops.SASA_MAX_SPHERE_POINTS:
+            raise ValueError(f"n_points must lie in 1 .. {ops.SASA_MAX_SPHERE_POINTS}, got {n_points}")
+        ops.check_sasa_shapes(points, radius, point_mask, isolate, None, probe)
+        sphere = _sphere_on(n, points.device)
+    return SolventAccessibility(*ops.solvent_accessibility(points.detach(), radius.detach(), point_mask, isolate, sphere=sphere,
+                                                           probe=float(probe)))
+
+
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):
     """chain_breaks as a (B, L) bool array / tensor ("the chain ends after residue i"), or None.  Accepts a list of
     residue indices (every structure), a list of B such lists, or a (B, L) ((L,) unbatched) boolean array / tensor."""

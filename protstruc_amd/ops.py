@@ -1498,6 +1498,65 @@ def dssp_assign(xyz: torch.Tensor, complete: torch.Tensor, junction: torch.Tenso
     return codes
 
 
+SASA_MAX_SPHERE_POINTS = 256   # PS_SASA_MAX_SPHERE_POINTS of include/protstruc_hip.h: an owner's buried mask lives in registers
+
+
+def check_sasa_shapes(points, radius, point_mask=None, isolate=None, sphere=None, probe=1.4) -> None:
+    """Shape rules of ``solvent_accessibility``, on shapes, dtypes, devices and the scalar only (no launch): ValueError.
+    ``isolate`` is an integer tensor; ``sphere`` a float32 (S,3) table with ``1 <= S <= SASA_MAX_SPHERE_POINTS`` (None is
+    not checked: the layers above build it); ``probe`` non-negative and finite."""
+    shape = tuple(points.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
+    B, M = shape[:2]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if M > 2 ** 24:
+        raise ValueError(f"at most 2^24 points per structure, got {M}")
+    _check_float_tensor(points, shape, "points", f"points {shape}")
+    _check_float_tensor(radius, (B, M), "radius", f"points {shape}")
+    if point_mask is not None and tuple(point_mask.shape) != (B, M):
+        raise ValueError(f"point_mask must have shape {(B, M)}, got {tuple(point_mask.shape)}")
+    if isolate is not None:
+        if tuple(isolate.shape) != (B, M):
+            raise ValueError(f"isolate must have shape {(B, M)}, got {tuple(isolate.shape)}")
+        if not _is_integer_tensor(isolate):
+            raise ValueError(f"isolate must be an integer tensor, got {isolate.dtype}")
+    if sphere is not None:
+        if not isinstance(sphere, torch.Tensor) or sphere.dtype != torch.float32 or sphere.ndim != 2 or sphere.shape[1] != 3:
+            raise ValueError("sphere must be a float32 tensor of shape (S, 3), got "
+                             f"{getattr(sphere, 'dtype', type(sphere).__name__)} {tuple(getattr(sphere, 'shape', ()))}")
+        if not 1 <= sphere.shape[0] <= SASA_MAX_SPHERE_POINTS:
+            raise ValueError(f"sphere must have between 1 and {SASA_MAX_SPHERE_POINTS} directions, got {sphere.shape[0]}")
+    if not (float(probe) >= 0 and float(probe) != float("inf")):
+        raise ValueError(f"probe must be non-negative and finite, got {probe}")
+    _same_device(points, radius=radius, point_mask=point_mask, isolate=isolate, sphere=sphere)
+
+
+def solvent_accessibility(points: torch.Tensor, radius: torch.Tensor, point_mask: Optional[torch.Tensor] = None,
+                          isolate: Optional[torch.Tensor] = None, *, sphere: torch.Tensor, probe: float = 1.4):
+    """K23.  Solvent-accessible surface area by Shrake & Rupley, fused: ``(count (B,M) int32, area (B,M) fp32)``.  Point i
+    carries the test points ``x_i + R_i u_k`` with ``R_i = radius_i + probe`` and ``u`` the rows of ``sphere`` (S,3;
+    fp32 unit vectors, ``S <= SASA_MAX_SPHERE_POINTS``); a test point is buried where it lies inside the sphere of radius
+    ``R_j`` around another point j -- both in ``point_mask`` (None = all) and, where ``isolate`` (B,M; integers) is given,
+    with equal keys.  ``count_i`` is the number of test points that are not buried and ``area_i = 4 pi R_i^2 count_i / S``
+    in A^2.  The decisions are taken in double on the fp32 inputs; nothing of size M^2 or M*S is built; masked points get
+    zeros and NaN there (coordinates or radii) never reaches the result; deterministic (include/protstruc_hip.h)."""
+    if sphere is None:
+        raise ValueError("sphere is required: the (S,3) float32 table of directions (geometry.sphere_points)")
+    check_sasa_shapes(points, radius, point_mask, isolate, sphere, probe)
+    x, r, pm, key = _f32c(points, "points"), _f32c(radius, "radius"), _u8c(point_mask, "point_mask"), _i32c(isolate, "isolate")
+    u = _f32c(sphere, "sphere")
+    B, M = x.shape[:2]
+    with _on(x.device):
+        count = torch.zeros(B, M, dtype=torch.int32, device=x.device)
+        area = torch.zeros(B, M, dtype=torch.float32, device=x.device)
+        if B and M:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_solvent_accessibility_f32", _ptr(x), _ptr(r), _ptr(pm), _ptr(key), _ptr(u), float(probe), _ptr(count),
+                    _ptr(area), B, M, int(u.shape[0]), _stream(x))
+    return count, area
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -479,20 +479,11 @@ class StructureBatch:
             raise ValueError(f"atoms {tuple(atoms)} do not fit the {A} atom slots of this batch")
         return slots
 
-    def steric_clashes(self, atoms="all", tolerance: float = 1.5, radii: Optional[torch.Tensor] = None,
-                       per_residue: bool = True) -> torch.Tensor:
-        """Steric clash energy (``geometry.steric_clash``; AlphaFold 2 suppl. 1.9.11) between the named ``atoms`` of
-        different residues (``atoms="all"``: every atom slot): per residue, (B,N), the sum over the residue's atoms
-        (``per_residue=True``), or per structure, (B,), the mean over the atoms that take part.  Two atoms clash where
-        they are closer than the sum of their van der Waals radii minus ``tolerance``; every clashing pair counts for
-        both of its atoms.  The radii come from the sequence (``general.vdw_radius_table``) or from ``radii`` (B,N,A);
-        a batch without a sequence knows the elements of N, CA, C, O and CB only, so any other selection needs ``radii``
-        (ValueError).  Atoms without a radius (0) take no part.  The peptide bond C(r) - N(r+1) at a valid junction is no
-        clash, nor are two cysteine SG atoms (a disulphide bridge).  The points reach the kernel as the (B, N*A, 3) view of
-        the coordinates with the selection folded into the point mask and the residue index as the group -- no gather.
-        Differentiable with respect to this batch's coordinates where they require grad (HIP kernels forwards and
-        backwards); NaN coordinates of missing atoms never reach the energy or the gradient."""
-        from . import geometry
+    def _atom_points(self, atoms, radii):
+        """What the all-atom sweeps take (:meth:`steric_clashes`, :meth:`solvent_accessibility`): the (B, N*A, 3) view of
+        the coordinates -- no gather --, the radii (B, N*A) from the sequence (``general.vdw_radius_table``) or from
+        ``radii`` (B,N,A), the point mask (B, N*A) with the selection ``atoms`` folded in (present, chosen and with a
+        radius above 0; NaN radii compare false), and the sequence codes (B,N) or None."""
         from .general import vdw_radius_table
         from .pdb import ONE_TO_INDEX
 
@@ -517,14 +508,76 @@ class StructureBatch:
         chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
         chosen[slots] = True
         takes_part = self._present_atoms() & chosen & (radius > 0)      # NaN radii compare false
+        return self.xyz.reshape(B, N * A, 3), radius.reshape(B, N * A), takes_part.reshape(B, N * A), seq_idx
+
+    def steric_clashes(self, atoms="all", tolerance: float = 1.5, radii: Optional[torch.Tensor] = None,
+                       per_residue: bool = True) -> torch.Tensor:
+        """Steric clash energy (``geometry.steric_clash``; AlphaFold 2 suppl. 1.9.11) between the named ``atoms`` of
+        different residues (``atoms="all"``: every atom slot): per residue, (B,N), the sum over the residue's atoms
+        (``per_residue=True``), or per structure, (B,), the mean over the atoms that take part.  Two atoms clash where
+        they are closer than the sum of their van der Waals radii minus ``tolerance``; every clashing pair counts for
+        both of its atoms.  The radii come from the sequence (``general.vdw_radius_table``) or from ``radii`` (B,N,A);
+        a batch without a sequence knows the elements of N, CA, C, O and CB only, so any other selection needs ``radii``
+        (ValueError).  Atoms without a radius (0) take no part.  The peptide bond C(r) - N(r+1) at a valid junction is no
+        clash, nor are two cysteine SG atoms (a disulphide bridge).  The points reach the kernel as the (B, N*A, 3) view of
+        the coordinates with the selection folded into the point mask and the residue index as the group -- no gather.
+        Differentiable with respect to this batch's coordinates where they require grad (HIP kernels forwards and
+        backwards); NaN coordinates of missing atoms never reach the energy or the gradient."""
+        from . import geometry
+        from .pdb import ONE_TO_INDEX
+
+        B, N, A = self.xyz.shape[:3]
+        points, radius, takes_part, seq_idx = self._atom_points(atoms, radii)
         groups = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
         is_cys = None if seq_idx is None else seq_idx == ONE_TO_INDEX["C"]
         link = clash_links(self._valid_junctions(), A, is_cys)
-        E, _ = geometry.steric_clash(self.xyz.reshape(B, N * A, 3), radius.reshape(B, N * A), takes_part.reshape(B, N * A),
-                                     groups, link, tolerance=tolerance, reduction="none")
+        E, _ = geometry.steric_clash(points, radius, takes_part, groups, link, tolerance=tolerance, reduction="none")
         if per_residue:
             return E.reshape(B, N, A).sum(-1)
-        return E.sum(-1) / takes_part.reshape(B, N * A).sum(-1).clamp(min=1)
+        return E.sum(-1) / takes_part.sum(-1).clamp(min=1)
+
+    def solvent_accessibility(self, atoms="all", probe: float = 1.4, n_points: int = 96,
+                              radii: Optional[torch.Tensor] = None, per_residue: bool = True, relative: bool = False,
+                              per_chain: bool = False) -> torch.Tensor:
+        """Solvent-accessible surface area in A^2 (``geometry.solvent_accessibility``; Shrake & Rupley 1973 with
+        ``n_points`` test points per atom and a solvent of radius ``probe``) of the named ``atoms`` (``"all"``: every atom
+        slot): per residue, (B,N), the sum over the residue's atoms (``per_residue=True``), or per atom, (B,N,A).  Only
+        the chosen atoms occlude.  The radii come from the sequence (``general.vdw_radius_table``) or from ``radii``
+        (B,N,A), with the rules of :meth:`steric_clashes`; atoms that are missing or have no radius neither occlude nor
+        are measured (0), and NaN coordinates there never reach the result.  ``relative=True`` divides a residue's area
+        by the theoretical maximum of its type (``general.max_accessibility_table``; Tien et al. 2013): it needs a
+        sequence and ``per_residue`` (ValueError), and residues of type X, masked and padded residues are NaN.
+        ``per_chain=True`` measures every chain alone, as if the others were not there.  Hydrogens are not modelled, as
+        usual for crystal structures.  One HIP kernel; not differentiable."""
+        from . import geometry
+        from .general import max_accessibility_table
+
+        B, N, A = self.xyz.shape[:3]
+        has_seq = self.seq is not None and self.chain_ids is not None
+        if relative and not (has_seq and per_residue):
+            raise ValueError("relative accessibility is per residue and needs a sequence: use per_residue=True on a batch "
+                             "that has one")
+        points, radius, takes_part, seq_idx = self._atom_points(atoms, radii)
+        isolate = None
+        if per_chain:   # the padding's NaN becomes -1; padded atoms are outside the mask anyway
+            isolate = torch.nan_to_num(self.chain_idx.to(torch.float32), nan=-1.0).to(torch.int32).repeat_interleave(A, dim=1)
+        area = geometry.solvent_accessibility(points, radius, takes_part, isolate, probe=probe, n_points=n_points).area
+        area = area.reshape(B, N, A)
+        if not per_residue:
+            return area
+        # summed, and divided, in double and rounded once: a residue's area is as close to the definition as an atom's
+        area = area.sum(-1, dtype=torch.float64)
+        if relative:
+            area = area / max_accessibility_table().to(device=self.device, dtype=torch.float64)[seq_idx]
+            area = torch.where(self.residue_mask, area, torch.full_like(area, float("nan")))
+        return area.to(torch.float32)
+
+    def interface_area(self) -> torch.Tensor:
+        """The surface every residue buries against the other chains, (B,N) A^2:
+        ``solvent_accessibility(per_chain=True) - solvent_accessibility()``, the residue's accessible area in its chain
+        alone less its area in the whole structure.  Non-negative up to rounding and exactly 0 for a structure of one
+        chain; summed over two chains it is the buried surface of their interface."""
+        return self.solvent_accessibility(per_chain=True) - self.solvent_accessibility()
 
     def peptide_bond_violations(self, **constants) -> torch.Tensor:
         """Peptide-bond violations at every junction r -> r+1, (B,N,3): bond length |C - N'|, cos of CA-C-N', cos of

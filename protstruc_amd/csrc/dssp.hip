@@ -25,6 +25,7 @@
 // donor j's kept list"; the bridge partners of i are found from the lists alone -- every bridge (i, j) has j or j - 1 in
 // the list of i or of i + 1, eight candidates -- so the kernel is O(N).
 #include "ps_common.hpp"
+#include "owner_sweep.hpp"   // WAVES, compact_slot and the barrier protocol of staging a tile
 
 #include <math.h>
 
@@ -33,7 +34,6 @@
 namespace {
 
 constexpr int OWNERS = PS_DSSP_RESIDUE_TILE;   // owners per workgroup = lanes per wave
-constexpr int WAVES = 4;
 constexpr int THREADS = OWNERS * WAVES;        // = raw residues staged per tile
 constexpr int ITEM_FLOATS = 20;                // N, CA, C, O (12), index, has_h, H as three doubles (6): five 16-byte reads
 static_assert(OWNERS == PS_WAVE, "one owner per lane");
@@ -83,26 +83,6 @@ __device__ __forceinline__ residue_t load_residue(const float* __restrict__ xyz,
         r.h[2] = (double)r.n.z + d[2] / len;
     }
     return r;
-}
-
-// Inclusive position of this thread's item among the workgroup's valid ones, and their number (as in violation.hip).
-// wave_counts: WAVES ints of LDS.  Two barriers; every thread of the workgroup must call it.
-__device__ __forceinline__ int compact_slot(bool valid, int* wave_counts, int& total) {
-    const unsigned long long ballot = __ballot(valid);
-    const int lane = threadIdx.x & (PS_WAVE - 1), wave = threadIdx.x / PS_WAVE;
-    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
-    __syncthreads();   // the previous tile's readers of wave_counts and of the staged items are done
-    if (lane == 0) wave_counts[wave] = __popcll(ballot);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = wave_counts[w];
-        base += w < wave ? c : 0;
-        total += c;
-    }
-    return base + before;
 }
 
 // Stage residues [m0, m0 + THREADS) of structure b, complete ones only, in index order; returns how many.

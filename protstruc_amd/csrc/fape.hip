@@ -12,13 +12,13 @@
 // waves' sums are added in wave order through LDS.  Owner-computes on both sides of the backward: nothing is saved
 // from the forward, there are no atomics, and every sum has one fixed order, so results repeat bit for bit.
 #include "ps_common.hpp"
+#include "owner_sweep.hpp"   // WAVES, compact_slot and the barrier protocol of staging a tile
 
 #include "../../include/protstruc_hip.h"
 
 namespace {
 
 constexpr int OWNERS = PS_FAPE_FRAME_TILE;   // owners per workgroup = lanes per wave
-constexpr int WAVES = 4;
 constexpr int THREADS = OWNERS * WAVES;      // = raw items staged per tile
 constexpr int POINT_FLOATS = 8;              // x (3), x' (3), 2 of padding: two 16-byte broadcast reads
 constexpr int FRAME_FLOATS = 24;             // R (9), t (3), R' (9), t' (3): six 16-byte broadcast reads
@@ -60,26 +60,6 @@ __device__ __forceinline__ float pair_distance(const frame_t& fp, const frame_t&
     const f3 v = rot_t_apply(ft.r, sub3(xt, ft.t));
     diff = sub3(u, v);
     return sqrt_rn_mk(norm_sq3(diff.x, diff.y, diff.z) + eps);
-}
-
-// Inclusive position of this thread's item among the workgroup's valid ones, and their number.  wave_counts: WAVES ints
-// of LDS.  Two barriers; every thread of the workgroup must call it.
-__device__ __forceinline__ int compact_slot(bool valid, int* wave_counts, int& total) {
-    const unsigned long long ballot = __ballot(valid);
-    const int lane = threadIdx.x & (PS_WAVE - 1), wave = threadIdx.x / PS_WAVE;
-    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
-    __syncthreads();   // the previous tile's readers of wave_counts and of the staged items are done
-    if (lane == 0) wave_counts[wave] = __popcll(ballot);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = wave_counts[w];
-        base += w < wave ? c : 0;
-        total += c;
-    }
-    return base + before;
 }
 
 // Number of non-zero bytes of mask[0 .. n) (n if mask is NULL), the same value in every thread.  scratch: THREADS ints.

@@ -24,6 +24,7 @@
 // accumulated in double: only included pairs reach that add, and a sequential float sum of a hundred terms would lose
 // what the terms themselves carry.
 #include "ps_common.hpp"
+#include "owner_sweep.hpp"   // WAVES, compact_slot and the barrier protocol of staging a tile
 
 #include <math.h>
 
@@ -32,7 +33,6 @@
 namespace {
 
 constexpr int OWNERS = PS_LDDT_POINT_TILE;   // owners per workgroup = lanes per wave
-constexpr int WAVES = 4;
 constexpr int THREADS = OWNERS * WAVES;      // = raw points staged per tile
 constexpr int POINT_FLOATS = 8;              // x (3), x' (3), key, w: two 16-byte broadcast reads
 constexpr int MAX_T = PS_LDDT_MAX_THRESHOLDS;
@@ -49,26 +49,6 @@ struct point_t {
     int key;   // the group, or the point's own index where there are no groups: a pair counts iff the keys differ
     float w;   // dL/dS of the point (backward only)
 };
-
-// Inclusive position of this thread's item among the workgroup's valid ones, and their number (as in fape.hip).
-// wave_counts: WAVES ints of LDS.  Two barriers; every thread of the workgroup must call it.
-__device__ __forceinline__ int compact_slot(bool valid, int* wave_counts, int& total) {
-    const unsigned long long ballot = __ballot(valid);
-    const int lane = threadIdx.x & (PS_WAVE - 1), wave = threadIdx.x / PS_WAVE;
-    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
-    __syncthreads();   // the previous tile's readers of wave_counts and of the staged items are done
-    if (lane == 0) wave_counts[wave] = __popcll(ballot);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = wave_counts[w];
-        base += w < wave ? c : 0;
-        total += c;
-    }
-    return base + before;
-}
 
 // Stage raw points [m0, m0 + THREADS) of structure b, valid ones only, in index order; returns how many.
 __device__ __forceinline__ int stage_points(const float* __restrict__ pts_p, const float* __restrict__ pts_t,

@@ -23,6 +23,7 @@
 // four waves' masks are ORed through LDS and counted.  No pair list, no (B,M,M) or (B,M,S) tensor, no atomics: results
 // repeat bit for bit.
 #include "ps_common.hpp"
+#include "owner_sweep.hpp"   // WAVES, compact_slot and the barrier protocol of staging a tile
 
 #include <math.h>
 
@@ -31,32 +32,11 @@
 namespace {
 
 constexpr int OWNERS = PS_SASA_POINT_TILE;    // owners per workgroup = lanes per wave
-constexpr int WAVES = 4;
 constexpr int THREADS = OWNERS * WAVES;       // = raw points staged per tile
 constexpr int MAX_DIRS = PS_SASA_MAX_SPHERE_POINTS;
 constexpr int WORDS = MAX_DIRS / 32;          // mask registers per owner
 static_assert(OWNERS == PS_WAVE, "one owner per lane");
 static_assert(MAX_DIRS <= THREADS, "one thread stages one direction");
-
-// Inclusive position of this thread's item among the workgroup's valid ones, and their number (as in violation.hip).
-// wave_counts: WAVES ints of LDS.  Two barriers; every thread of the workgroup must call it.
-__device__ __forceinline__ int compact_slot(bool valid, int* wave_counts, int& total) {
-    const unsigned long long ballot = __ballot(valid);
-    const int lane = threadIdx.x & (PS_WAVE - 1), wave = threadIdx.x / PS_WAVE;
-    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
-    __syncthreads();   // the previous tile's readers of wave_counts and of the staged items are done
-    if (lane == 0) wave_counts[wave] = __popcll(ballot);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = wave_counts[w];
-        base += w < wave ? c : 0;
-        total += c;
-    }
-    return base + before;
-}
 
 // Stage raw points [m0, m0 + THREADS) of structure b, valid ones only, in index order; returns how many.  An item is
 // (x, y, z, radius) in `tile` and (raw index, isolate key) in `tags`.

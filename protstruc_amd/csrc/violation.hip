@@ -27,6 +27,7 @@
 // two junctions and writes the residue's whole (A,3) row, so no atomics are needed); a dozen loads and a few hundred
 // flops per lane, evaluated in double for the same reason -- |l - l0| - tau sigma is a difference of small numbers.
 #include "ps_common.hpp"
+#include "owner_sweep.hpp"   // WAVES, compact_slot and the barrier protocol of staging a tile
 
 #include <math.h>
 
@@ -35,7 +36,6 @@
 namespace {
 
 constexpr int OWNERS = PS_CLASH_POINT_TILE;   // owners per workgroup = lanes per wave
-constexpr int WAVES = 4;
 constexpr int THREADS = OWNERS * WAVES;       // = raw points staged per tile
 constexpr int POINT_FLOATS = 8;               // x (3), radius, key, link, w, unused: two 16-byte broadcast reads
 static_assert(OWNERS == PS_WAVE, "one owner per lane");
@@ -47,26 +47,6 @@ struct atom_t {
     int link;   // two points with the same non-negative link never clash; -1 where there are no links
     float w;    // dL/dE of the point (backward only)
 };
-
-// Inclusive position of this thread's item among the workgroup's valid ones, and their number (as in lddt.hip).
-// wave_counts: WAVES ints of LDS.  Two barriers; every thread of the workgroup must call it.
-__device__ __forceinline__ int compact_slot(bool valid, int* wave_counts, int& total) {
-    const unsigned long long ballot = __ballot(valid);
-    const int lane = threadIdx.x & (PS_WAVE - 1), wave = threadIdx.x / PS_WAVE;
-    const int before = __popcll(ballot & ((1ull << lane) - 1ull));
-    __syncthreads();   // the previous tile's readers of wave_counts and of the staged items are done
-    if (lane == 0) wave_counts[wave] = __popcll(ballot);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = wave_counts[w];
-        base += w < wave ? c : 0;
-        total += c;
-    }
-    return base + before;
-}
 
 __device__ __forceinline__ atom_t load_atom(const float* __restrict__ pts, const float* __restrict__ radius,
                                             const int* __restrict__ groups, const int* __restrict__ link,

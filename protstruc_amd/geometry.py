@@ -332,6 +332,11 @@ class _LDDT(torch.autograd.Function):
         return (grad.to(ctx.dtype),) + (None,) * 7
 
 
+def _check_reduction(reduction) -> None:
+    if reduction not in ("point", "structure", "none"):
+        raise ValueError(f"reduction must be 'point', 'structure' or 'none', got {reduction!r}")
+
+
 def lddt(points, target_points, point_mask=None, groups=None, cutoff=15.0, thresholds=ops.LDDT_THRESHOLDS, smooth=False,
          reduction="point", eps=1e-10):
     """lDDT (local distance difference test) of ``points`` (B,M,3) against ``target_points``: for every point the mean,
@@ -349,8 +354,7 @@ def lddt(points, target_points, point_mask=None, groups=None, cutoff=15.0, thres
     Forward and backward are one fused HIP kernel each (``ops.lddt``, ``ops.lddt_backward``): nothing of size M^2 is ever
     built; the reductions are ordinary torch on (B,M) tensors.  Masked points get exact zeros (score and gradient), and NaN
     there (missing atoms) never reaches a result.  The target is a constant; no double backward."""
-    if reduction not in ("point", "structure", "none"):
-        raise ValueError(f"reduction must be 'point', 'structure' or 'none', got {reduction!r}")
+    _check_reduction(reduction)
     S, n = _LDDT.apply(points, target_points.detach(), point_mask, groups, float(cutoff),
                        tuple(float(t) for t in thresholds), bool(smooth), float(eps))
     if reduction == "none":
@@ -395,8 +399,7 @@ def steric_clash(points, radius, point_mask=None, groups=None, link=None, tolera
     Differentiable with respect to ``points`` (the radii are constants).  Forward and backward are one fused HIP kernel
     each (``ops.clash``, ``ops.clash_backward``): nothing of size M^2 is ever built.  Masked points get exact zeros
     (energy and gradient), and NaN there (missing atoms) never reaches a result.  No double backward."""
-    if reduction not in ("point", "structure", "none"):
-        raise ValueError(f"reduction must be 'point', 'structure' or 'none', got {reduction!r}")
+    _check_reduction(reduction)
     E, n = _StericClash.apply(points, radius.detach(), point_mask, groups, link, float(tolerance), float(eps))
     if reduction == "none":
         return E, n

@@ -36,6 +36,10 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _f32c_opt(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    return None if t is None else _f32c(t, name)
+
+
 def _u8c(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
     """A mask as a contiguous one-byte-per-entry tensor for the kernels, which test every byte against zero (C ABI:
     "any non-zero input byte counts as true"): bool and uint8 tensors are passed as they are -- only their address is
@@ -104,6 +108,66 @@ def _check_out(t: Optional[torch.Tensor], shape, name: str, device: Optional[tor
             or not t.is_contiguous() or (device is not None and t.device != device)):
         raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)}"
                          + (f" on {device}" if device is not None else ""))
+
+
+def _is_integer_tensor(t) -> bool:
+    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+
+
+def _check_float_tensor(t, shape, name: str, like: str) -> None:
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)} to match {like}, got {tuple(t.shape)}")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+
+
+def _check_optional(t, shape, name: str, like: str = "", like_shape=None, integer: bool = False) -> None:
+    """An operand that may be None: its shape, a tuple -- the message ends "to match ``like`` ``like_shape``" where those are
+    given -- and, with ``integer``, its dtype."""
+    if t is None:
+        return
+    if tuple(t.shape) != shape:
+        match = f" to match {like}" + ("" if like_shape is None else f" {like_shape}") if like else ""
+        raise ValueError(f"{name} must have shape {shape}{match}, got {tuple(t.shape)}")
+    if integer and not _is_integer_tensor(t):
+        raise ValueError(f"{name} must be an integer tensor, got {t.dtype}")
+
+
+def _xyz_dims(xyz, floating: bool = True) -> Tuple[int, int, int]:
+    """(B, N, A) of (batch, residues, atoms, 3) coordinates, which are of a floating-point type unless ``floating`` is
+    False; ValueError otherwise."""
+    shape = tuple(xyz.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
+    if floating and not xyz.dtype.is_floating_point:
+        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
+    return shape[:3]
+
+
+def _points_dims(points, max_batch: int, max_points: int) -> Tuple[int, int]:
+    """(B, M) of floating-point (batch, points, 3) points within the limits of a launch -- a grid dimension per
+    structure, ``max_points`` (a power of two) points in one; ValueError otherwise."""
+    shape = tuple(points.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
+    B, M = shape[:2]
+    if B > max_batch:
+        raise ValueError(f"at most {max_batch} structures per call, got {B}")
+    if M > max_points:
+        raise ValueError(f"at most 2^{max_points.bit_length() - 1} points per structure, got {M}")
+    if not points.dtype.is_floating_point:
+        raise ValueError(f"points must be a floating-point tensor, got {points.dtype}")
+    return B, M
+
+
+_INF = float("inf")
+
+
+def _check_scalar(value, name: str, rule: str) -> None:
+    """``rule`` is "positive" or "non-negative" (both also finite) or "finite"; NaN passes none of them."""
+    v = float(value)
+    if not (abs(v) < _INF and (rule == "finite" or v > 0 or (v == 0 and rule == "non-negative"))):
+        raise ValueError(f"{name} must be {rule}{'' if rule == 'finite' else ' and finite'}, got {value}")
 
 
 def _row_range(N: int, row_begin: int, row_end: Optional[int], compact: bool):
@@ -549,25 +613,16 @@ def check_inter_residue_geometry_backward_shapes(xyz, grads, atom_mask=None, out
     for key in grads:
         if key not in IRG_GRAD_KEYS:
             raise KeyError(f"{key!r} is not a differentiable plane of inter_residue_geometry (known: {', '.join(IRG_GRAD_KEYS)})")
-    shape = tuple(xyz.shape)
-    if len(shape) != 4 or shape[-1] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
-    if not xyz.dtype.is_floating_point:
-        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
-    B, N, A = shape[:3]
+    B, N, A = _xyz_dims(xyz)
+    shape = (B, N, A, 3)
     if A < 5:
         raise IndexError("inter_residue_geometry needs the N, CA, C, O, CB atom slots")
     if N > IRG_BACKWARD_MAX_N:
         raise ValueError(f"inter_residue_geometry_backward takes at most {IRG_BACKWARD_MAX_N} residues, got {N}")
-    if atom_mask is not None and tuple(atom_mask.shape) != (B, N, A):
-        raise ValueError(f"atom_mask must have shape {(B, N, A)} to match xyz {shape}, got {tuple(atom_mask.shape)}")
+    _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
     for key, g in grads.items():
-        if g is None:
-            continue
-        if tuple(g.shape) != (B, N, N):
-            raise ValueError(f"grads[{key!r}] must have shape {(B, N, N)} to match xyz {shape}, got {tuple(g.shape)}")
-        if not g.dtype.is_floating_point:
-            raise ValueError(f"grads[{key!r}] must be a floating-point tensor, got {g.dtype}")
+        if g is not None:
+            _check_float_tensor(g, (B, N, N), f"grads[{key!r}]", f"xyz {shape}")
     _check_out(out, shape, "out")
 
 
@@ -624,8 +679,7 @@ def check_backbone_from_dihedrals_shapes(dihedrals, chain_idx=None, residue_mask
         raise ValueError(f"dihedrals must have shape (batch, residues, 3) [phi, psi, omega], got {shape}")
     for name, t, want in (("chain_idx", chain_idx, shape[:2]), ("residue_mask", residue_mask, shape[:2]),
                           ("bond_angles", bond_angles, shape), ("bond_lengths", bond_lengths, shape)):
-        if t is not None and tuple(t.shape) != want:
-            raise ValueError(f"{name} must have shape {want} to match dihedrals {shape}, got {tuple(t.shape)}")
+        _check_optional(t, want, name, "dihedrals", shape)
 
 
 def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.Tensor] = None,
@@ -640,10 +694,8 @@ def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.T
         raise ValueError(f"n_slots = {n_slots} leaves no room for {'N, CA, C and CB' if include_cb else 'N, CA, C'}")
     dih = _f32c(dihedrals, "dihedrals")
     _same_device(dih, chain_idx=chain_idx, residue_mask=residue_mask, bond_angles=bond_angles, bond_lengths=bond_lengths)
-    chain = None if chain_idx is None else _f32c(chain_idx, "chain_idx")
-    rmask = _u8c(residue_mask, "residue_mask")
-    ang = None if bond_angles is None else _f32c(bond_angles, "bond_angles")
-    lens = None if bond_lengths is None else _f32c(bond_lengths, "bond_lengths")
+    chain, rmask = _f32c_opt(chain_idx, "chain_idx"), _u8c(residue_mask, "residue_mask")
+    ang, lens = _f32c_opt(bond_angles, "bond_angles"), _f32c_opt(bond_lengths, "bond_lengths")
     B, N = dih.shape[:2]
     dev = dih.device
     with _on(dev):
@@ -658,20 +710,13 @@ def backbone_from_dihedrals(dihedrals: torch.Tensor, chain_idx: Optional[torch.T
 def check_backbone_from_dihedrals_backward_shapes(xyz, grad_xyz, chain_idx=None, residue_mask=None, include_cb=False,
                                                   want_bond_angles=False, want_bond_lengths=False, out=None) -> None:
     """Shape rules of ``backbone_from_dihedrals_backward``, on shapes and dtypes only (no device, no launch): ValueError."""
-    shape = tuple(xyz.shape)
-    if len(shape) != 4 or shape[-1] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
-    if tuple(grad_xyz.shape) != shape:
-        raise ValueError(f"grad_xyz must have shape {shape} to match xyz, got {tuple(grad_xyz.shape)}")
-    for name, t in (("xyz", xyz), ("grad_xyz", grad_xyz)):
-        if not t.dtype.is_floating_point:
-            raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
-    B, N, A = shape[:3]
+    B, N, A = _xyz_dims(xyz)
+    shape = (B, N, A, 3)
+    _check_float_tensor(grad_xyz, shape, "grad_xyz", "xyz")
     if A < (5 if include_cb else 3):
         raise ValueError(f"{A} atom slots leave no room for {'N, CA, C and CB' if include_cb else 'N, CA, C'}")
-    for name, t in (("chain_idx", chain_idx), ("residue_mask", residue_mask)):
-        if t is not None and tuple(t.shape) != (B, N):
-            raise ValueError(f"{name} must have shape {(B, N)} to match xyz {shape}, got {tuple(t.shape)}")
+    _check_optional(chain_idx, (B, N), "chain_idx", "xyz", shape)
+    _check_optional(residue_mask, (B, N), "residue_mask", "xyz", shape)
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 3:
             raise ValueError("out must be a (grad_dihedrals, grad_bond_angles, grad_bond_lengths) triple (None where not wanted)")
@@ -697,9 +742,7 @@ def backbone_from_dihedrals_backward(xyz: torch.Tensor, grad_xyz: torch.Tensor, 
     outs = list(out) if out is not None else [None, None, None]
     _same_device(xyz, grad_xyz=grad_xyz, chain_idx=chain_idx, residue_mask=residue_mask,
                  **{f"out[{k}]": t for k, t in enumerate(outs)})
-    gx = _f32c(grad_xyz, "grad_xyz")
-    chain = None if chain_idx is None else _f32c(chain_idx, "chain_idx")
-    rmask = _u8c(residue_mask, "residue_mask")
+    gx, chain, rmask = _f32c(grad_xyz, "grad_xyz"), _f32c_opt(chain_idx, "chain_idx"), _u8c(residue_mask, "residue_mask")
     B, N, A = xyz.shape[:3]
     dev = xyz.device
     with _on(dev):
@@ -720,8 +763,7 @@ def check_distmat_shapes(d_cb, omega, theta, phi, mask=None, chain_breaks=None, 
         raise ValueError(f"d_cb must have shape (batch, L, L), got {shape}")
     for name, t, want in (("omega", omega, shape), ("theta", theta, shape), ("phi", phi, shape), ("mask", mask, shape),
                           ("chain_breaks", chain_breaks, shape[:2]), ("lengths", lengths, shape[:1])):
-        if t is not None and tuple(t.shape) != want:
-            raise ValueError(f"{name} must have shape {want} to match d_cb {shape}, got {tuple(t.shape)}")
+        _check_optional(t, want, name, "d_cb", shape)
     check_distmat_size(shape[0], shape[1])
 
 
@@ -802,9 +844,8 @@ def backbone_distmat_finish_(D: torch.Tensor, chain_breaks: Optional[torch.Tenso
     """Steps 8-9 in place on a (B,3,3,L,L) float32 tensor: (D + D^T) / 2 over the 3 L nodes, the bonds again (none
     across a chain break) and NaN for residues at or beyond ``lengths``."""
     B, L = check_floyd_warshall_shape(D, 3)
-    for name, t, want in (("chain_breaks", chain_breaks, (B, L)), ("lengths", lengths, (B,))):
-        if t is not None and tuple(t.shape) != want:
-            raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
+    _check_optional(chain_breaks, (B, L), "chain_breaks")
+    _check_optional(lengths, (B,), "lengths")
     _require_f32c(D, "D", "D must be a contiguous float32 tensor (it is updated in place)")
     _same_device(D, chain_breaks=chain_breaks, lengths=lengths)
     brk, lens = _u8c(chain_breaks, "chain_breaks"), _i32c(lengths, "lengths")
@@ -973,32 +1014,21 @@ def frames(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 1, *, wan
     return rot, trans
 
 
-def _check_float_tensor(t, shape, name: str, like: str) -> None:
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)} to match {like}, got {tuple(t.shape)}")
-    if not t.dtype.is_floating_point:
-        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
-
-
 def check_frames_backward_shapes(xyz, a1: int, a2: int, a3: int, t_atom: int = 1, grad_rot=None, grad_trans=None,
                                  residue_mask=None, out=None) -> None:
     """Shape rules of ``frames_backward``, on shapes, dtypes and slots only (no device, no launch): ValueError."""
-    shape = tuple(xyz.shape)
-    if len(shape) != 4 or shape[-1] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
-    if not xyz.dtype.is_floating_point:
-        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
-    B, N, A = shape[:3]
+    B, N, A = _xyz_dims(xyz)
+    shape = (B, N, A, 3)
     if grad_rot is None and grad_trans is None:
         raise ValueError("at least one of grad_rot and grad_trans is required")
+    like = f"xyz {shape}"
     if grad_rot is not None:
-        _check_float_tensor(grad_rot, (B, N, 3, 3), "grad_rot", f"xyz {shape}")
+        _check_float_tensor(grad_rot, (B, N, 3, 3), "grad_rot", like)
         _check_atom_slots(A, a1, a2, a3)
     if grad_trans is not None:
-        _check_float_tensor(grad_trans, (B, N, 3), "grad_trans", f"xyz {shape}")
+        _check_float_tensor(grad_trans, (B, N, 3), "grad_trans", like)
         _check_atom_slots(A, t_atom)
-    if residue_mask is not None and tuple(residue_mask.shape) != (B, N):
-        raise ValueError(f"residue_mask must have shape {(B, N)} to match xyz {shape}, got {tuple(residue_mask.shape)}")
+    _check_optional(residue_mask, (B, N), "residue_mask", "xyz", shape)
     _check_out(out, shape, "out")
 
 
@@ -1013,8 +1043,7 @@ def frames_backward(xyz: torch.Tensor, a1: int, a2: int, a3: int, t_atom: int = 
     check_frames_backward_shapes(xyz, a1, a2, a3, t_atom, grad_rot, grad_trans, residue_mask, out)
     xyz = _f32c(xyz, "xyz")
     _same_device(xyz, grad_rot=grad_rot, grad_trans=grad_trans, residue_mask=residue_mask, out=out)
-    g_rot = None if grad_rot is None else _f32c(grad_rot, "grad_rot")
-    g_trans = None if grad_trans is None else _f32c(grad_trans, "grad_trans")
+    g_rot, g_trans = _f32c_opt(grad_rot, "grad_rot"), _f32c_opt(grad_trans, "grad_trans")
     rmask = _u8c(residue_mask, "residue_mask")
     B, N, A = xyz.shape[:3]
     with _on(xyz.device):
@@ -1046,23 +1075,21 @@ def check_fape_shapes(rot, trans, points, target_rot, target_trans, target_point
         raise ValueError(f"at most 65535 structures per call, got {B}")
     if N > 2 ** 30 or M > 2 ** 30:
         raise ValueError(f"at most 2^30 frames and points per structure, got {N} and {M}")
+    like = f"rot {shape} and points {pshape}"
     for name, t, want in (("rot", rot, shape), ("trans", trans, (B, N, 3)), ("points", points, pshape),
                           ("target_rot", target_rot, shape), ("target_trans", target_trans, (B, N, 3)),
                           ("target_points", target_points, pshape)):
-        _check_float_tensor(t, want, name, f"rot {shape} and points {pshape}")
-    for name, t, want in (("frame_mask", frame_mask, (B, N)), ("point_mask", point_mask, (B, M))):
-        if t is not None and tuple(t.shape) != want:
-            raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
+        _check_float_tensor(t, want, name, like)
+    _check_optional(frame_mask, (B, N), "frame_mask")
+    _check_optional(point_mask, (B, M), "point_mask")
     if isinstance(clamp, torch.Tensor):
         _check_float_tensor(clamp, (B,), "clamp", f"rot {shape}")
         if not clamp.is_cuda and not bool((clamp > 0).all()):
             raise ValueError("clamp must be positive (inf = unclamped)")
     elif not float(clamp) > 0:
         raise ValueError(f"clamp must be positive (inf = unclamped), got {clamp}")
-    if not (float(scale) > 0 and float(scale) != float("inf")):
-        raise ValueError(f"scale must be positive and finite, got {scale}")
-    if not (float(eps) >= 0 and float(eps) != float("inf")):
-        raise ValueError(f"eps must be non-negative and finite, got {eps}")
+    _check_scalar(scale, "scale", "positive")
+    _check_scalar(eps, "eps", "non-negative")
     if grad_loss is not None:
         _check_float_tensor(grad_loss, (B,), "grad_loss", f"rot {shape}")
     tensors = {"trans": trans, "points": points, "target_rot": target_rot, "target_trans": target_trans,
@@ -1155,34 +1182,20 @@ def check_lddt_shapes(points, target_points, point_mask=None, groups=None, cutof
     """Shape rules of ``lddt`` / ``lddt_backward``, on shapes, dtypes, devices and the scalars only (no launch):
     ValueError.  ``thresholds``: 1 to 8 strictly increasing floats in (0, 64]; ``cutoff`` positive and finite; ``groups``
     an integer tensor."""
-    shape = tuple(points.shape)
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
-    B, M = shape[:2]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if M > 2 ** 30:
-        raise ValueError(f"at most 2^30 points per structure, got {M}")
-    _check_float_tensor(points, shape, "points", f"points {shape}")
-    _check_float_tensor(target_points, shape, "target_points", f"points {shape}")
-    if point_mask is not None and tuple(point_mask.shape) != (B, M):
-        raise ValueError(f"point_mask must have shape {(B, M)}, got {tuple(point_mask.shape)}")
-    if groups is not None:
-        if tuple(groups.shape) != (B, M):
-            raise ValueError(f"groups must have shape {(B, M)}, got {tuple(groups.shape)}")
-        if groups.dtype.is_floating_point or groups.dtype.is_complex or groups.dtype == torch.bool:
-            raise ValueError(f"groups must be an integer tensor, got {groups.dtype}")
-    if not (float(cutoff) > 0 and float(cutoff) != float("inf")):
-        raise ValueError(f"cutoff must be positive and finite, got {cutoff}")
+    B, M = _points_dims(points, 65535, 2 ** 30)
+    like = f"points {(B, M, 3)}"
+    _check_float_tensor(target_points, (B, M, 3), "target_points", like)
+    _check_optional(point_mask, (B, M), "point_mask")
+    _check_optional(groups, (B, M), "groups", integer=True)
+    _check_scalar(cutoff, "cutoff", "positive")
     thr = [float(t) for t in thresholds]
     if not 1 <= len(thr) <= LDDT_MAX_THRESHOLDS:
         raise ValueError(f"between 1 and {LDDT_MAX_THRESHOLDS} thresholds, got {len(thr)}")
     if not all(0 < t <= LDDT_MAX_THRESHOLD for t in thr) or any(b <= a for a, b in zip(thr, thr[1:])):
         raise ValueError(f"thresholds must be strictly increasing and in (0, {LDDT_MAX_THRESHOLD}], got {tuple(thr)}")
-    if not (float(eps) >= 0 and float(eps) != float("inf")):
-        raise ValueError(f"eps must be non-negative and finite, got {eps}")
+    _check_scalar(eps, "eps", "non-negative")
     if grad_S is not None:
-        _check_float_tensor(grad_S, (B, M), "grad_S", f"points {shape}")
+        _check_float_tensor(grad_S, (B, M), "grad_S", like)
     _same_device(points, target_points=target_points, point_mask=point_mask, groups=groups, grad_S=grad_S)
 
 
@@ -1247,39 +1260,20 @@ PEPTIDE_BOND = dict(l0=1.329, sigma_l=0.014, l0_pro=1.341, sigma_l_pro=0.016, co
 PEPTIDE_BOND_CONSTANTS = 12   # PS_PEPTIDE_BOND_CONSTANTS of include/protstruc_hip.h
 
 
-def _is_integer_tensor(t) -> bool:
-    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
-
-
 def check_clash_shapes(points, radius, point_mask=None, groups=None, link=None, tolerance=CLASH_TOLERANCE, eps=1e-10,
                        grad_E=None) -> None:
     """Shape rules of ``clash`` / ``clash_backward``, on shapes, dtypes, devices and the scalars only (no launch):
     ValueError.  ``groups`` and ``link`` are integer tensors; ``tolerance`` finite; ``eps`` non-negative and finite."""
-    shape = tuple(points.shape)
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
-    B, M = shape[:2]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if M > 2 ** 30:
-        raise ValueError(f"at most 2^30 points per structure, got {M}")
-    _check_float_tensor(points, shape, "points", f"points {shape}")
-    _check_float_tensor(radius, (B, M), "radius", f"points {shape}")
-    if point_mask is not None and tuple(point_mask.shape) != (B, M):
-        raise ValueError(f"point_mask must have shape {(B, M)}, got {tuple(point_mask.shape)}")
-    for name, t in (("groups", groups), ("link", link)):
-        if t is None:
-            continue
-        if tuple(t.shape) != (B, M):
-            raise ValueError(f"{name} must have shape {(B, M)}, got {tuple(t.shape)}")
-        if not _is_integer_tensor(t):
-            raise ValueError(f"{name} must be an integer tensor, got {t.dtype}")
-    if not abs(float(tolerance)) < float("inf"):
-        raise ValueError(f"tolerance must be finite, got {tolerance}")
-    if not (float(eps) >= 0 and float(eps) != float("inf")):
-        raise ValueError(f"eps must be non-negative and finite, got {eps}")
+    B, M = _points_dims(points, 65535, 2 ** 30)
+    like = f"points {(B, M, 3)}"
+    _check_float_tensor(radius, (B, M), "radius", like)
+    _check_optional(point_mask, (B, M), "point_mask")
+    _check_optional(groups, (B, M), "groups", integer=True)
+    _check_optional(link, (B, M), "link", integer=True)
+    _check_scalar(tolerance, "tolerance", "finite")
+    _check_scalar(eps, "eps", "non-negative")
     if grad_E is not None:
-        _check_float_tensor(grad_E, (B, M), "grad_E", f"points {shape}")
+        _check_float_tensor(grad_E, (B, M), "grad_E", like)
     _same_device(points, radius=radius, point_mask=point_mask, groups=groups, link=link, grad_E=grad_E)
 
 
@@ -1355,20 +1349,15 @@ def check_peptide_bond_shapes(xyz, junction_mask=None, next_is_proline=None, n_s
                               c_slot: int = 2, eps=1e-10, grad_viol=None, **constants) -> None:
     """Shape rules of ``peptide_bond`` / ``peptide_bond_backward``, on shapes, dtypes, devices, slots and the constants
     only (no launch): ValueError.  The three slots differ; ``constants`` are names of ``PEPTIDE_BOND``."""
-    shape = tuple(xyz.shape)
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
-    if not xyz.dtype.is_floating_point:
-        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
-    B, N, A = shape[:3]
+    B, N, A = _xyz_dims(xyz)
+    shape = (B, N, A, 3)
     if B * N > 2 ** 31:
         raise ValueError(f"at most 2^31 residues per call, got {B * N}")
     _check_atom_slots(A, n_slot, ca_slot, c_slot)
     if len({int(n_slot), int(ca_slot), int(c_slot)}) != 3:
         raise ValueError(f"the N, CA and C slots must differ, got {(n_slot, ca_slot, c_slot)}")
-    for name, t in (("junction_mask", junction_mask), ("next_is_proline", next_is_proline)):
-        if t is not None and tuple(t.shape) != (B, N):
-            raise ValueError(f"{name} must have shape {(B, N)} to match xyz {shape}, got {tuple(t.shape)}")
+    _check_optional(junction_mask, (B, N), "junction_mask", "xyz", shape)
+    _check_optional(next_is_proline, (B, N), "next_is_proline", "xyz", shape)
     _peptide_bond_constants(eps, constants)
     if grad_viol is not None:
         _check_float_tensor(grad_viol, (B, N, 3), "grad_viol", f"xyz {shape}")
@@ -1426,12 +1415,8 @@ def check_dssp_shapes(xyz, complete, junction, donor=None, n_slot: int = 0, ca_s
     """Shape rules of ``backbone_hbonds`` / ``dssp_assign``, on shapes, dtypes, devices and slots only (no launch):
     ValueError.  The four slots differ; with ``acceptor_idx`` (the assignment) only ``ca_slot`` counts and a structure
     has at most ``DSSP_MAX_RESIDUES`` residues."""
-    shape = tuple(xyz.shape)
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
-    if not xyz.dtype.is_floating_point:
-        raise ValueError(f"xyz must be a floating-point tensor, got {xyz.dtype}")
-    B, N, A = shape[:3]
+    B, N, A = _xyz_dims(xyz)
+    shape = (B, N, A, 3)
     if B > 65535:
         raise ValueError(f"at most 65535 structures per call, got {B}")
     if N > 2 ** 24:
@@ -1447,8 +1432,7 @@ def check_dssp_shapes(xyz, complete, junction, donor=None, n_slot: int = 0, ca_s
     for name, t in (("complete", complete), ("junction", junction), ("donor", donor)):
         if t is None and name != "donor":
             raise ValueError(f"{name} is required")
-        if t is not None and tuple(t.shape) != (B, N):
-            raise ValueError(f"{name} must have shape {(B, N)} to match xyz {shape}, got {tuple(t.shape)}")
+        _check_optional(t, (B, N), name, "xyz", shape)
     if acceptor_idx is not None:
         if N > DSSP_MAX_RESIDUES:
             raise ValueError(f"at most {DSSP_MAX_RESIDUES} residues per structure, got {N}")
@@ -1505,31 +1489,17 @@ def check_sasa_shapes(points, radius, point_mask=None, isolate=None, sphere=None
     """Shape rules of ``solvent_accessibility``, on shapes, dtypes, devices and the scalar only (no launch): ValueError.
     ``isolate`` is an integer tensor; ``sphere`` a float32 (S,3) table with ``1 <= S <= SASA_MAX_SPHERE_POINTS`` (None is
     not checked: the layers above build it); ``probe`` non-negative and finite."""
-    shape = tuple(points.shape)
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
-    B, M = shape[:2]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if M > 2 ** 24:
-        raise ValueError(f"at most 2^24 points per structure, got {M}")
-    _check_float_tensor(points, shape, "points", f"points {shape}")
-    _check_float_tensor(radius, (B, M), "radius", f"points {shape}")
-    if point_mask is not None and tuple(point_mask.shape) != (B, M):
-        raise ValueError(f"point_mask must have shape {(B, M)}, got {tuple(point_mask.shape)}")
-    if isolate is not None:
-        if tuple(isolate.shape) != (B, M):
-            raise ValueError(f"isolate must have shape {(B, M)}, got {tuple(isolate.shape)}")
-        if not _is_integer_tensor(isolate):
-            raise ValueError(f"isolate must be an integer tensor, got {isolate.dtype}")
+    B, M = _points_dims(points, 65535, 2 ** 24)
+    _check_float_tensor(radius, (B, M), "radius", f"points {(B, M, 3)}")
+    _check_optional(point_mask, (B, M), "point_mask")
+    _check_optional(isolate, (B, M), "isolate", integer=True)
     if sphere is not None:
         if not isinstance(sphere, torch.Tensor) or sphere.dtype != torch.float32 or sphere.ndim != 2 or sphere.shape[1] != 3:
             raise ValueError("sphere must be a float32 tensor of shape (S, 3), got "
                              f"{getattr(sphere, 'dtype', type(sphere).__name__)} {tuple(getattr(sphere, 'shape', ()))}")
         if not 1 <= sphere.shape[0] <= SASA_MAX_SPHERE_POINTS:
             raise ValueError(f"sphere must have between 1 and {SASA_MAX_SPHERE_POINTS} directions, got {sphere.shape[0]}")
-    if not (float(probe) >= 0 and float(probe) != float("inf")):
-        raise ValueError(f"probe must be non-negative and finite, got {probe}")
+    _check_scalar(probe, "probe", "non-negative")
     _same_device(points, radius=radius, point_mask=point_mask, isolate=isolate, sphere=sphere)
 
 
@@ -1657,10 +1627,7 @@ def affine_(xyz: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torc
 
 def check_rigid_shapes(xyz, R=None, t=None) -> Tuple[int, int]:
     """Shape rules of ``rigid``, on shapes only (no launch): ValueError.  Returns the kernel's (r_mode, t_mode)."""
-    shape = tuple(xyz.shape)
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {shape}")
-    B, N, A = shape[:3]
+    B, N, A = _xyz_dims(xyz, floating=False)
     r_mode = t_mode = 0
     if R is not None:
         r_mode = {2: 1, 3: 2, 4: 3}.get(R.ndim, -1)
@@ -1678,7 +1645,7 @@ def check_rigid_shapes(xyz, R=None, t=None) -> Tuple[int, int]:
         elif t_shape == (B, N, A, 3):
             t_mode = 4
         else:
-            raise ValueError(f"translation shape {t_shape} does not broadcast against xyz {shape}")
+            raise ValueError(f"translation shape {t_shape} does not broadcast against xyz {(B, N, A, 3)}")
     return r_mode, t_mode
 
 
@@ -1703,12 +1670,10 @@ def rigid(xyz: torch.Tensor, R: Optional[torch.Tensor] = None, t: Optional[torch
 def center_of_mass(xyz: torch.Tensor, atom: int = 1) -> torch.Tensor:
     """(B,3) nanmean over residues of one atom slot, per component (a residue with a NaN y still counts for x and z);
     NaN where no residue has the component.  Accumulated in double and rounded once."""
-    if xyz.ndim != 4 or xyz.shape[3] != 3:
-        raise ValueError(f"xyz must have shape (batch, residues, atoms, 3), got {tuple(xyz.shape)}")
-    if xyz.shape[2]:
-        _check_atom_slots(xyz.shape[2], atom)
+    B, N, A = _xyz_dims(xyz, floating=False)
+    if A:
+        _check_atom_slots(A, atom)
     xyz = _f32c(xyz, "xyz")
-    B, N, A = xyz.shape[:3]
     with _on(xyz.device):
         # no residues: the reference's nanmean over nothing is NaN
         com = (torch.empty if xyz.numel() else (lambda *a, **k: torch.full(a, float("nan"), **k)))(

@@ -6,7 +6,7 @@ import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from protstruc_amd import StructureBatch, _lib, ops
+from protstruc_amd import StructureBatch, _lib, geometry, ops
 
 g = torch.Generator().manual_seed(0)
 B, N = 1, 64
@@ -18,6 +18,19 @@ xg, mg = sb.get_xyz(), sb.get_atom_mask()
 d = torch.empty(B, N, N, 15, 15, device="cuda")
 m = torch.empty(B, N, N, 15, 15, dtype=torch.bool, device="cuda")
 beta = torch.full((B,), 0.01, device="cuda")
+
+# operands of the fused losses and structure features (K13 - K23), 64 residues / points: each of these wrappers checks its
+# arguments (ops.check_*_shapes) on every call, which is most of what it costs at this size
+pts = xg[:, :, 1].contiguous()                  # the CA atoms as (B, N, 3) points
+tgt = pts + 0.25
+rot, trans = ops.frames(xg, 0, 1, 2)
+pmask = torch.ones(B, N, dtype=torch.bool, device="cuda")
+groups = torch.arange(N, dtype=torch.int32, device="cuda").repeat(B, 1)
+radius = torch.full((B, N), 1.7, device="cuda")
+junction = pmask.clone()
+junction[:, -1] = False
+sphere = geometry.sphere_points(32).cuda()
+g_rot, g_trans = torch.ones_like(rot), torch.ones_like(trans)
 
 
 def per_call(fn, n=2000):
@@ -41,6 +54,13 @@ rows = [
     ("sb.pairwise_dihedrals(CA,CB|CA,CB)", lambda: sb.pairwise_dihedrals(["CA", "CB"], ["CA", "CB"])),
     ("sb.inter_residue_geometry()", lambda: sb.inter_residue_geometry()),
     ("sb.diffuse_xyz(beta)", lambda: sb.diffuse_xyz(beta)),
+    ("ops.frames_backward", lambda: ops.frames_backward(xg, 0, 1, 2, grad_rot=g_rot, grad_trans=g_trans, residue_mask=pmask)),
+    ("ops.fape", lambda: ops.fape(rot, trans, pts, rot, trans, tgt, pmask, pmask)),
+    ("ops.lddt", lambda: ops.lddt(pts, tgt, pmask, groups)),
+    ("ops.clash", lambda: ops.clash(pts, radius, pmask, groups)),
+    ("ops.peptide_bond", lambda: ops.peptide_bond(xg, junction)),
+    ("ops.backbone_hbonds", lambda: ops.backbone_hbonds(xg, pmask, junction)),
+    ("ops.solvent_accessibility", lambda: ops.solvent_accessibility(pts, radius, pmask, sphere=sphere)),
     ("torch.empty + torch.add (reference point)", lambda: torch.add(xg, 1.0)),
     # config 5's eager step: diffuse_xyz + backbone_orientations
     ("config-5 eager step (diffuse_xyz + backbone_orientations)", lambda: (sb.diffuse_xyz(beta), sb.backbone_orientations())),

@@ -37,7 +37,7 @@ extern "C" {
 #define PS_RNG_STATE_WORDS 528
 
 /* ABI version of this header (bumped on any signature change); ps_abi_version() returns the library's. */
-#define PS_ABI_VERSION 15
+#define PS_ABI_VERSION 16
 int ps_abi_version(void);
 
 /* Always 0: the library contains no timing experiments.  (Kept for ABI stability: earlier versions had a tools-only build
@@ -632,6 +632,35 @@ int ps_dssp_assign(const float* xyz, const uint8_t* complete, const uint8_t* jun
 int ps_solvent_accessibility_f32(const float* points, const float* radius, const uint8_t* point_mask,
                                  const int32_t* isolate, const float* sphere, float probe,
                                  int32_t* count, float* area, int B, int M, int S, void* stream);
+
+/*
+ * K24 (ABI 16) -- k nearest neighbours, fused: for every query point its k nearest candidate points of the same
+ * structure, sorted by distance; no (B,Q,M) tensor exists.  points (B,M,3); point_mask (B,M), one byte each, NULL = every
+ * point; queries (B,Q,3), NULL = the points themselves (the self graph: Q must equal M and query_mask and query_exclude
+ * must be NULL -- they are point_mask and exclude); query_mask (B,Q), NULL = every query; exclude (B,M) and query_exclude
+ * (B,Q) int32, both or neither: a candidate is skipped for a query with an equal key (the residue index for atom graphs,
+ * the chain index for interface graphs); 1 <= k <= PS_KNN_MAX_K; cutoff > 0, +inf = none; include_self: the self graph
+ * only -- without it candidate j == q is skipped.  With X = (double)x:
+ *   dx = Xj.x - Xq.x, dy, dz likewise       d2 = (dx*dx + dy*dy) + dz*dz       in double, in exactly this order
+ *   j is a neighbour of q iff both are in their masks, their keys differ where keys are given, j != q in the self graph
+ *   unless include_self, d2 is finite, and d2 <= C2 = (double)cutoff * (double)cutoff
+ *   the neighbours ordered by (d2, j) ascending -- equal distances go to the lower index --, the first k kept
+ *   idx[b][q][0..k-1] (int32, into the M axis; padding -1)      dist[b][q][0..k-1] = (float)sqrt(d2) (padding +inf)
+ *   count[b][q] = the number of real neighbours, at most k (int32)
+ * Every element of the three outputs is written; a masked query gets count 0 and all padding.  The library is built with
+ * -ffp-contract=off, which is part of the definition: a float64 restatement gives the same bits.  A NaN or infinite
+ * coordinate makes d2 non-finite, so such a point is nobody's neighbour and such a query has none; masked points are
+ * compacted away while a tile is staged, so NaN there never reaches arithmetic.  A column is dropped in fp32 only where
+ * fl32(|xj - xq|^2) > fl32(tau) (1 + 2^-20) + 2^-126, tau the owner's current k-th best d2 (C2 until it has k), which no pair
+ * the double test keeps satisfies; the pairs that pass are decided in double.  Each wave owns 64 queries, one max-heap of k
+ * entries per query in LDS; no atomics, one fixed order per list: bit-for-bit repeatable.  Any M and Q.  B <= 65535;
+ * M, Q <= 2^24; cutoff not NaN.
+ */
+#define PS_KNN_MAX_K 64
+int ps_nearest_neighbors_f32(const float* points, const uint8_t* point_mask, const float* queries,
+                             const uint8_t* query_mask, const int32_t* exclude, const int32_t* query_exclude,
+                             int k, float cutoff, int include_self, int32_t* idx, float* dist, int32_t* count,
+                             int B, int M, int Q, void* stream);
 
 /*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,

@@ -12,7 +12,7 @@ from typing import NamedTuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROTSTRUC_AMD_LIB selects another build of the library: the same-process A/B of two builds (tools/k1_ab_libs.py)
 LIB_PATH = os.environ.get("PROTSTRUC_AMD_LIB") or os.path.join(_HERE, "lib", "libprotstruc_hip.so")
-EXPECTED_ABI = 15  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
+EXPECTED_ABI = 16  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
 
 
 class K1Config(ctypes.Structure):
@@ -101,6 +101,9 @@ SIGNATURES = {
                                 _c_stream]),
     "ps_solvent_accessibility_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, _c_f32p, ctypes.c_float,
                                               ctypes.c_void_p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
+    "ps_nearest_neighbors_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int,
+                                          ctypes.c_float, _c_int, ctypes.c_void_p, _c_f32p, ctypes.c_void_p, _c_int, _c_int,
+                                          _c_int, _c_stream]),
     "ps_rigid_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_center_of_mass_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_frames_to_backbone_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),

@@ -23,6 +23,7 @@
 // 14: ps_backbone_hbonds_f32 (K21, the two best backbone hydrogen bonds of every residue, DSSP energies),
 //     ps_dssp_assign (K22, DSSP secondary-structure labels from them).
 // 15: ps_solvent_accessibility_f32 (K23, Shrake-Rupley solvent-accessible surface area per point).
+// 16: ps_nearest_neighbors_f32 (K24, the k nearest neighbours of every query point, sorted, with masks, keys and a cutoff).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

@@ -13,7 +13,9 @@ per-residue frames as a differentiable function of the coordinates (``ops.frames
 hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward``); ``steric_clash`` and
 ``peptide_bond_violations`` are the structural-violation terms (``ops.clash`` / ``ops.peptide_bond`` and their backwards);
 ``backbone_hbonds`` and ``dssp`` are the DSSP hydrogen bonds and secondary-structure labels (``ops.backbone_hbonds`` /
-``ops.dssp_assign``).
+``ops.dssp_assign``); ``solvent_accessibility`` is Shrake and Rupley's surface area (``ops.solvent_accessibility``);
+``nearest_neighbors`` is the k-nearest-neighbour graph (``ops.nearest_neighbors``) and ``gather_neighbors`` the gather
+that turns its indices into edge features.
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -550,6 +552,64 @@ def solvent_accessibility(points, radius, point_mask=None, isolate=None, probe=1
         sphere = _sphere_on(n, points.device)
     return SolventAccessibility(*ops.solvent_accessibility(points.detach(), radius.detach(), point_mask, isolate, sphere=sphere,
                                                            probe=float(probe)))
+
+
+class Neighbors(NamedTuple):
+    """The k nearest neighbours of every query (``nearest_neighbors``), nearest first."""
+    idx: torch.Tensor     # (B,Q,k) int32: indices into the points' M axis; -1 where a query has fewer than k neighbours
+    dist: torch.Tensor    # (B,Q,k) fp32: the distances, ascending; +inf at the padding
+    count: torch.Tensor   # (B,Q) int32: the number of real neighbours, at most k
+
+
+def nearest_neighbors(points, k, point_mask=None, *, queries=None, query_mask=None, exclude=None, query_exclude=None,
+                      cutoff=float("inf"), include_self=False) -> Neighbors:
+    """The ``k`` nearest ``points`` (B,M,3) of every query, sorted by distance: ``Neighbors(idx, dist, count)`` with
+    ``idx`` and ``dist`` (B,Q,k) and ``count`` (B,Q).  The queries are ``queries`` (B,Q,3) or, None, the points themselves
+    (the neighbour graph of the points, Q = M; a point is not its own neighbour unless ``include_self``).  Points outside
+    ``point_mask`` (B,M) are no candidates and queries outside ``query_mask`` (B,Q; in the self graph ``point_mask``) get
+    no neighbours; NaN there never reaches a result.  ``exclude`` (B,M) and ``query_exclude`` (B,Q; in the self graph
+    ``exclude``) are integer keys: a candidate with the query's key is skipped -- the residue index leaves out an atom's
+    own residue, the chain index leaves only the other chains.  ``cutoff`` drops candidates further away (inclusive).
+    Distances are compared in double on the float32 coordinates and ties go to the lower index, so the result is defined
+    bit for bit; a query with fewer than ``k`` neighbours is padded with index -1 and distance +inf, and ``count`` says
+    how many are real.  ``k <= ops.KNN_MAX_K``.  One HIP kernel (``ops.nearest_neighbors``); no (B,Q,M) tensor is built.
+    numpy in -> numpy out; tensors come back on the device of ``points``, CPU tensors included.
+
+    Not differentiable -- the selection is discrete -- and the outputs carry no graph.  Edge lengths that are
+    differentiable with respect to the coordinates are rebuilt from the indices::
+
+        nb = nearest_neighbors(x, 30, mask)
+        xj = gather_neighbors(x, nb.idx)                        # (B,M,k,3), zeros at the padding
+        edge = (xj - x[:, :, None]).norm(dim=-1)                # (B,M,k), equal to nb.dist up to float32 rounding
+        edge = edge.masked_fill(nb.idx < 0, 0.0)                # the padding takes no gradient
+    """
+    given = [(name, t) for name, t in (("points", points), ("point_mask", point_mask), ("queries", queries),
+                                       ("query_mask", query_mask), ("exclude", exclude), ("query_exclude", query_exclude))
+             if t is not None]
+    for name, t in given:
+        if not isinstance(t, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{name} must be a tensor or an ndarray")
+    home = points.device if isinstance(points, torch.Tensor) else None
+    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
+    args = dict(zip((name for name, _ in given), prepped))
+    out = ops.nearest_neighbors(args.pop("points"), k, args.pop("point_mask", None), cutoff=cutoff, include_self=include_self,
+                                **args)
+    return Neighbors(*(_finish(t if home is None else t.to(home), ft) for t in out))
+
+
+def gather_neighbors(values, idx, fill=0):
+    """``values`` (B,M,...) at the neighbours ``idx`` (B,Q,k) of ``nearest_neighbors``: (B,Q,k,...), with ``fill`` where
+    ``idx`` is -1 (the padding).  Plain torch, on any device; differentiable with respect to ``values`` (the padding takes
+    no gradient)."""
+    if idx.ndim != 3 or values.ndim < 2 or values.shape[0] != idx.shape[0]:
+        raise ValueError(f"values must be (B, M, ...) and idx (B, Q, k), got {tuple(values.shape)} and {tuple(idx.shape)}")
+    B, Q, k = idx.shape
+    if values.shape[1] == 0:   # no candidates: everything is padding
+        return values.new_full((B, Q, k, *values.shape[2:]), fill)
+    real = idx >= 0
+    at = idx.clamp(min=0).long().reshape(B, Q * k, *([1] * (values.ndim - 2))).expand(B, Q * k, *values.shape[2:])
+    out = torch.gather(values, 1, at).reshape(B, Q, k, *values.shape[2:])
+    return torch.where(real.reshape(B, Q, k, *([1] * (values.ndim - 2))), out, torch.full_like(out, fill))
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

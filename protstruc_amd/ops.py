@@ -1527,6 +1527,78 @@ def solvent_accessibility(points: torch.Tensor, radius: torch.Tensor, point_mask
     return count, area
 
 
+KNN_MAX_K = 64   # PS_KNN_MAX_K of include/protstruc_hip.h: an owner's list of k lives in LDS
+
+
+def check_knn_shapes(points, k, point_mask=None, queries=None, query_mask=None, exclude=None, query_exclude=None,
+                     cutoff=_INF, include_self=False) -> None:
+    """Shape rules of ``nearest_neighbors``, on shapes, dtypes, devices and the scalars only (no launch): ValueError.
+    ``1 <= k <= KNN_MAX_K``; ``cutoff`` positive, +inf allowed; ``exclude`` / ``query_exclude`` integer tensors.  Without
+    ``queries`` (the self graph) ``query_mask`` and ``query_exclude`` are not given -- they are ``point_mask`` and
+    ``exclude``; with ``queries``, ``exclude`` and ``query_exclude`` come together and ``include_self`` means nothing."""
+    B, M = _points_dims(points, 65535, 2 ** 24)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must be an integer in 1 .. {KNN_MAX_K}, got {k!r}")
+    if float(cutoff) != _INF:
+        _check_scalar(cutoff, "cutoff", "positive")
+    _check_optional(point_mask, (B, M), "point_mask", "points", (B, M, 3))
+    _check_optional(exclude, (B, M), "exclude", "points", (B, M, 3), integer=True)
+    if queries is None:
+        for name, t in (("query_mask", query_mask), ("query_exclude", query_exclude)):
+            if t is not None:
+                raise ValueError(f"{name} needs queries: in the self graph the points' own mask and keys are used")
+    else:
+        shape = tuple(queries.shape)
+        if len(shape) != 3 or shape[2] != 3 or shape[0] != B:
+            raise ValueError(f"queries must have shape ({B}, queries, 3) to match points {(B, M, 3)}, got {shape}")
+        if not queries.dtype.is_floating_point:
+            raise ValueError(f"queries must be a floating-point tensor, got {queries.dtype}")
+        Q = shape[1]
+        if Q > 2 ** 24:
+            raise ValueError(f"at most 2^24 queries per structure, got {Q}")
+        _check_optional(query_mask, (B, Q), "query_mask", "queries", shape)
+        _check_optional(query_exclude, (B, Q), "query_exclude", "queries", shape, integer=True)
+        if (exclude is None) != (query_exclude is None):
+            raise ValueError("exclude and query_exclude come together: a candidate is skipped where the two keys are equal")
+        if include_self:
+            raise ValueError("include_self applies to the self graph only (queries=None)")
+    _same_device(points, point_mask=point_mask, queries=queries, query_mask=query_mask, exclude=exclude,
+                 query_exclude=query_exclude)
+
+
+def nearest_neighbors(points: torch.Tensor, k: int, point_mask: Optional[torch.Tensor] = None, *,
+                      queries: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None,
+                      exclude: Optional[torch.Tensor] = None, query_exclude: Optional[torch.Tensor] = None,
+                      cutoff: float = _INF, include_self: bool = False):
+    """K24.  The k nearest neighbours of every query, fused and sorted: ``(idx (B,Q,k) int32, dist (B,Q,k) fp32, count
+    (B,Q) int32)``.  ``points`` (B,M,3) are the candidates, ``queries`` (B,Q,3) the points asked for -- None: the points
+    themselves (the self graph, Q = M, where a point is not its own neighbour unless ``include_self``).  A candidate j is a
+    neighbour of query q where both are in their masks (``point_mask`` (B,M), ``query_mask`` (B,Q); None = all; the self
+    graph uses ``point_mask`` for both), their keys differ (``exclude`` (B,M), ``query_exclude`` (B,Q), integers: the
+    residue index for atom graphs, the chain index for interface graphs), the squared distance ``d2 = (dx*dx + dy*dy) +
+    dz*dz``, evaluated in double on the float32 inputs, is finite and ``d2 <= cutoff^2``.  The neighbours are ordered by
+    ``(d2, j)`` -- equal distances to the lower index -- and the first ``k <= KNN_MAX_K`` kept: ``idx`` indexes the M axis
+    (padding -1), ``dist = sqrt(d2)`` rounded to float32 once (padding +inf), ``count`` is the number of real neighbours.
+    A masked query gets count 0 and all padding; a NaN or infinite coordinate makes a point nobody's neighbour, and NaN
+    under a mask never reaches arithmetic.  Nothing of size Q*M is built; deterministic (include/protstruc_hip.h)."""
+    check_knn_shapes(points, k, point_mask, queries, query_mask, exclude, query_exclude, cutoff, include_self)
+    x, pm, key = _f32c(points, "points"), _u8c(point_mask, "point_mask"), _i32c(exclude, "exclude")
+    y, qm, qkey = _f32c_opt(queries, "queries"), _u8c(query_mask, "query_mask"), _i32c(query_exclude, "query_exclude")
+    B, M = x.shape[:2]
+    Q, k = M if y is None else y.shape[1], int(k)
+    with _on(x.device):
+        if not (B and M and Q):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            return (torch.full((B, Q, k), -1, dtype=torch.int32, device=x.device),
+                    torch.full((B, Q, k), _INF, dtype=torch.float32, device=x.device),
+                    torch.zeros(B, Q, dtype=torch.int32, device=x.device))
+        idx = torch.empty(B, Q, k, dtype=torch.int32, device=x.device)   # the kernel writes every element
+        dist = torch.empty(B, Q, k, dtype=torch.float32, device=x.device)
+        count = torch.empty(B, Q, dtype=torch.int32, device=x.device)
+        _launch("ps_nearest_neighbors_f32", _ptr(x), _ptr(pm), _ptr(y), _ptr(qm), _ptr(key), _ptr(qkey), k, float(cutoff),
+                int(bool(include_self)), _ptr(idx), _ptr(dist), _ptr(count), B, M, Q, _stream(x))
+    return idx, dist, count
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -559,8 +559,8 @@ class StructureBatch:
                              "that has one")
         points, radius, takes_part, seq_idx = self._atom_points(atoms, radii)
         isolate = None
-        if per_chain:   # the padding's NaN becomes -1; padded atoms are outside the mask anyway
-            isolate = torch.nan_to_num(self.chain_idx.to(torch.float32), nan=-1.0).to(torch.int32).repeat_interleave(A, dim=1)
+        if per_chain:
+            isolate = self._chain_keys().repeat_interleave(A, dim=1)
         area = geometry.solvent_accessibility(points, radius, takes_part, isolate, probe=probe, n_points=n_points).area
         area = area.reshape(B, N, A)
         if not per_residue:
@@ -578,6 +578,51 @@ class StructureBatch:
         alone less its area in the whole structure.  Non-negative up to rounding and exactly 0 for a structure of one
         chain; summed over two chains it is the buried surface of their interface."""
         return self.solvent_accessibility(per_chain=True) - self.solvent_accessibility()
+
+    # ------------------------------------------------------------------ neighbour graphs
+    def _chain_keys(self) -> torch.Tensor:
+        """(B,N) int32 chain index; the padding's NaN becomes -1 (padded residues are outside every mask anyway)."""
+        return torch.nan_to_num(self.chain_idx.to(torch.float32), nan=-1.0).to(torch.int32)
+
+    def knn_graph(self, k: int = 30, atom: str = "CA", cutoff: Optional[float] = None, include_self: bool = False,
+                  other_chains_only: bool = False):
+        """The ``k`` nearest residues of every residue by the distance between their ``atom`` (default CA):
+        ``geometry.Neighbors(idx, dist, count)`` with ``idx`` and ``dist`` (B,N,k), nearest first, and ``count`` (B,N).
+        A residue takes part -- as a query and as a neighbour -- where it is in the residue mask and has the atom; the
+        others get no neighbours, and NaN coordinates there never reach the result.  ``cutoff`` (A) drops residues
+        further away; a residue with fewer than ``k`` neighbours is padded with index -1 and distance +inf.  A residue is
+        not its own neighbour unless ``include_self``; ``other_chains_only`` keeps the residues of the other chains only
+        (the interface graph).  Equal distances go to the lower index.  One HIP kernel (``geometry.nearest_neighbors``);
+        no (B,N,N) tensor is built; not differentiable -- ``geometry.gather_neighbors`` rebuilds differentiable edges."""
+        from . import geometry
+
+        if not ATOM.is_valid(atom):
+            raise ValueError(f"Atom {atom} is not valid.")
+        (slot,) = self._atom_slots((atom,))
+        exclude = self._chain_keys() if other_chains_only else None
+        return geometry.nearest_neighbors(self.xyz[:, :, slot], k, self._present_atoms()[:, :, slot], exclude=exclude,
+                                          cutoff=float("inf") if cutoff is None else cutoff, include_self=include_self)
+
+    def atom_knn_graph(self, k: int = 32, atoms="all", cutoff: Optional[float] = None, exclude_same_residue: bool = True):
+        """The ``k`` nearest atoms of every atom, over the (B, N*A, 3) view of the coordinates -- no gather:
+        ``geometry.Neighbors(idx, dist, count)`` with ``idx`` and ``dist`` (B, N*A, k) and ``count`` (B, N*A).  ``idx``
+        indexes the flattened atom axis: ``idx // A`` is the neighbour's residue and ``idx % A`` its atom slot (padding
+        -1: test ``idx >= 0`` first).  An atom takes part where it is present, its residue is in the residue mask and its
+        slot is among ``atoms`` (``"all"``: every slot); the selection is folded into the point mask, and atoms outside
+        it get no neighbours.  ``exclude_same_residue`` leaves out the atoms of the atom's own residue (the residue index
+        is the exclusion key); without it only the atom itself is left out.  ``cutoff`` (A) drops atoms further away.
+        Needs neither a sequence nor radii.  One HIP kernel; no (B, N*A, N*A) tensor is built; not differentiable."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+        chosen[self._atom_slots(atoms)] = True
+        takes_part = (self._present_atoms() & chosen).reshape(B, N * A)
+        residue = None
+        if exclude_same_residue:
+            residue = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
+        return geometry.nearest_neighbors(self.xyz.reshape(B, N * A, 3), k, takes_part, exclude=residue,
+                                          cutoff=float("inf") if cutoff is None else cutoff)
 
     def peptide_bond_violations(self, **constants) -> torch.Tensor:
         """Peptide-bond violations at every junction r -> r+1, (B,N,3): bond length |C - N'|, cos of CA-C-N', cos of

@@ -663,6 +663,47 @@ int ps_nearest_neighbors_f32(const float* points, const uint8_t* point_mask, con
                              int B, int M, int Q, void* stream);
 
 /*
+ * K25 (additive to ABI 16: a new symbol changes no signature) -- radial basis functions of the atom-pair distances along
+ * the edges of a neighbour graph, fused: no gathered (B,N,k,A,3) tensor and no broadcast (B,N,k,P,R) intermediate exists.
+ * xyz (B,N,A,3); atom_mask (B,N,A), one byte each, NULL = every atom; idx (B,N,k) int32, the neighbour lists of K24 on the
+ * same N axis: ANY entry outside [0, N) is padding, not only -1, so no value in idx makes the kernel read out of bounds.
+ * pair_i[p], pair_j[p], p < P: the atom slot on the source residue i and on the neighbour j; centers[c], c < R: HOST
+ * arrays, read and validated before the call returns.  1 <= k <= PS_KNN_MAX_K, 1 <= P <= PS_EDGE_MAX_PAIRS,
+ * 1 <= R <= PS_EDGE_MAX_RBF, slots in [0, A), sigma > 0 and finite with sqrt(log2 e) / sigma a normal float32;
+ * B <= 65535, N <= 2^24.  Outputs, either may be NULL, not both: dist (B,N,k,P) and rbf (B,N,k,P*R), element [p*R + c].
+ * For the edge (i, s), j = idx[b][i][s], with X = (double)x:
+ *   dx = Xj.x - Xi.x, dy, dz likewise     d2 = (dx*dx + dy*dy) + dz*dz in double, in exactly this order
+ *   dist = (float)sqrt(d2), as K24's: defined bit for bit (the library is built with -ffp-contract=off)
+ *   rbf[p*R + c] = exp(-z*z), z = (dist - centers[c]) / sigma, evaluated in fp32: within 1e-6 absolute of that expression
+ *   in float64 on the fp32 dist, centers and sigma (evaluated as exp2(-(w*w)), w = (dist - centers[c]) * fl32(sqrt(log2 e) /
+ *   sigma): under 2e-7 by analysis).
+ * dist and rbf are exactly 0 where the edge is padding or either atom of the pair is outside atom_mask; coordinates
+ * there are never read, so NaN under a mask never reaches arithmetic; an unmasked NaN propagates.  Every output element
+ * is written (the caller need not clear them), from any 4-byte aligned base -- 16-byte stores start at the first 16-byte
+ * boundary of each row's actual address --; all output offsets are 64-bit.  No atomics: two calls agree bit for bit.
+ */
+#define PS_EDGE_MAX_PAIRS 64
+#define PS_EDGE_MAX_RBF 64
+int ps_edge_rbf_f32(const float* xyz, const uint8_t* atom_mask, const int32_t* idx, const int32_t* pair_i,
+                    const int32_t* pair_j, int P, const float* centers, int R, float sigma, float* dist, float* rbf,
+                    int B, int N, int A, int k, void* stream);
+
+/*
+ * K26 (additive to ABI 16) -- the neighbour's frame in the source residue's frame along the edges of a neighbour graph.
+ * Frames as in K4 and K13: rot (B,N,3,3) row-major with the basis vectors as columns, trans (B,N,3); frame_mask (B,N),
+ * one byte each, NULL = every frame; idx (B,N,k) int32 as for K25 (any entry outside [0, N) is padding).  Outputs, either
+ * may be NULL, not both: local_pos (B,N,k,3) = R_i^T (t_j - t_i) and rel_rot (B,N,k,3,3) = R_i^T R_j, in double on the
+ * fp32 inputs in exactly this order, each value rounded to fp32 once:
+ *   v = t_j - t_i
+ *   local_pos[c]  = (R_i[0][c]*v0 + R_i[1][c]*v1) + R_i[2][c]*v2
+ *   rel_rot[a][c] = (R_i[0][a]*R_j[0][c] + R_i[1][a]*R_j[1][c]) + R_i[2][a]*R_j[2][c]
+ * Exactly 0 at the padding and where i or j is outside frame_mask (frames there are never read); every element is
+ * written.  rot and trans are both required.  1 <= k <= PS_KNN_MAX_K; B <= 65535, N <= 2^24.  Deterministic.
+ */
+int ps_edge_frames_f32(const float* rot, const float* trans, const uint8_t* frame_mask, const int32_t* idx,
+                       float* local_pos, float* rel_rot, int B, int N, int k, void* stream);
+
+/*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,
  * rotate, center_at and get_local_xyz (protstruc.py:662-694, :759-788, :347-362):
  *   out = R x + t   (transpose = 0)   or   out = R^T x + t   (transpose = 1)

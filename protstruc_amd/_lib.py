@@ -104,6 +104,11 @@ SIGNATURES = {
     "ps_nearest_neighbors_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int,
                                           ctypes.c_float, _c_int, ctypes.c_void_p, _c_f32p, ctypes.c_void_p, _c_int, _c_int,
                                           _c_int, _c_stream]),
+    "ps_edge_rbf_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_int,
+                                 ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_float, _c_f32p, _c_f32p, _c_int, _c_int,
+                                 _c_int, _c_int, _c_stream]),
+    "ps_edge_frames_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int,
+                                    _c_stream]),
     "ps_rigid_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_center_of_mass_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_frames_to_backbone_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),

@@ -24,6 +24,9 @@
 //     ps_dssp_assign (K22, DSSP secondary-structure labels from them).
 // 15: ps_solvent_accessibility_f32 (K23, Shrake-Rupley solvent-accessible surface area per point).
 // 16: ps_nearest_neighbors_f32 (K24, the k nearest neighbours of every query point, sorted, with masks, keys and a cutoff).
+//     Additive to 16 (new symbols change no signature, so the number stays): ps_edge_rbf_f32 (K25, radial basis functions of
+//     the atom-pair distances along the edges of a neighbour graph), ps_edge_frames_f32 (K26, the neighbour's frame in the
+//     source residue's frame).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

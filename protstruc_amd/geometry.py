@@ -15,7 +15,8 @@ hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward
 ``backbone_hbonds`` and ``dssp`` are the DSSP hydrogen bonds and secondary-structure labels (``ops.backbone_hbonds`` /
 ``ops.dssp_assign``); ``solvent_accessibility`` is Shrake and Rupley's surface area (``ops.solvent_accessibility``);
 ``nearest_neighbors`` is the k-nearest-neighbour graph (``ops.nearest_neighbors``) and ``gather_neighbors`` the gather
-that turns its indices into edge features.
+that turns its indices into edge features; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
+features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -610,6 +611,83 @@ def gather_neighbors(values, idx, fill=0):
     at = idx.clamp(min=0).long().reshape(B, Q * k, *([1] * (values.ndim - 2))).expand(B, Q * k, *values.shape[2:])
     out = torch.gather(values, 1, at).reshape(B, Q, k, *values.shape[2:])
     return torch.where(real.reshape(B, Q, k, *([1] * (values.ndim - 2))), out, torch.full_like(out, fill))
+
+
+BACKBONE_PAIRS = tuple((a, b) for a in range(5) for b in range(5))   # all ordered pairs of N, CA, C, O, CB: ProteinMPNN's 25
+
+
+def rbf_centers(n_rbf: int = 16, d_min: float = 2.0, d_max: float = 22.0):
+    """``(centers, sigma)`` of ``n_rbf`` Gaussians spread evenly over [d_min, d_max]: ``centers`` is a float32 array of
+    shape (n_rbf,) on the host -- the kernel takes it as an argument --, the linspace computed in double and rounded once,
+    and ``sigma = (d_max - d_min) / n_rbf``, a float
+    -- ProteinMPNN's choice (16 centres from 2 to 22 A, sigma 1.25)."""
+    if isinstance(n_rbf, bool) or not isinstance(n_rbf, (int, np.integer)) or not 1 <= n_rbf <= ops.EDGE_MAX_RBF:
+        raise ValueError(f"n_rbf must be an integer in 1 .. {ops.EDGE_MAX_RBF}, got {n_rbf!r}")
+    if not float(d_max) > float(d_min):
+        raise ValueError(f"d_max must be above d_min, got {d_min} and {d_max}")
+    centers = np.linspace(float(d_min), float(d_max), int(n_rbf), dtype=np.float64).astype(np.float32)
+    return centers, (float(d_max) - float(d_min)) / int(n_rbf)
+
+
+def _edge_call(named, run):
+    """What the two edge-feature functions share: numpy or tensors in (``named``: (name, value) pairs, the first one
+    deciding the device the results come back on), ``run(**prepared)`` -> a tuple of tensors or None, the same out."""
+    given = [(name, t) for name, t in named if t is not None]
+    for name, t in given:
+        if not isinstance(t, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{name} must be a tensor or an ndarray")
+    home = given[0][1].device if isinstance(given[0][1], torch.Tensor) else None
+    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
+    out = run(**dict(zip((name for name, _ in given), prepped)))
+    return tuple(None if t is None else _finish(t if home is None else t.to(home), ft) for t in out)
+
+
+def edge_distance_features(xyz, idx, atom_mask=None, pairs=BACKBONE_PAIRS, centers=None, sigma=None, return_dist=False):
+    """Radial basis functions of the atom-pair distances along the edges of a neighbour graph: ``rbf`` (B,N,k,P*R) fp32
+    or, with ``return_dist``, ``(rbf, dist)`` with ``dist`` (B,N,k,P).  ``xyz`` is (B,N,A,3); ``idx`` (B,N,k) are the
+    neighbour lists of ``nearest_neighbors`` on the residues (``Neighbors.idx``; any entry outside [0, N), the -1 of the
+    padding included, is padding); ``pairs`` are (slot on the source residue, slot on the neighbour) -- by default all 25
+    ordered pairs of the first five slots, N, CA, C, O, CB --; ``centers`` (R,) and ``sigma`` default to ``rbf_centers()``
+    (16 centres over 2 .. 22 A, sigma 1.25), and one given without the other is refused.
+    ``rbf[..., p*R + c] = exp(-((dist_p - centers[c]) / sigma)^2)`` with ``dist`` the distance computed in double on the
+    float32 coordinates and rounded once.  Both are exactly 0 at the padding and where either atom is outside
+    ``atom_mask`` (B,N,A), and NaN there never reaches the result.  One HIP kernel (``ops.edge_rbf``): the gathered
+    (B,N,k,A,3) coordinates and the broadcast (B,N,k,P,R) intermediates of the composed route are never built.
+    numpy in -> numpy out; tensors come back on the device of ``xyz``, CPU tensors included.
+
+    Not differentiable: the outputs carry no graph, and no backward kernel exists.  The differentiable route stays
+    ``gather_neighbors`` and plain torch on what it returns."""
+    if (centers is None) != (sigma is None):
+        raise ValueError("centers and sigma come together (rbf_centers() returns both)")
+    if centers is None:
+        centers, sigma = rbf_centers()
+    pairs = [tuple(p) for p in pairs]
+    if any(len(p) != 2 for p in pairs):
+        raise ValueError("pairs must be (slot on the source residue, slot on the neighbour) pairs")
+    dist, rbf = _edge_call((("xyz", xyz), ("idx", idx), ("atom_mask", atom_mask)),
+                           lambda xyz, idx, atom_mask=None: ops.edge_rbf(
+                               xyz, idx, atom_mask, pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs],
+                               centers=centers, sigma=sigma, want_dist=bool(return_dist)))
+    return (rbf, dist) if return_dist else rbf
+
+
+class EdgeFrames(NamedTuple):
+    """The neighbours' frames in the source residues' frames (``edge_frame_features``)."""
+    local_pos: torch.Tensor   # (B,N,k,3) fp32: R_i^T (t_j - t_i)
+    rel_rot: torch.Tensor     # (B,N,k,3,3) fp32: R_i^T R_j
+
+
+def edge_frame_features(rot, trans, idx, frame_mask=None) -> EdgeFrames:
+    """Every neighbour's position and orientation in the source residue's frame (Ingraham et al. 2019; GVP, PiFold,
+    Chroma): ``EdgeFrames(local_pos (B,N,k,3) = R_i^T (t_j - t_i), rel_rot (B,N,k,3,3) = R_i^T R_j)``.  ``rot`` (B,N,3,3)
+    has the basis vectors as columns and ``trans`` is (B,N,3), as ``backbone_frames`` returns them; ``idx`` (B,N,k) are
+    the neighbour lists of ``nearest_neighbors`` (any entry outside [0, N) is padding).  Evaluated in double on the
+    float32 inputs in a fixed order and rounded once, so defined bit for bit; exactly 0 at the padding and where i or j
+    is outside ``frame_mask`` (B,N), and NaN there never reaches the result.  One HIP kernel (``ops.edge_frames``).
+    numpy in -> numpy out; tensors come back on the device of ``rot``, CPU tensors included.
+
+    Not differentiable: the outputs carry no graph.  The differentiable route stays ``gather_neighbors`` and plain torch."""
+    return EdgeFrames(*_edge_call((("rot", rot), ("trans", trans), ("idx", idx), ("frame_mask", frame_mask)), ops.edge_frames))
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

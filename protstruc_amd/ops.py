@@ -1599,6 +1599,143 @@ def nearest_neighbors(points: torch.Tensor, k: int, point_mask: Optional[torch.T
     return idx, dist, count
 
 
+EDGE_MAX_PAIRS = 64   # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
+EDGE_MAX_RBF = 64     # PS_EDGE_MAX_RBF: the centres travel in the kernel's arguments
+
+
+def _check_neighbor_idx(idx, B: int, N: int, like: str) -> int:
+    """k of the neighbour lists ``idx`` (B,N,k) of ``nearest_neighbors`` on the N axis of ``like``; ValueError otherwise."""
+    shape = tuple(idx.shape)
+    if len(shape) != 3 or shape[:2] != (B, N):
+        raise ValueError(f"idx must have shape ({B}, {N}, k) to match {like}, got {shape}")
+    if not _is_integer_tensor(idx):
+        raise ValueError(f"idx must be an integer tensor, got {idx.dtype}")
+    if not 1 <= shape[2] <= KNN_MAX_K:
+        raise ValueError(f"idx must hold 1 .. {KNN_MAX_K} neighbours per residue, got {shape[2]}")
+    return shape[2]
+
+
+def _idx32(idx: torch.Tensor, N: int) -> torch.Tensor:
+    """``idx`` as contiguous int32 for the edge kernels, to which every value outside [0, N) is padding: wider integers
+    are clamped to [-1, N] first, so that none wraps into the range."""
+    _require_device(idx, "idx")
+    if idx.dtype != torch.int32:
+        idx = idx.clamp(-1, N).to(torch.int32)
+    return idx.contiguous()
+
+
+def _host_f32(values, name: str) -> np.ndarray:
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    try:
+        arr = np.asarray(values, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a sequence of numbers") from None
+    if arr.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional, got shape {arr.shape}")
+    return arr
+
+
+def check_edge_rbf_shapes(xyz, idx, atom_mask=None, pair_i=(), pair_j=(), centers=(), sigma=1.0, want_dist=True,
+                          want_rbf=True) -> None:
+    """Shape rules of ``edge_rbf``, on shapes, dtypes, devices, the host tables and the scalar only (no launch):
+    ValueError.  ``idx`` (B,N,k) integers with ``1 <= k <= KNN_MAX_K``; ``pair_i`` and ``pair_j`` equally long, 1 ..
+    ``EDGE_MAX_PAIRS`` atom slots in [0, A); 1 .. ``EDGE_MAX_RBF`` ``centers``; ``sigma`` positive and finite; one of
+    the two outputs wanted."""
+    B, N, A = _xyz_dims(xyz)
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if N > 2 ** 24:
+        raise ValueError(f"at most 2^24 residues per structure, got {N}")
+    _check_neighbor_idx(idx, B, N, f"xyz {(B, N, A, 3)}")
+    _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", (B, N, A, 3))
+    try:
+        slots_i, slots_j = [int(s) for s in pair_i], [int(s) for s in pair_j]
+    except (TypeError, ValueError):
+        raise ValueError("pair_i and pair_j must be sequences of atom slots") from None
+    if len(slots_i) != len(slots_j) or not 1 <= len(slots_i) <= EDGE_MAX_PAIRS:
+        raise ValueError(f"pair_i and pair_j must be equally long, 1 .. {EDGE_MAX_PAIRS} atom slots each, got "
+                         f"{len(slots_i)} and {len(slots_j)}")
+    _check_atom_slots(A, *slots_i, *slots_j)
+    R = _host_f32(centers, "centers").shape[0]
+    if not 1 <= R <= EDGE_MAX_RBF:
+        raise ValueError(f"centers must hold 1 .. {EDGE_MAX_RBF} values, got {R}")
+    _check_scalar(sigma, "sigma", "positive")
+    if not (want_dist or want_rbf):
+        raise ValueError("nothing to compute: want_dist and want_rbf are both False")
+    _same_device(xyz, idx=idx, atom_mask=atom_mask)
+
+
+def edge_rbf(xyz: torch.Tensor, idx: torch.Tensor, atom_mask: Optional[torch.Tensor] = None, *, pair_i: Sequence[int],
+             pair_j: Sequence[int], centers, sigma: float, want_dist: bool = True, want_rbf: bool = True):
+    """K25.  Radial basis functions of the atom-pair distances along the edges of a neighbour graph, fused: ``(dist
+    (B,N,k,P) fp32, rbf (B,N,k,P*R) fp32)``, None for an output not wanted.  ``xyz`` (B,N,A,3); ``idx`` (B,N,k) the
+    neighbour lists of ``nearest_neighbors`` on the same N axis -- any entry outside [0, N) is padding --; pair p is atom
+    slot ``pair_i[p]`` of the source residue against slot ``pair_j[p]`` of the neighbour; ``centers`` are R values.
+    ``dist = sqrt((dx*dx + dy*dy) + dz*dz)`` in double on the float32 inputs, rounded once (K24's distance, defined bit
+    for bit); ``rbf[..., p*R + c] = exp(-((dist - centers[c]) / sigma)^2)`` in float32, within 1e-6 absolute of the
+    float64 value.  Both are exactly 0 at the padding and where either atom is outside ``atom_mask`` (B,N,A; None =
+    all); NaN under the mask never reaches arithmetic.  Nothing of the size of the gathered coordinates or of a
+    broadcast intermediate is built; every element is written; deterministic (include/protstruc_hip.h)."""
+    check_edge_rbf_shapes(xyz, idx, atom_mask, pair_i, pair_j, centers, sigma, want_dist, want_rbf)
+    x, am = _f32c(xyz, "xyz"), _u8c(atom_mask, "atom_mask")
+    B, N, A = x.shape[:3]
+    nb = _idx32(idx, N)
+    k = nb.shape[2]
+    cen = _host_f32(centers, "centers")
+    P, R = len(pair_i), cen.shape[0]
+    ints = ctypes.c_int * P
+    with _on(x.device):
+        # the kernel writes every element; an empty tensor has no device pointer and nothing is launched for it
+        dist = torch.empty(B, N, k, P, dtype=torch.float32, device=x.device) if want_dist else None
+        rbf = torch.empty(B, N, k, P * R, dtype=torch.float32, device=x.device) if want_rbf else None
+        if B and N:
+            _launch("ps_edge_rbf_f32", _ptr(x), _ptr(am), _ptr(nb), ints(*(int(s) for s in pair_i)),
+                    ints(*(int(s) for s in pair_j)), P, (ctypes.c_float * R)(*cen.tolist()), R, float(sigma), _ptr(dist),
+                    _ptr(rbf), B, N, A, k, _stream(x))
+    return dist, rbf
+
+
+def check_edge_frames_shapes(rot, trans, idx, frame_mask=None, want_pos=True, want_rot=True) -> None:
+    """Shape rules of ``edge_frames``, on shapes, dtypes and devices only (no launch): ValueError."""
+    shape = tuple(rot.shape)
+    if len(shape) != 4 or shape[2:] != (3, 3):
+        raise ValueError(f"rot must have shape (batch, frames, 3, 3), got {shape}")
+    B, N = shape[:2]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if N > 2 ** 24:
+        raise ValueError(f"at most 2^24 frames per structure, got {N}")
+    _check_float_tensor(rot, shape, "rot", f"rot {shape}")
+    _check_float_tensor(trans, (B, N, 3), "trans", f"rot {shape}")
+    _check_neighbor_idx(idx, B, N, f"rot {shape}")
+    _check_optional(frame_mask, (B, N), "frame_mask", "rot", shape)
+    if not (want_pos or want_rot):
+        raise ValueError("nothing to compute: want_pos and want_rot are both False")
+    _same_device(rot, trans=trans, idx=idx, frame_mask=frame_mask)
+
+
+def edge_frames(rot: torch.Tensor, trans: torch.Tensor, idx: torch.Tensor, frame_mask: Optional[torch.Tensor] = None, *,
+                want_pos: bool = True, want_rot: bool = True):
+    """K26.  The neighbour's frame in the source residue's frame along the edges of a neighbour graph: ``(local_pos
+    (B,N,k,3), rel_rot (B,N,k,3,3))`` fp32, None for an output not wanted.  ``rot`` (B,N,3,3) has the basis vectors as
+    columns, as ``frames`` returns it, ``trans`` is (B,N,3); ``idx`` (B,N,k) as for ``edge_rbf``.  ``local_pos = R_i^T
+    (t_j - t_i)`` and ``rel_rot = R_i^T R_j``, evaluated in double on the float32 inputs in the order stated in
+    include/protstruc_hip.h and rounded once: defined bit for bit.  Exactly 0 at the padding and where i or j is outside
+    ``frame_mask`` (B,N; None = all); frames there are never read.  Every element is written; deterministic."""
+    check_edge_frames_shapes(rot, trans, idx, frame_mask, want_pos, want_rot)
+    r, t, fm = _f32c(rot, "rot"), _f32c(trans, "trans"), _u8c(frame_mask, "frame_mask")
+    B, N = r.shape[:2]
+    nb = _idx32(idx, N)
+    k = nb.shape[2]
+    with _on(r.device):
+        pos = torch.empty(B, N, k, 3, dtype=torch.float32, device=r.device) if want_pos else None
+        rel = torch.empty(B, N, k, 3, 3, dtype=torch.float32, device=r.device) if want_rot else None
+        if B and N:
+            _launch("ps_edge_frames_f32", _ptr(r), _ptr(t), _ptr(fm), _ptr(nb), _ptr(pos), _ptr(rel), B, N, k, _stream(r))
+    return pos, rel
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

@@ -24,7 +24,7 @@ Deliberate, documented differences from the reference (SURVEY.md quirk list):
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -35,6 +35,16 @@ from .general import ATOM
 
 def _always_tensor(x):
     return torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+
+
+class EdgeFeatures(NamedTuple):
+    """The edge features of a neighbour graph (``StructureBatch.edge_features``)."""
+    idx: torch.Tensor                   # (B,N,k) int32: the graph; -1 at the padding
+    mask: torch.Tensor                  # (B,N,k) bool: idx >= 0
+    rbf: torch.Tensor                   # (B,N,k,P*n_rbf) fp32: radial basis functions of the atom-pair distances
+    offset: torch.Tensor                # (B,N,k) int64: the class of the sequence offset
+    local_pos: Optional[torch.Tensor]   # (B,N,k,3) fp32: the neighbour's CA in the source residue's frame, or None
+    rel_rot: Optional[torch.Tensor]     # (B,N,k,3,3) fp32: the neighbour's frame in the source residue's frame, or None
 
 
 def _default_device() -> torch.device:
@@ -623,6 +633,72 @@ class StructureBatch:
             residue = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
         return geometry.nearest_neighbors(self.xyz.reshape(B, N * A, 3), k, takes_part, exclude=residue,
                                           cutoff=float("inf") if cutoff is None else cutoff)
+
+    # ------------------------------------------------------------------ edge features
+    def _edge_offsets(self, idx: torch.Tensor, max_offset: int) -> torch.Tensor:
+        """(B,N,k) int64 class of every edge of ``idx`` (padding -1): ``clip(r_i - r_j + max_offset, 0, 2 max_offset)``
+        within a chain, ``2 max_offset + 1`` across chains, 0 at the padding; ``r`` is ``residue_idx`` where the batch holds
+        one and the position along N otherwise.  Plain torch, on any device."""
+        from . import geometry
+
+        B, N = self.xyz.shape[:2]
+        if self.residue_idx is None:
+            r = torch.arange(N, device=self.device).expand(B, N)
+        else:   # the padding's NaN becomes 0; padded residues are nobody's neighbour
+            r = torch.nan_to_num(_always_tensor(self.residue_idx).to(self.device, torch.float64), nan=0.0).long()
+        chain = self._chain_keys()
+        within = geometry.gather_neighbors(chain, idx, fill=-2) == chain[:, :, None]
+        offset = (r[:, :, None] - geometry.gather_neighbors(r, idx) + max_offset).clamp(0, 2 * max_offset)
+        offset = torch.where(within, offset, torch.full_like(offset, 2 * max_offset + 1))
+        return offset.masked_fill(idx < 0, 0)
+
+    def edge_features(self, graph=None, k: int = 30, atoms=("N", "CA", "C", "O", "CB"), n_rbf: int = 16, d_min: float = 2.0,
+                      d_max: float = 22.0, frames: bool = True, max_offset: int = 32) -> EdgeFeatures:
+        """What a structure network computes on every edge of a neighbour graph, between :meth:`knn_graph` and its first
+        linear layer (ProteinMPNN, Structured Transformer, GVP, PiFold): ``EdgeFeatures(idx, mask, rbf, offset, local_pos,
+        rel_rot)``.
+
+        ``graph`` is a ``geometry.Neighbors`` or an index tensor (B,N,k) on the residues; None: ``self.knn_graph(k)``.
+        ``idx`` (B,N,k) int32 is the graph with every entry outside [0, N) turned into -1, the padding, and ``mask`` is
+        ``idx >= 0``.  ``rbf`` (B,N,k,P*n_rbf): ``n_rbf`` Gaussians (``geometry.rbf_centers(n_rbf, d_min, d_max)``) of the
+        distances between the P = len(atoms)^2 ordered atom pairs, pair ``p = a * len(atoms) + b`` being ``atoms[a]`` of the
+        source residue against ``atoms[b]`` of the neighbour, at ``rbf[..., p * n_rbf + c]``; exactly 0 at the padding and
+        where either atom is missing (the atom mask is the atoms present in residues of the residue mask).  ``offset``
+        (B,N,k) int64 is the class of the sequence offset: ``clip(r_i - r_j + max_offset, 0, 2 max_offset)`` within a chain
+        and ``2 max_offset + 1`` across chains, with ``r`` the batch's residue numbering (the position along N where it
+        holds none); 0 at the padding.  With ``frames``, ``local_pos`` (B,N,k,3) and ``rel_rot`` (B,N,k,3,3) are the
+        neighbour's CA and N-CA-C frame in the source residue's frame, ``R_i^T (t_j - t_i)`` and ``R_i^T R_j``, zero
+        where either residue lacks N, CA or C; otherwise both are None.  Two HIP kernels
+        (``geometry.edge_distance_features``, ``.edge_frame_features``); the offsets are plain torch.  Not differentiable
+        -- ``geometry.gather_neighbors`` is the differentiable route."""
+        from . import geometry
+
+        if isinstance(max_offset, bool) or not isinstance(max_offset, (int, np.integer)) or max_offset < 0:
+            raise ValueError(f"max_offset must be a non-negative integer, got {max_offset!r}")
+        for atom in atoms:
+            if not ATOM.is_valid(atom):
+                raise ValueError(f"Atom {atom} is not valid.")
+        slots = [int(ATOM[a]) for a in atoms]
+        A, N = self.max_n_atoms_per_residue, self.n_residues
+        if not slots or max(slots) >= A:
+            raise ValueError(f"atoms {tuple(atoms)} do not fit the {A} atom slots of this batch")
+        if graph is None:
+            graph = self.knn_graph(k)
+        idx = _always_tensor(graph.idx if isinstance(graph, geometry.Neighbors) else graph).to(self.device)
+        idx = torch.where((idx >= 0) & (idx < N), idx, torch.full_like(idx, -1)).to(torch.int32)
+        centers, sigma = geometry.rbf_centers(n_rbf, d_min, d_max)
+        present = self._present_atoms()
+        with torch.no_grad():
+            rbf = geometry.edge_distance_features(self.xyz, idx, present, pairs=[(a, b) for a in slots for b in slots],
+                                                  centers=centers, sigma=sigma)
+            local_pos = rel_rot = None
+            if frames:
+                if A < 3:
+                    raise ValueError(f"frames need the N, CA and C slots; this batch has {A} atom slots")
+                rot, trans = self.backbone_orientations_and_translations()
+                local_pos, rel_rot = geometry.edge_frame_features(rot, trans, idx, present[:, :, :3].all(dim=-1))
+            offset = self._edge_offsets(idx, int(max_offset))
+        return EdgeFeatures(idx, idx >= 0, rbf, offset, local_pos, rel_rot)
 
     def peptide_bond_violations(self, **constants) -> torch.Tensor:
         """Peptide-bond violations at every junction r -> r+1, (B,N,3): bond length |C - N'|, cos of CA-C-N', cos of

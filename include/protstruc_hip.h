@@ -704,6 +704,64 @@ int ps_edge_frames_f32(const float* rot, const float* trans, const uint8_t* fram
                        float* local_pos, float* rel_rot, int B, int N, int k, void* stream);
 
 /*
+ * K27 - K30 (additive to ABI 16) -- side-chain torsions: the chi angles of every residue, measured and set, with both
+ * gradients.  The kernels know no amino acids; two HOST tables, read and validated before the call returns, say what an
+ * angle is: chi_atoms (T,4,4) int32, the atom slots a, b, c, d of angle k of residue type t -- all -1 (no such angle) or
+ * four distinct slots in [0, A) --, and chi_last (T,4) int32: angle k turns the slots [d, last]; -1 (measured, never
+ * turned), or in [d, A) with none of a, b, c inside [d, last].  1 <= T <= PS_CHI_MAX_TYPES.  xyz (B,N,A,3);
+ * residue_type (B,N) int32, the table row of each residue: a value outside [0, T) is padding, which has no angles and
+ * never indexes the table; atom_mask (B,N,A), one byte each, NULL = every atom.  Angle k of a residue is DEFINED where
+ * the table has it and all four atoms are in the mask; coordinates outside the mask never reach arithmetic.  All
+ * arithmetic is in double on the fp32 values, in the order written here (the library is built with -ffp-contract=off),
+ * with u x v = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x) and u . v = (u.x v.x + u.y v.y) + u.z v.z.
+ * One lane owns one residue; no atomics: every result repeats bit for bit.  Every tensor may start at any 4-byte
+ * aligned address.  B * N <= 2^31; 1 <= A <= 64; B = 0 or N = 0 launches nothing.
+ *
+ * K27, ps_chi_f32: chi (B,N,4) fp32 and chi_mask (B,N,4) bytes; either may be NULL, not both.
+ *   b0 = a - b     b1 = c - b     b2 = d - c     n1 = b0 x b1     n2 = b2 x b1     m = n1 x n2
+ *   x = n1 . n2    y = (m . b1) / sqrt(b1 . b1)  chi = (float)atan2(y, x)       -- the sign of mode 1 of ps_pointwise_f32, IUPAC
+ * An undefined angle gives exact 0 and mask 0.
+ *
+ * K28, ps_chi_backward_f32: grad_xyz (B,N,A,3) from grad_chi (B,N,4).  With l = sqrt(b1 . b1), p = (b0 . b1) / (b1 . b1),
+ * q = (b2 . b1) / (b1 . b1):
+ *   ga = (l / (n1 . n1)) n1     gd = -(l / (n2 . n2)) n2     gb = (p - 1) ga + q gd     gc = -(p ga) - (1 + q) gd
+ * each times (double)grad_chi[k]; an atom's contributions are summed in the order k = 0..3 and rounded once.  The whole
+ * (A,3) row of every residue is written, exact zeros in the slots no defined angle reads; grad_chi is not read at an
+ * undefined angle.
+ */
+#define PS_CHI_MAX_TYPES 32
+int ps_chi_f32(const float* xyz, const uint8_t* atom_mask, const int32_t* residue_type, const int32_t* chi_atoms, int T,
+               float* chi, uint8_t* chi_mask, int B, int N, int A, void* stream);
+int ps_chi_backward_f32(const float* xyz, const uint8_t* atom_mask, const int32_t* residue_type,
+                        const int32_t* chi_atoms, int T, const float* grad_chi, float* grad_xyz, int B, int N, int A,
+                        void* stream);
+
+/*
+ * K29, ps_chi_set_f32: out (B,N,A,3), the coordinates with the chi angles turned to chi (B,N,4) -- by chi if relative is
+ * non-zero.  chi_select (B,N,4), one byte each, NULL = every angle.  For k = 0, 1, 2, 3 in this order, where angle k is
+ * defined, chi_last[t][k] >= 0 and chi_select is NULL or non-zero, on the residue's CURRENT coordinates (doubles between
+ * the steps):
+ *   delta = (double)chi[k] - phi, phi the angle of K27 before its rounding;   delta = (double)chi[k] if relative
+ *   e = c - b     u = e / sqrt(e . e)     cs = cos(delta)     sn = sin(delta)
+ *   for every slot s in [d, last] inside the mask:   v = p_s - c     p_s = ((c + v cs) + (u x v) sn) + u ((u . v) (1 - cs))
+ * Each result is rounded to fp32 once, at the store.  Every other float of out, and every float of a residue with nothing
+ * to turn, is the input's bit pattern -- the NaN of a missing atom, the padding.  chi[k] is not read where it is not
+ * used.  out may not alias xyz.
+ *
+ * K30, ps_chi_set_backward_f32: grad_chi (B,N,4) from grad_out (B,N,A,3) and the coordinates `out` that K29 wrote, with
+ * K29's atom_mask, residue_type, tables and chi_select:
+ *   grad_chi[k] = sum over the slots s in [d, last] inside the mask, in slot order, of (u x (p_s - c)) . g_s
+ * with u and c of angle k as above, on `out`; exact 0 at an angle K29 did not turn.  This is the whole derivative in both
+ * modes: a turn about an inner axis carries the outer axes along rigidly.  xyz is a constant of K29.
+ */
+int ps_chi_set_f32(const float* xyz, const uint8_t* atom_mask, const int32_t* residue_type, const int32_t* chi_atoms,
+                   const int32_t* chi_last, int T, const float* chi, const uint8_t* chi_select, int relative,
+                   float* out, int B, int N, int A, void* stream);
+int ps_chi_set_backward_f32(const float* out, const uint8_t* atom_mask, const int32_t* residue_type,
+                            const int32_t* chi_atoms, const int32_t* chi_last, int T, const uint8_t* chi_select,
+                            const float* grad_out, float* grad_chi, int B, int N, int A, void* stream);
+
+/*
  * Rigid-body ops.  ps_rigid_f32 replaces StructureBatch.translate,
  * rotate, center_at and get_local_xyz (protstruc.py:662-694, :759-788, :347-362):
  *   out = R x + t   (transpose = 0)   or   out = R^T x + t   (transpose = 1)

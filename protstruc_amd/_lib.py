@@ -109,6 +109,15 @@ SIGNATURES = {
                                  _c_int, _c_int, _c_stream]),
     "ps_edge_frames_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int,
                                     _c_stream]),
+    # chi_atoms (T,4,4) and chi_last (T,4) are HOST arrays of ints (ctypes arrays, or their addresses)
+    "ps_chi_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_u8p, _c_int, _c_int,
+                            _c_int, _c_stream]),
+    "ps_chi_backward_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p, _c_int,
+                                     _c_int, _c_int, _c_stream]),
+    "ps_chi_set_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p,
+                                _c_u8p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
+    "ps_chi_set_backward_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_int,
+                                         _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
     "ps_rigid_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_center_of_mass_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "ps_frames_to_backbone_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),

@@ -26,7 +26,9 @@
 // 16: ps_nearest_neighbors_f32 (K24, the k nearest neighbours of every query point, sorted, with masks, keys and a cutoff).
 //     Additive to 16 (new symbols change no signature, so the number stays): ps_edge_rbf_f32 (K25, radial basis functions of
 //     the atom-pair distances along the edges of a neighbour graph), ps_edge_frames_f32 (K26, the neighbour's frame in the
-//     source residue's frame).
+//     source residue's frame); ps_chi_f32 / ps_chi_backward_f32 (K27 / K28, the side-chain torsions chi1 - chi4 and their
+//     gradient), ps_chi_set_f32 / ps_chi_set_backward_f32 (K29 / K30, the side chains turned to given angles, and the
+//     gradient towards the angles).
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 
 extern "C" const char* ps_error_string(int code) { return hipGetErrorString(static_cast<hipError_t>(code)); }

@@ -73,3 +73,63 @@ def max_accessibility_table():
     for one, value in _MAX_ACCESSIBILITY.items():
         table[ONE_TO_INDEX[one]] = value
     return table
+
+
+# the atoms after CB along which chi1 .. chi4 are defined: chi1 = N CA CB X, chi2 = CA CB X Y, chi3 = CB X Y Z, chi4 = X Y Z W
+# (IUPAC-IUB 1970; the table of AlphaFold 2's torsion-angle loss).  ALA, GLY and the unknown type X have none.
+_CHI_CHAIN = {
+    "ARG": "CG CD NE CZ", "LYS": "CG CD CE NZ", "MET": "CG SD CE", "GLN": "CG CD OE1", "GLU": "CG CD OE1",
+    "ASN": "CG OD1", "ASP": "CG OD1", "HIS": "CG ND1", "LEU": "CG CD1", "PHE": "CG CD1", "TRP": "CG CD1", "TYR": "CG CD1",
+    "ILE": "CG1 CD1", "PRO": "CG CD", "CYS": "SG", "SER": "OG", "THR": "OG1", "VAL": "CG1",
+}
+# (residue, angle): chi and chi + pi name the same structure (the two atoms the angle ends in are equivalent)
+_CHI_PI_PERIODIC = (("ASP", 1), ("GLU", 2), ("PHE", 1), ("TYR", 1))
+
+
+def chi_atom_table():
+    """The four atoms of every side-chain torsion: a (21, 4, 4) int32 tensor indexed [``pdb.ONE_TO_INDEX`` code][chi][a, b,
+    c, d], atom slots from ``pdb.ATOM_SLOT``, -1 where a residue type has no such angle.  chi1 is N CA CB X, chi2 CA CB X
+    Y, chi3 CB X Y Z and chi4 X Y Z W along the type's chain of atoms after CB (CG CD NE CZ for ARG, ..., SG for CYS)."""
+    import torch
+
+    from .pdb import ATOM_SLOT, ONE_TO_INDEX, THREE_TO_ONE
+
+    table = torch.full((len(ONE_TO_INDEX), 4, 4), -1, dtype=torch.int32)
+    for three, chain in _CHI_CHAIN.items():
+        names = ["N", "CA", "CB"] + chain.split()
+        for k in range(len(names) - 3):
+            table[ONE_TO_INDEX[THREE_TO_ONE[three]], k] = torch.tensor([ATOM_SLOT[three][a] for a in names[k:k + 4]],
+                                                                       dtype=torch.int32)
+    return table
+
+
+def chi_last_table():
+    """The last atom slot every side-chain torsion moves: a (21, 4) int32 tensor.  Turning chi k moves the slots from its
+    fourth atom through the last side-chain slot of the type, both inclusive (ILE's chi2 moves CD1 alone), never OXT in
+    slot 14.  -1 where there is no angle, and for both angles of proline: they can be measured, but turning them would
+    open the ring."""
+    import torch
+
+    from .pdb import ATOM_SLOT, ONE_TO_INDEX, THREE_TO_ONE
+
+    atoms = chi_atom_table()
+    table = torch.full((len(ONE_TO_INDEX), 4), -1, dtype=torch.int32)
+    for three in _CHI_CHAIN:
+        if three == "PRO":
+            continue
+        row = ONE_TO_INDEX[THREE_TO_ONE[three]]
+        side_chain_end = max(slot for name, slot in ATOM_SLOT[three].items() if name != "OXT")
+        table[row] = torch.where(atoms[row, :, 3] >= 0, torch.tensor(side_chain_end, dtype=torch.int32), table[row])
+    return table
+
+
+def chi_pi_periodic_table():
+    """(21, 4) bool: chi and chi + pi name the same structure -- ASP chi2, GLU chi3, PHE chi2 and TYR chi2."""
+    import torch
+
+    from .pdb import ONE_TO_INDEX, THREE_TO_ONE
+
+    table = torch.zeros(len(ONE_TO_INDEX), 4, dtype=torch.bool)
+    for three, k in _CHI_PI_PERIODIC:
+        table[ONE_TO_INDEX[THREE_TO_ONE[three]], k] = True
+    return table

@@ -16,7 +16,9 @@ hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward
 ``ops.dssp_assign``); ``solvent_accessibility`` is Shrake and Rupley's surface area (``ops.solvent_accessibility``);
 ``nearest_neighbors`` is the k-nearest-neighbour graph (``ops.nearest_neighbors``) and ``gather_neighbors`` the gather
 that turns its indices into edge features; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
-features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``).
+features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``); ``side_chain_torsions``
+measures chi1 .. chi4, differentiably in the coordinates, and ``set_side_chain_torsions`` turns the side chains to given
+angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -688,6 +690,99 @@ def edge_frame_features(rot, trans, idx, frame_mask=None) -> EdgeFrames:
 
     Not differentiable: the outputs carry no graph.  The differentiable route stays ``gather_neighbors`` and plain torch."""
     return EdgeFrames(*_edge_call((("rot", rot), ("trans", trans), ("idx", idx), ("frame_mask", frame_mask)), ops.edge_frames))
+
+
+class SideChainTorsions(NamedTuple):
+    """The side-chain torsions chi1 .. chi4 of every residue (``side_chain_torsions``)."""
+    chi: torch.Tensor    # (B,N,4) fp32, radians in [-pi, pi]; exactly 0 where undefined
+    mask: torch.Tensor   # (B,N,4) bool: the residue type has the angle and its four atoms are present
+
+
+class _SideChainTorsions(torch.autograd.Function):
+    """ops.chi with ops.chi_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, xyz, residue_type, atom_mask, chi_atoms):
+        ctx.chi_atoms = chi_atoms
+        ctx.save_for_backward(xyz, residue_type, atom_mask)
+        ctx.dtype = xyz.dtype
+        chi, mask = ops.chi(xyz, residue_type, atom_mask, chi_atoms=chi_atoms)
+        ctx.mark_non_differentiable(mask)
+        return chi, mask
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_chi, _grad_mask):
+        xyz, residue_type, atom_mask = ctx.saved_tensors
+        grad = ops.chi_backward(xyz, residue_type, grad_chi, atom_mask, chi_atoms=ctx.chi_atoms)
+        return grad.to(ctx.dtype), None, None, None
+
+
+def side_chain_torsions(xyz, residue_type, atom_mask=None, chi_atoms=None) -> SideChainTorsions:
+    """The side-chain torsions chi1 .. chi4 of ``xyz`` (B,N,A,3): ``SideChainTorsions(chi (B,N,4) fp32, mask (B,N,4)
+    bool)``.  ``residue_type`` (B,N) integers selects each residue's row of ``chi_atoms`` (T,4,4), the atom slots a, b,
+    c, d of every angle (None: ``general.chi_atom_table()``, indexed by ``pdb.ONE_TO_INDEX``); a type outside [0, T) is
+    padding.  An angle is defined where the table has it and its four atoms are in ``atom_mask`` (B,N,A; None = all):
+    ``chi = atan2((m . b1) / |b1|, n1 . n2)`` with ``b0 = a - b, b1 = c - b, b2 = d - c, n1 = b0 x b1, n2 = b2 x b1, m = n1 x
+    n2`` -- the sign of ``dihedral`` and of IUPAC --, evaluated in double on the float32 coordinates and rounded once.
+    Undefined angles are exactly 0 with mask False, value and gradient, whatever NaN sits under the mask.
+    Differentiable with respect to ``xyz`` (nothing else); one HIP kernel forwards (``ops.chi``) and one backwards
+    (``ops.chi_backward``, deterministic).  No double backward.  Tensors on the GPU."""
+    if chi_atoms is None:
+        from .general import chi_atom_table
+        chi_atoms = chi_atom_table()
+    ops.check_chi_shapes(xyz, residue_type, atom_mask, chi_atoms)
+    return SideChainTorsions(*_SideChainTorsions.apply(xyz, residue_type, atom_mask, chi_atoms))
+
+
+class _SetSideChainTorsions(torch.autograd.Function):
+    """ops.chi_set with ops.chi_set_backward as its vector-Jacobian product towards the angles."""
+
+    @staticmethod
+    def forward(ctx, xyz, chi, residue_type, atom_mask, chi_select, relative, chi_atoms, chi_last):
+        out = ops.chi_set(xyz, chi, residue_type, atom_mask, chi_select, chi_atoms=chi_atoms, chi_last=chi_last,
+                          relative=relative)
+        ctx.tables = dict(chi_atoms=chi_atoms, chi_last=chi_last)
+        ctx.save_for_backward(out, residue_type, atom_mask, chi_select)
+        ctx.dtype = chi.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        out, residue_type, atom_mask, chi_select = ctx.saved_tensors
+        grad = ops.chi_set_backward(out, grad_out, residue_type, atom_mask, chi_select, **ctx.tables)
+        return None, grad.to(ctx.dtype), None, None, None, None, None, None
+
+
+def set_side_chain_torsions(xyz, chi, residue_type, atom_mask=None, chi_select=None, relative=False, chi_atoms=None,
+                            chi_last=None):
+    """``xyz`` (B,N,A,3) with the side chains turned to the angles ``chi`` (B,N,4), or by them with ``relative``: a new
+    (B,N,A,3) fp32 tensor.  ``chi_atoms`` (T,4,4) names the four atoms of every angle and ``chi_last`` (T,4) the last atom
+    slot it moves (None: ``general.chi_atom_table()`` and ``general.chi_last_table()``); ``residue_type`` (B,N) selects
+    the rows, a type outside [0, T) is padding.  For k = 0..3 in this order, where the angle is defined
+    (``side_chain_torsions``), ``chi_last`` is not -1 (proline's angles are measured but never turned: that would open
+    the ring) and ``chi_select`` (B,N,4; None = all) is true, the present atoms from the angle's fourth atom through
+    ``chi_last`` are rotated about its b -> c axis by ``chi[k]`` minus the angle measured on the current coordinates (by
+    ``chi[k]`` with ``relative``), in double, rounded once.  Every other float is the input's own -- missing atoms' NaN,
+    the padding --, and ``chi`` may hold anything, NaN included, where it is not used.
+
+    Differentiable with respect to ``chi``: ``grad_chi[k] = sum_s (u_k x (p_s - c_k)) . grad_s`` over the atoms angle k
+    moved, which is the whole derivative in both modes (``ops.chi_set_backward``, one HIP kernel, deterministic; exactly
+    0 at angles that were not turned).  NOT differentiable with respect to ``xyz``, which is a constant of this
+    function: an ``xyz`` that requires grad raises ValueError rather than lose its gradient silently -- pass
+    ``xyz.detach()``.  No double backward.  Tensors on the GPU."""
+    if chi_atoms is None:
+        from .general import chi_atom_table
+        chi_atoms = chi_atom_table()
+    if chi_last is None:
+        from .general import chi_last_table
+        chi_last = chi_last_table()
+    ops.check_chi_set_shapes(xyz, chi, residue_type, atom_mask, chi_select, chi_atoms, chi_last)
+    if isinstance(xyz, torch.Tensor) and xyz.requires_grad:
+        raise ValueError("set_side_chain_torsions: xyz is a constant here and gets no gradient, but it requires grad; "
+                         "pass xyz.detach() (only chi is differentiable)")
+    return _SetSideChainTorsions.apply(xyz, chi, residue_type, atom_mask, chi_select, bool(relative), chi_atoms, chi_last)
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

@@ -1736,6 +1736,210 @@ def edge_frames(rot: torch.Tensor, trans: torch.Tensor, idx: torch.Tensor, frame
     return pos, rel
 
 
+CHI_MAX_TYPES = 32   # PS_CHI_MAX_TYPES of include/protstruc_hip.h: the tables travel in the kernel's arguments
+
+
+def _host_i32_table(values, shape_tail, name: str) -> np.ndarray:
+    """A host table of the chi kernels as a contiguous int32 array of shape (T, *shape_tail), 1 <= T <= CHI_MAX_TYPES."""
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    try:
+        arr = np.asarray(values)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be an integer array of shape (types, {', '.join(map(str, shape_tail))})") from None
+    if arr.ndim != 1 + len(shape_tail) or arr.shape[1:] != tuple(shape_tail) or arr.dtype.kind not in "iu":
+        raise ValueError(f"{name} must be an integer array of shape (types, {', '.join(map(str, shape_tail))}), got "
+                         f"{arr.dtype} {arr.shape}")
+    if not 1 <= arr.shape[0] <= CHI_MAX_TYPES:
+        raise ValueError(f"{name} must hold 1 .. {CHI_MAX_TYPES} residue types, got {arr.shape[0]}")
+    return np.ascontiguousarray(arr.astype(np.int64).clip(-2, 2 ** 31 - 1).astype(np.int32))
+
+
+def _chi_tables(chi_atoms, chi_last, A: int, with_last: bool):
+    """The validated host tables (chi_atoms (T,4,4) int32, chi_last (T,4) int32 or None): the library's own rules."""
+    if chi_atoms is None or (with_last and chi_last is None):
+        raise ValueError("chi_atoms" + (" and chi_last are" if with_last else " is") + " required "
+                         "(general.chi_atom_table()" + (", general.chi_last_table())" if with_last else ")"))
+    atoms = _host_i32_table(chi_atoms, (4, 4), "chi_atoms")
+    T = atoms.shape[0]
+    none = (atoms == -1).all(-1)
+    inside = ((atoms >= 0) & (atoms < A)).all(-1)
+    distinct = np.array([[len(set(row.tolist())) == 4 for row in per_type] for per_type in atoms])
+    if not (none | (inside & distinct)).all():
+        t, k = np.argwhere(~(none | (inside & distinct)))[0]
+        raise ValueError(f"chi_atoms[{t}][{k}] = {atoms[t, k].tolist()} must be all -1 or four distinct atom slots in [0, {A})")
+    if not with_last:
+        return atoms, None
+    last = _host_i32_table(chi_last, (4,), "chi_last")
+    if last.shape[0] != T:
+        raise ValueError(f"chi_last must hold the {T} residue types of chi_atoms, got {last.shape[0]}")
+    d = atoms[:, :, 3]
+    ok = (last == -1) | (~none & (last >= d) & (last < A)
+                         & ~((atoms[:, :, :3] >= d[..., None]) & (atoms[:, :, :3] <= last[..., None])).any(-1))
+    if not ok.all():
+        t, k = np.argwhere(~ok)[0]
+        raise ValueError(f"chi_last[{t}][{k}] = {last[t, k]} must be -1, or in [d, {A}) with none of a, b, c of "
+                         f"chi_atoms[{t}][{k}] = {atoms[t, k].tolist()} inside [d, last]")
+    return atoms, last
+
+
+def _check_residue_type(residue_type, B: int, N: int, like: str) -> None:
+    if tuple(residue_type.shape) != (B, N):
+        raise ValueError(f"residue_type must have shape {(B, N)} to match {like}, got {tuple(residue_type.shape)}")
+    if not _is_integer_tensor(residue_type):
+        raise ValueError(f"residue_type must be an integer tensor, got {residue_type.dtype}")
+
+
+def _chi_dims(xyz) -> Tuple[int, int, int]:
+    B, N, A = _xyz_dims(xyz)
+    if B * N > 2 ** 31:
+        raise ValueError(f"at most 2^31 residues per call, got {B * N}")
+    if not 1 <= A <= 64:
+        raise ValueError(f"1 .. 64 atom slots per residue, got {A}")
+    return B, N, A
+
+
+def _type32(residue_type: torch.Tensor, T: int) -> torch.Tensor:
+    """``residue_type`` as contiguous int32 for the chi kernels, to which every value outside [0, T) is padding: wider
+    integers are clamped to [-1, T] first, so that none wraps into the range."""
+    _require_device(residue_type, "residue_type")
+    if residue_type.dtype != torch.int32:
+        residue_type = residue_type.clamp(-1, T).to(torch.int32)
+    return residue_type.contiguous()
+
+
+def _ints(table: Optional[np.ndarray]):
+    return None if table is None else (ctypes.c_int * table.size)(*table.ravel().tolist())
+
+
+def check_chi_shapes(xyz, residue_type, atom_mask=None, chi_atoms=None, grad_chi=None, want_chi=True, want_mask=True) -> None:
+    """Shape rules of ``chi`` / ``chi_backward``, on shapes, dtypes, devices and the host table only (no launch):
+    ValueError.  ``xyz`` (B,N,A,3) floating point with ``B * N <= 2^31`` and ``1 <= A <= 64``; ``residue_type`` (B,N)
+    integers; ``atom_mask`` (B,N,A); ``chi_atoms`` (T,4,4) integers, ``1 <= T <= CHI_MAX_TYPES``, every angle all -1 or
+    four distinct slots in [0, A); ``grad_chi`` (B,N,4) floating point; one of the two outputs wanted."""
+    _checked_chi(xyz, residue_type, atom_mask, chi_atoms, grad_chi, want_chi, want_mask)
+
+
+def _checked_chi(xyz, residue_type, atom_mask, chi_atoms, grad_chi, want_chi=True, want_mask=True) -> np.ndarray:
+    """``check_chi_shapes``; returns the validated host table."""
+    B, N, A = _chi_dims(xyz)
+    shape = (B, N, A, 3)
+    _check_residue_type(residue_type, B, N, f"xyz {shape}")
+    _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
+    atoms, _ = _chi_tables(chi_atoms, None, A, False)
+    if grad_chi is not None:
+        _check_float_tensor(grad_chi, (B, N, 4), "grad_chi", f"xyz {shape}")
+    if not (want_chi or want_mask):
+        raise ValueError("nothing to compute: want_chi and want_mask are both False")
+    _same_device(xyz, residue_type=residue_type, atom_mask=atom_mask, grad_chi=grad_chi)
+    return atoms
+
+
+def chi(xyz: torch.Tensor, residue_type: torch.Tensor, atom_mask: Optional[torch.Tensor] = None, *, chi_atoms,
+        want_chi: bool = True, want_mask: bool = True):
+    """K27.  The side-chain torsions of every residue: ``(chi (B,N,4) fp32, chi_mask (B,N,4) bool)``, None for an output
+    not wanted.  ``chi_atoms`` (T,4,4) is the host table of the four atom slots a, b, c, d of angle k of residue type t
+    (``general.chi_atom_table()``), ``residue_type`` (B,N) the row of each residue -- a value outside [0, T) is padding
+    --, ``atom_mask`` (B,N,A; None = all).  An angle is defined where the table has it and its four atoms are in the mask:
+    ``chi = atan2((m . b1) / |b1|, n1 . n2)`` with ``b0 = a - b, b1 = c - b, b2 = d - c, n1 = b0 x b1, n2 = b2 x b1, m = n1 x
+    n2`` in double on the float32 coordinates, rounded once (``geometry.dihedral``'s sign); exact 0 and mask False
+    elsewhere, whatever NaN sits under the mask (include/protstruc_hip.h)."""
+    atoms = _checked_chi(xyz, residue_type, atom_mask, chi_atoms, None, want_chi, want_mask)
+    x, am = _f32c(xyz, "xyz"), _u8c(atom_mask, "atom_mask")
+    B, N, A = x.shape[:3]
+    rt = _type32(residue_type, atoms.shape[0])
+    with _on(x.device):
+        out = torch.empty(B, N, 4, dtype=torch.float32, device=x.device) if want_chi else None
+        mask = torch.empty(B, N, 4, dtype=torch.bool, device=x.device) if want_mask else None
+        if B and N:
+            _launch("ps_chi_f32", _ptr(x), _ptr(am), _ptr(rt), _ints(atoms), atoms.shape[0], _ptr(out), _ptr(mask), B, N, A,
+                    _stream(x))
+    return out, mask
+
+
+def chi_backward(xyz: torch.Tensor, residue_type: torch.Tensor, grad_chi: torch.Tensor,
+                 atom_mask: Optional[torch.Tensor] = None, *, chi_atoms) -> torch.Tensor:
+    """K28.  Vector-Jacobian product of ``chi`` in one launch: ``grad_xyz`` (B,N,A,3) fp32 from the upstream ``grad_chi``
+    (B,N,4).  The lane that owns a residue sums the contributions of its angles per atom in double, in the order k =
+    0..3, and writes the whole row: exact zeros in the slots no defined angle reads; ``grad_chi`` is not read at an
+    undefined angle; no atomics, deterministic (include/protstruc_hip.h)."""
+    atoms = _checked_chi(xyz, residue_type, atom_mask, chi_atoms, grad_chi)
+    x, am, g = _f32c(xyz, "xyz"), _u8c(atom_mask, "atom_mask"), _f32c(grad_chi, "grad_chi")
+    B, N, A = x.shape[:3]
+    rt = _type32(residue_type, atoms.shape[0])
+    with _on(x.device):
+        out = torch.empty(B, N, A, 3, dtype=torch.float32, device=x.device)
+        if B and N:
+            _launch("ps_chi_backward_f32", _ptr(x), _ptr(am), _ptr(rt), _ints(atoms), atoms.shape[0], _ptr(g), _ptr(out),
+                    B, N, A, _stream(x))
+    return out
+
+
+def check_chi_set_shapes(xyz, chi, residue_type, atom_mask=None, chi_select=None, chi_atoms=None, chi_last=None,
+                         grad_out=None) -> None:
+    """Shape rules of ``chi_set`` / ``chi_set_backward``, on shapes, dtypes, devices and the host tables only (no
+    launch): ValueError.  As ``check_chi_shapes``, with ``chi`` (B,N,4) floating point (None for the backward pass),
+    ``chi_select`` (B,N,4), ``chi_last`` (T,4) integers -- -1, or in [d, A) with none of a, b, c inside [d, last] -- and
+    ``grad_out`` of the shape of ``xyz``."""
+    _checked_chi_set(xyz, chi, residue_type, atom_mask, chi_select, chi_atoms, chi_last, grad_out)
+
+
+def _checked_chi_set(xyz, chi, residue_type, atom_mask, chi_select, chi_atoms, chi_last, grad_out=None):
+    """``check_chi_set_shapes``; returns the validated host tables."""
+    B, N, A = _chi_dims(xyz)
+    shape = (B, N, A, 3)
+    if chi is not None:
+        _check_float_tensor(chi, (B, N, 4), "chi", f"xyz {shape}")
+    _check_residue_type(residue_type, B, N, f"xyz {shape}")
+    _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
+    _check_optional(chi_select, (B, N, 4), "chi_select", "xyz", shape)
+    tables = _chi_tables(chi_atoms, chi_last, A, True)
+    if grad_out is not None:
+        _check_float_tensor(grad_out, shape, "grad_out", f"xyz {shape}")
+    _same_device(xyz, chi=chi, residue_type=residue_type, atom_mask=atom_mask, chi_select=chi_select, grad_out=grad_out)
+    return tables
+
+
+def chi_set(xyz: torch.Tensor, chi: torch.Tensor, residue_type: torch.Tensor, atom_mask: Optional[torch.Tensor] = None,
+            chi_select: Optional[torch.Tensor] = None, *, chi_atoms, chi_last, relative: bool = False) -> torch.Tensor:
+    """K29.  The coordinates with the side chains turned to the angles ``chi`` (B,N,4) -- by them if ``relative`` --: a
+    new (B,N,A,3) fp32 tensor.  For k = 0..3 in this order, where angle k is defined (``chi``), ``chi_last[t][k] >= 0``
+    (``general.chi_last_table()``: the last slot the angle moves; -1 = never turned, as proline's) and ``chi_select``
+    (B,N,4; None = all) is non-zero, the present slots [d, last] of the residue's current coordinates are rotated about
+    b -> c by ``chi[k] - measured`` (``chi[k]`` if relative), in double, rounded once at the store.  Every other float is
+    the input's bit pattern, NaN of missing atoms and padding included; ``chi`` is not read where it is not used
+    (include/protstruc_hip.h)."""
+    atoms, last = _checked_chi_set(xyz, chi, residue_type, atom_mask, chi_select, chi_atoms, chi_last)
+    x, c, am, sel = _f32c(xyz, "xyz"), _f32c(chi, "chi"), _u8c(atom_mask, "atom_mask"), _u8c(chi_select, "chi_select")
+    B, N, A = x.shape[:3]
+    rt = _type32(residue_type, atoms.shape[0])
+    with _on(x.device):
+        out = torch.empty(B, N, A, 3, dtype=torch.float32, device=x.device)
+        if B and N:
+            _launch("ps_chi_set_f32", _ptr(x), _ptr(am), _ptr(rt), _ints(atoms), _ints(last), atoms.shape[0], _ptr(c),
+                    _ptr(sel), int(bool(relative)), _ptr(out), B, N, A, _stream(x))
+    return out
+
+
+def chi_set_backward(out: torch.Tensor, grad_out: torch.Tensor, residue_type: torch.Tensor,
+                     atom_mask: Optional[torch.Tensor] = None, chi_select: Optional[torch.Tensor] = None, *, chi_atoms,
+                     chi_last) -> torch.Tensor:
+    """K30.  Vector-Jacobian product of ``chi_set`` towards the angles: ``grad_chi`` (B,N,4) fp32 from the upstream
+    ``grad_out`` (B,N,A,3) and the coordinates ``out`` that ``chi_set`` returned, with its masks and tables:
+    ``grad_chi[k] = sum_s (u_k x (p_s - c_k)) . g_s`` over the present slots angle k turned, in double; exact 0 at an
+    angle that was not turned.  The whole derivative in both modes; there is no gradient towards ``xyz``."""
+    atoms, last = _checked_chi_set(out, None, residue_type, atom_mask, chi_select, chi_atoms, chi_last, grad_out)
+    x, g, am, sel = _f32c(out, "out"), _f32c(grad_out, "grad_out"), _u8c(atom_mask, "atom_mask"), _u8c(chi_select, "chi_select")
+    B, N, A = x.shape[:3]
+    rt = _type32(residue_type, atoms.shape[0])
+    with _on(x.device):
+        grad = torch.empty(B, N, 4, dtype=torch.float32, device=x.device)
+        if B and N:
+            _launch("ps_chi_set_backward_f32", _ptr(x), _ptr(am), _ptr(rt), _ints(atoms), _ints(last), atoms.shape[0],
+                    _ptr(sel), _ptr(g), _ptr(grad), B, N, A, _stream(x))
+    return grad
+
+
 def diffuse_(xyz: torch.Tensor, beta: torch.Tensor, rng_state: Optional[torch.Tensor] = None,
              noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K5, in place on a contiguous fp32 ``xyz``.  ``rng_state``: int64 device tensor of RNG_STATE_WORDS

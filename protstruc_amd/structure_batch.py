@@ -700,6 +700,56 @@ class StructureBatch:
             offset = self._edge_offsets(idx, int(max_offset))
         return EdgeFeatures(idx, idx >= 0, rbf, offset, local_pos, rel_rot)
 
+    # ------------------------------------------------------------------ side-chain torsions
+    def _residue_types(self, what: str) -> torch.Tensor:
+        """(B,N) int32 codes of ``pdb.ONE_TO_INDEX`` from the sequence, which ``what`` needs: ValueError without one."""
+        if self.seq is None or self.chain_ids is None:
+            raise ValueError(f"{what} needs a sequence: which atoms a chi angle joins depends on the residue type "
+                             "(construct the batch with `seq` and `chain_ids`, or use from_pdb)")
+        return self.get_seq_idx().to(torch.int32)
+
+    def side_chain_torsions(self):
+        """The side-chain torsions chi1 .. chi4 of every residue (``geometry.side_chain_torsions``):
+        ``SideChainTorsions(chi (B,N,4) fp32 in radians, mask (B,N,4) bool)``, with the atoms of every angle from
+        ``general.chi_atom_table()`` by the sequence.  An angle is defined where the residue type has it, the residue is
+        in the residue mask and its four atoms are present; elsewhere ``chi`` is exactly 0 and ``mask`` False.  Needs a
+        sequence (ValueError).  One HIP kernel; differentiable with respect to this batch's coordinates where they
+        require grad (a second HIP kernel backwards)."""
+        from . import geometry
+
+        return geometry.side_chain_torsions(self.xyz, self._residue_types("side_chain_torsions"), self._present_atoms())
+
+    def chi_pi_periodic(self) -> torch.Tensor:
+        """(B,N,4) bool: chi and chi + pi name the same structure (``general.chi_pi_periodic_table()`` by the sequence:
+        ASP chi2, GLU chi3, PHE chi2, TYR chi2) -- what a torsion-angle loss needs next to the angles.  False where the
+        residue type has no such angle.  Needs a sequence (ValueError)."""
+        from .general import chi_pi_periodic_table
+
+        return chi_pi_periodic_table().to(self.device)[self._residue_types("chi_pi_periodic").long()]
+
+    def with_side_chain_torsions(self, chi: torch.Tensor, chi_select: Optional[torch.Tensor] = None,
+                                 relative: bool = False) -> "StructureBatch":
+        """A new batch whose side chains are turned to the angles ``chi`` (B,N,4) -- by them with ``relative`` --
+        (``geometry.set_side_chain_torsions`` with ``general.chi_atom_table()`` and ``general.chi_last_table()`` by the
+        sequence); this batch is untouched.  Only the angles :meth:`side_chain_torsions` reports as defined are turned,
+        of those only where ``chi_select`` (B,N,4; None = all) is true, and never proline's; every other coordinate is
+        copied bit for bit.  The new batch shares the masks, chains, sequence and numbering.  Differentiable with respect
+        to ``chi`` (HIP kernels on both passes), so a loss of the new batch -- :meth:`steric_clashes`, :meth:`lddt`,
+        :meth:`frame_aligned_point_error` -- reaches the angles; this batch's coordinates are a constant and must not
+        require grad (ValueError).  Needs a sequence (ValueError)."""
+        from . import geometry
+
+        types = self._residue_types("with_side_chain_torsions")
+        chi = _always_tensor(chi).to(self.device)
+        if chi_select is not None:
+            chi_select = _always_tensor(chi_select).to(self.device)
+        xyz = geometry.set_side_chain_torsions(self.xyz, chi, types, self._present_atoms(), chi_select, relative)
+        new = StructureBatch(xyz, self.atom_mask, self.chain_idx, self.chain_ids, self.seq, self.residue_idx,
+                             device=self.device)
+        if self._standardized:
+            new.mu, new.std, new._standardized = self.mu, self.std, True
+        return new
+
     def peptide_bond_violations(self, **constants) -> torch.Tensor:
         """Peptide-bond violations at every junction r -> r+1, (B,N,3): bond length |C - N'|, cos of CA-C-N', cos of
         C-N'-CA' (``geometry.peptide_bond_violations``; ``tau=12.0`` and the other constants of ``ops.PEPTIDE_BOND`` by

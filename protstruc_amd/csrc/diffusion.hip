@@ -29,7 +29,12 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1
     return c;
 }
 
-// 24 random bits -> uniform in (0,1), never 0 or 1
+// 24 random bits m = r >> 8 -> a uniform on a 2^24-point grid in [2^-25, 1].  Never 0.  (m + 0.5) * 2^-24 is exact only
+// for m < 2^23: above, m + 0.5 is a tie in float32 and rounds to the even neighbour (m for even m, m + 1 for odd m), and
+// m = 2^24 - 1 gives exactly 1.0, with probability 2^-24 per word.  Harmless in normal4: a radius word of 1.0 gives
+// log2 = 0, r = 0 and z = +-0, a finite draw at the centre of the distribution; an angle word of 1.0 is one whole
+// revolution, the same point as 0.  The arithmetic is the stream's definition (tests/diffusion_ref.py mirrors it and
+// tests/test_gpu_diffusion.py pins the draws at both ends of the grid): do not "fix" it.
 __device__ __forceinline__ float u01(uint32_t r) { return ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // four standard normals for float4 group `group` of draw number `offset` (Box-Muller).

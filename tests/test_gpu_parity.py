@@ -1308,7 +1308,7 @@ def test_k3_sweep_kernels_bit_identical_to_the_one_column_kernel(SB, N, faithful
     (always the dword layout; short chains: the one-column kernel) are both held to it; full launches and an odd row range.
     `faithful`: the same in the reference's order of operations (`set_exact_angles(True)`, round 5): there the one-column
     kernel CALLS the device library (atan2f, acosf, the compiler's IEEE division) per element while the sweep kernels run
-    the library's instruction sequences restated in packed form (ps_common.hpp: atan2_lib_vn, acos_lib_vn, div_ieee_vn) --
+    the library's instruction sequences restated in packed form (k3_arith.hpp: atan2_lib_vn, acos_lib_vn, div_ieee_vn) --
     this identity is what pins the restatement to the library."""
     from protstruc_amd import ops
     B = 3

@@ -42,7 +42,12 @@ int main(int argc, char** argv) {
             printf("\n");
         };
         AtomSel s22{{1, 4, 1, 4}}, s31{{0, 1, 4, 4}}, sp{{1, 4, 4, 0}};
-#define L(NPv, SRCv, NCv, VECv, sel) [&] { return launch_sweep<NPv, SRCv, NCv, VECv>(xyz, out, B, N, A, sel, 0, N, N, 0, nullptr); }
+        // through K3Call and K3Go, as the product's launch() does (null stream, the current device's CUs)
+        const K3Go go{nullptr, nullptr, k3_cu_count(nullptr)};
+        auto call = [&](const AtomSel& sel) {
+            return K3Call{xyz, out, B, N, A, sel, 0, N, N, 0, (unsigned)(reinterpret_cast<uintptr_t>(out) & 15u)};
+        };
+#define L(NPv, SRCv, NCv, VECv, sel) [&] { return launch_sweep<NPv, SRCv, NCv, VECv, false>(call(sel), go); }
         bench("dihedral (2,2)", {{"nc4 vec", L(4, 12, 4, true, s22)}, {"nc4 dword", L(4, 12, 4, false, s22)}, {"nc2 vec", L(4, 12, 2, true, s22)}, {"nc2 dword", L(4, 12, 2, false, s22)}});
         bench("dihedral (3,1)", {{"nc4 vec", L(4, 8, 4, true, s31)}, {"nc4 dword", L(4, 8, 4, false, s31)}, {"nc2 vec", L(4, 8, 2, true, s31)}, {"nc2 dword", L(4, 8, 2, false, s31)}});
         bench("planar (2,1)", {{"nc4 vec", L(3, 4, 4, true, sp)}, {"nc4 dword", L(3, 4, 4, false, sp)}, {"nc2 vec", L(3, 4, 2, true, sp)}, {"nc2 dword", L(3, 4, 2, false, sp)}});

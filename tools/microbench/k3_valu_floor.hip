@@ -1,7 +1,7 @@
-// What does K3's arithmetic alone cost?  The dihedral / planar-angle bodies of ps_common.hpp on register operands (no
+// What does K3's arithmetic alone cost?  The dihedral / planar-angle bodies of k3_arith.hpp on register operands (no
 // loads, no stores, no LDS), 4 columns x 2 rows per trip as in the strip kernels, at 1 / 2 / 4 waves per SIMD.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -o tools/microbench/k3_valu_floor tools/microbench/k3_valu_floor.hip
-#include "../../protstruc_amd/csrc/ps_common.hpp"
+#include "../../protstruc_amd/csrc/k3_arith.hpp"
 #include <cstdio>
 #include <cstdlib>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("ERR %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(1024) void k(float* out, int trips, float seed) {
     if (acc.x + acc.y == 12345.678f) out[threadIdx.x] = acc.x;
 }
 
-// the column-interleaved atan2 (atan2_k3_vn) is the product's, ps_common.hpp
+// the column-interleaved atan2 (atan2_k3_vn) is the product's, k3_arith.hpp
 __global__ __launch_bounds__(1024) void k_il(float* out, int trips, float seed) {
     f3 cj[4], dj[4];
     for (int c = 0; c < 4; ++c) {

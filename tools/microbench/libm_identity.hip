@@ -1,4 +1,4 @@
-// The restatements of the device library's atan2f / acosf and of the compiler's IEEE division (ps_common.hpp: the scalar
+// The restatements of the device library's atan2f / acosf and of the compiler's IEEE division (k3_arith.hpp: the scalar
 // atan2_lib / acos_lib of the one-column kernels and the packed atan2_lib_vn / acos_lib_vn / div_ieee_vn of the FAITHFUL
 // sweep kernels of K3) against the library calls themselves, bit for bit:
 //   acosf:   every one of the 2^32 float bit patterns;
@@ -9,7 +9,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -I protstruc_amd/csrc tools/microbench/libm_identity.hip -o tools/microbench/libm_identity
 // Prints the mismatch count of each (must be 0) and the first few mismatching inputs.  (The same flags as the library:
 // -ffp-contract=off is part of the contract.)
-#include "ps_common.hpp"
+#include "k3_arith.hpp"
 
 #include <cstdio>
 #include <cstdlib>

@@ -451,6 +451,8 @@ def peptide_bond_violations(xyz, junction_mask=None, next_is_proline=None, n_slo
 
 DSSP_CODES = "-HBEGITS"
 DSSP_REDUCED_CODES = "CHE"
+# the reduced class of every code of DSSP_CODES (- -> C, H G I -> H, B E -> E), two bits per code
+_DSSP_REDUCED_PACKED = sum(cls << (2 * code) for code, cls in enumerate((0, 1, 2, 2, 1, 1, 0, 0)))
 
 
 class BackboneHBonds(NamedTuple):
@@ -485,8 +487,9 @@ def dssp(xyz, complete, junction, donor=None, reduced=False):
     acceptor_idx = ops.backbone_hbonds(xyz, complete, junction, donor)[0]
     codes = ops.dssp_assign(xyz, complete, junction, acceptor_idx)
     if reduced:
-        table = torch.tensor([0, 1, 2, 2, 1, 1, 0, 0], dtype=torch.int8, device=codes.device)
-        codes = table[codes.long()]
+        # arithmetic on the device, not a table built on the host: a host tensor would be copied on every call, which
+        # synchronises and cannot be captured in a graph.  Two bits per code, code c at bits 2c
+        codes = ((_DSSP_REDUCED_PACKED >> (codes.to(torch.int32) * 2)) & 3).to(torch.int8)
     return codes
 
 

@@ -395,3 +395,60 @@ def test_pdb_edge_features_without_frames_and_on_a_users_graph(pkg):
     ref = E.edge_frames(rot.cpu().numpy(), trans.cpu().numpy(), ef.idx.cpu().numpy(),
                         batch._present_atoms()[:, :, :3].all(-1).cpu().numpy())
     assert_frames_equal_the_yardstick((ef.local_pos, ef.rel_rot), ref, "a bare tensor, frames")
+
+
+# ---- second trips of the two grid-capped kernels ---------------------------------------------------------------------------------
+def prefix_graph(B, N, k, seed):
+    """(B,N,k) int32 from numpy alone, not from the kNN kernel: every row a random number (0 .. k) of random neighbours
+    followed by -1, a tenth of the rows wholly padded -- consecutive residues of one workgroup use different amounts of
+    what the workgroup keeps between them"""
+    rng = np.random.default_rng(seed)
+    idx = rng.integers(0, N, size=(B, N, k)).astype(np.int32)
+    count = rng.integers(0, k + 1, size=(B, N))
+    count[rng.random((B, N)) < 0.1] = 0
+    idx[np.arange(k)[None, None, :] >= count[..., None]] = -1
+    return idx
+
+
+# k_edge_rbf runs min(N, 1024) workgroups that walk residues i, i + 1024, ...: at N = 1025 workgroup 0 alone takes a second
+# residue, at N = 2050 workgroups 0 and 1 take three and the others two; rows of 45 floats (no multiple of 4) and of 1904
+@pytest.mark.parametrize("N", (1025, 2050))
+@pytest.mark.parametrize("k,A,P,R", ((3, 5, 3, 5), (17, 15, 7, 16)))
+def test_rbf_workgroups_that_take_more_than_one_residue(pkg, N, k, A, P, R):
+    rng = np.random.default_rng(1000 * k + N)
+    xyz = (rng.normal(size=(2, N, A, 3)) * 8.0).astype(np.float32)
+    mask = rng.random((2, N, A)) >= 1.0 / 3.0
+    xyz[~mask] = np.nan                                                              # NaN under the mask
+    idx = prefix_graph(2, N, k, seed=k + N)
+    assert k * P * R in (45, 1904) and (idx[:, :1024] >= 0).any() and (idx[:, 1024:] >= 0).any()
+    assert ((idx >= 0).sum(-1) == 0).any() and ((idx >= 0).sum(-1) == k).any()
+    pairs, centers, sigma = tables(A, P, R)
+    ref = E.edge_rbf(xyz, idx, mask, [p[0] for p in pairs], [p[1] for p in pairs], centers, sigma)
+    assert ref.real[:, :1024].any() and ref.real[:, 1024:].any() and not ref.real[:, 1024:].all()
+    got = run_rbf(pkg, xyz, idx, mask, pairs, centers, sigma)
+    assert_rbf_meets_the_yardstick(got, ref, f"N={N} k={k} A={A} P={P} R={R}")
+    # dist alone: the workgroup skips the rbf row of every residue it takes
+    kw = dict(pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers, sigma=sigma)
+    dist, none = pkg.ops.edge_rbf(dev(xyz), dev(idx), dev(mask), want_rbf=False, **kw)
+    assert none is None and torch.equal(bits(dist), bits(got[0]))
+    raw = rbf_in_sentinels(pkg, dev(xyz), dev(idx), dev(mask), pairs, centers, sigma, want_rbf=False)
+    assert raw[1] is None and torch.equal(bits(raw[0]), bits(got[0]))
+
+
+def test_frames_grid_that_takes_a_second_trip(pkg):
+    """k_edge_frames caps its grid at 4096 workgroups of 256 lanes, 1 048 576 edges of a structure per trip: N = 16500,
+    k = 64 are 1 056 000, so the first 29 workgroups take a second trip"""
+    B, N, k = 2, 16500, 64
+    assert N * k - 4096 * 256 == 7424
+    rot, trans = E.random_frames(B, N, seed=5)
+    mask = np.random.default_rng(6).random((B, N)) >= 0.3
+    rot[~mask], trans[~mask] = np.nan, np.nan                                        # NaN under the mask
+    idx = prefix_graph(B, N, k, seed=7)
+    ref = E.edge_frames(rot, trans, idx, mask)
+    last = ref.real.reshape(B, N * k)[:, 4096 * 256:]
+    assert last.any() and not last.all()
+    got = pkg.geometry.edge_frame_features(dev(rot), dev(trans), dev(idx), dev(mask))
+    raw = frames_in_sentinels(pkg, dev(rot), dev(trans), dev(idx), dev(mask))
+    for a, b in zip(got, raw):
+        assert a.shape == b.shape and torch.equal(bits(a), bits(b)), "two launches differ"
+    assert_frames_equal_the_yardstick(got, ref, f"N={N} k={k}")

@@ -201,10 +201,11 @@ int ps_backbone_dihedrals_f32(const float* xyz, const float* chain_idx,
  *        conditioning gates of SURVEY hard part 3 (3.8e-6 of off-diagonal dihedrals more than 1e-5 from the reference
  *        at unit scale, max 6.5e-5; profiles/r04_k3_error_stats.log);
  *     1  the reference's order of operations (geometry.py:110-124, :64-66): three cross products, y / |b1| with a
- *        correctly rounded square root and an IEEE division, the device library's atan2f / acosf.  No entry more than
- *        1e-5 from the reference on well-conditioned inputs.  Since ABI 5 on the same per-CU sweep kernels as the fast
- *        arithmetic (the library routines restated instruction for instruction in packed form, bit-identical to the
- *        library calls of the one-column kernel); DESIGN.md section 4 has both modes' times side by side.
+ *        correctly rounded square root and an IEEE division, the device library's atan2f / acosf restated instruction
+ *        for instruction (atan2_lib / acos_lib; no kernel calls the library).  No entry more than 1e-5 from the reference
+ *        on well-conditioned inputs.  Since ABI 5 on the same per-CU sweep kernels as the fast arithmetic (the
+ *        restatement in packed form, bit-identical to the scalar restatement the one-column kernel runs and to the
+ *        library's own results); DESIGN.md section 4 has both modes' times side by side.
  *   bit 1 -- [diagnostic] the simple one-column kernel at every shape, in the arithmetic bit 0 selects: the layout-free
  *        cross-check kernel of the parity tests, like ps_k1_config.variant = 1.  Same bits as without it.
  *   (So 0 = fast, 1 = faithful, 2 = fast / one-column, 3 = faithful / one-column; anything else: hipErrorInvalidValue.)

@@ -144,8 +144,55 @@ def build_c_example(verbose=True):
     return EXAMPLE_BIN
 
 
+PROBE_SRC = os.path.join(HERE, "..", "tests", "native", "arith_probe.hip")
+PROBE_LIB_PATH = os.path.join(HERE, "..", "build", "libps_arith_probe.so")
+
+
+def _probe_hash():
+    h = hashlib.sha256(" ".join(FLAGS).encode())
+    for d in [PROBE_SRC] + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))):
+        h.update(os.path.basename(d).encode())
+        with open(d, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
+def arith_probe_is_stale():
+    if not os.path.exists(PROBE_LIB_PATH):
+        return True
+    try:
+        with open(PROBE_LIB_PATH + ".srchash") as f:
+            return f.read().strip() != _probe_hash()
+    except OSError:
+        return True
+
+
+def build_arith_probe(force=False, verbose=True):
+    """build/libps_arith_probe.so: tests/native/arith_probe.hip, the test-only entry point that evaluates one arithmetic
+    primitive of csrc/*.hpp elementwise (tests/test_gpu_arith.py).  Compiled with exactly FLAGS -- the primitives must be
+    probed in the arithmetic the library runs them in -- and kept out of libprotstruc_hip.so: the product ABI has no probe."""
+    if not force and not arith_probe_is_stale():
+        return PROBE_LIB_PATH
+    os.makedirs(os.path.dirname(PROBE_LIB_PATH), exist_ok=True)
+    tmp = f"{PROBE_LIB_PATH}.{os.getpid()}.tmp"
+    cmd = [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp, PROBE_SRC]
+    if verbose:
+        print("[protstruc_amd.build]", " ".join(cmd), flush=True)
+    try:
+        digest = _probe_hash()
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, PROBE_LIB_PATH)
+        with open(PROBE_LIB_PATH + ".srchash", "w") as f:
+            f.write(digest + "\n")
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return PROBE_LIB_PATH
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build(force=force))
     print(build_rccl(force=force))
     print(build_c_example())
+    print(build_arith_probe(force=force))

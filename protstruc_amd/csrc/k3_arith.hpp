@@ -7,7 +7,8 @@
 //   * the faithful forms in that packed, NC-column shape (div_ieee_vn, atan2_lib_vn, acos_lib_vn, dihedral4v_ref_n,
 //     angle3v_ref_n).
 // Each scalar / packed / NC-column variant of a routine performs the same operations in the same order per element, so
-// they agree bit for bit; tests/test_gpu_parity.py holds the kernels built on them to each other.
+// they agree bit for bit; tests/test_gpu_arith.py holds each variant to its scalar form routine by routine (samples of the
+// plane, special values in every (column, half) slot, tails), tests/test_gpu_parity.py the kernels built on them to each other.
 #pragma once
 
 #include "ps_common.hpp"
@@ -15,8 +16,9 @@
 // ---- the FAITHFUL forms (round 4): geometry.dihedral / geometry.angle op for op in the reference's order ----
 // What `exact_angles` of ps_pairwise_angles_f32 / ps_inter_residue_geometry_f32 selects, as `exact_sqrt` does for K1: three
 // cross products, y divided by |b1| (correctly rounded square root, IEEE division), atan2 / acos in the device library's
-// arithmetic (<= 2 ulp; the reference's np.arctan2 / torch.arccos are libm-grade as well) -- no algebraic rewriting, no
-// reciprocal square roots, no polynomials of this file.
+// arithmetic (against float64 on the MI355X, tests/test_gpu_arith.py and profiles/arith_probe_errors.json: atan2 2.65 ulp
+// = 3.0e-7, acos 1.44 ulp = 3.1e-7; the reference's np.arctan2 / torch.arccos are libm-grade as well) -- no algebraic
+// rewriting, no reciprocal square roots, no polynomials of this file.
 //
 // atan2_lib / acos_lib (round 5) ARE the device library's atan2f / acosf (ROCm 7.2 ocml: __ocml_atan2_f32 with its
 // __ocmlpriv_atanred_f32, __ocml_acos_f32; denormals on, finite-only off), written out instruction for instruction as hipcc
@@ -26,8 +28,10 @@
 // (inside a loop body: the cheap form; hoisted out of a loop whose operands are all loop-invariant -- K3 with every point
 // from the column residue -- the IEEE form): two kernels calling atan2f on the same arguments disagreed in the last bit on
 // 13 % of them.  Written with builtins the sequence is the same everywhere; it is the cheap form, which is what a plain
-// call gives, and tools/microbench/libm_identity.hip holds it to such calls over 2^32 argument pairs (0 mismatches,
-// profiles/r05_libm_identity.log).
+// call gives, and tests/test_gpu_arith.py holds it to such calls on every run of the suite -- acosf on all 2^32 arguments,
+// atan2f on 4e7 pairs (the plane, random bit patterns, the special values), scalar and packed forms alike; a ROCm whose
+// ocml differs fails there.  (First checked over 2^32 pairs by tools/microbench/libm_identity.hip,
+// profiles/r05_libm_identity.log.)
 __device__ __forceinline__ float atan2_lib(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float v = __builtin_fminf(ax, ay), u = __builtin_fmaxf(ax, ay);
@@ -100,6 +104,11 @@ __device__ __forceinline__ float angle3_ref(f3 a, f3 b, f3 c) {
 //     then x = (n1 . n2) * rsq is NaN as well; x alone is NaN when b1 = 0 (0 * inf), the reference's 0 / 0;
 //   * atan2(+-inf, +-inf) and atan2(finite, +-inf) come out NaN instead of multiples of pi / 4.  x and y are dot
 //     products of cross products of coordinate differences: they overflow only for coordinates beyond 4e9 A.
+// Two more consequences, pinned with the rest by tests/test_gpu_arith.py: a NaN y next to a number x is NOT propagated (the
+// result is an angle with y's sign bit); and the clamp makes the quotient of two subnormal arguments min / FLT_MIN
+// instead of min / max, so atan2_k3(s, s) for a subnormal s is atan(s / FLT_MIN), not pi / 4 (errors up to pi / 4 below
+// FLT_MIN; the result is always a finite angle, where atan2_ps gives NaN or an infinity).  Accuracy elsewhere is atan2_ps's: 1.41e-7 in
+// the first octant, 2.87e-7 over the plane.
 __device__ __forceinline__ float atan2_k3(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(fmaxf(ax, ay), 1.17549435e-38f), mn = fminf(ax, ay);

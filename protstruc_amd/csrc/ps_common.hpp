@@ -37,9 +37,10 @@ __device__ __forceinline__ float dot3(f3 a, f3 b) {
 // share one v_pk_* instruction: 4 + 3.5 + 2 issue slots per element against 4 + 9 for a v_sqrt_f32 with two exact
 // residual tests (sqrt_rn_pos, the first routine; kept in tools/microbench/sqrt_check.hip as the cross-check).  Zero, subnormal
 // and +inf inputs are returned as x (sqrt(0) = 0 and sqrt(inf) = inf exactly; a subnormal squared distance means
-// atoms closer than 1e-19, error < 1.1e-19).  Checked against sqrtf over every float in [0, +inf]
-// (tools/microbench/sqrt_check.hip): equal for every x >= 2.0e-31 (atoms further apart than 4.5e-16), at most
-// 1 ulp off below.  In K1's pattern kernel this takes the inner loop from 66 to 50 VALU instructions per 16-byte
+// atoms closer than 1e-19, error < 1.1e-19).  Held to sqrtf over every non-negative float and to the correctly rounded
+// np.sqrt over whole binades of mantissas by tests/test_gpu_arith.py (first by tools/microbench/sqrt_check.hip): equal for
+// every x >= 2.0e-31 (atoms further apart than 4.5e-16), at most 1 ulp off below (1.8e6 of the normal floats
+// below are: profiles/arith_probe_errors.json).  In K1's pattern kernel this takes the inner loop from 66 to 50 VALU instructions per 16-byte
 // slot, which is what lets it reach its store-only time (profiles/r01_k1_ab_sqrt_mk.log).
 __device__ __forceinline__ float sqrt_rn_mk(float x) {
     const float y = __builtin_amdgcn_rsqf(x);
@@ -96,11 +97,16 @@ __device__ __forceinline__ f3 cross3(f3 u, f3 v) {
     return r;
 }
 
-// atan2 for the torsion kernels: odd minimax polynomial of degree 17 on [0,1] (max error 1.0e-7 = 1.7 ulp in
-// fp32, fitted and checked in fp32 emulation over 2e6 points), argument reduction by min/max and the usual
-// quadrant fix-ups.  IEEE special cases are kept: signed zeros (atan2(+0,-0) = pi, atan2(-0,+0) = -0), NaN
-// propagation, inf/inf.  About half the instructions of the library routine; K3 is VALU-bound, so this is
-// where its time goes.  The reference's own np.arctan2 / libm results differ from each other by similar amounts.
+// atan2 for the torsion kernels: odd minimax polynomial of degree 17 on [0,1], argument reduction by min/max and the
+// usual quadrant fix-ups.  Against float64 on the MI355X (tests/test_gpu_arith.py, 3.7e6 points of the plane incl. the
+// octant boundaries and their neighbours; profiles/arith_probe_errors.json): 1.41e-7 in the first octant -- the
+// polynomial's 1.0e-7 plus the 1-ulp v_rcp_f32 and the rounded quotient -- and 2.87e-7 over the plane, where the
+// subtractions from fl(pi / 2) and fl(pi) add their roundings; the test holds them to the derived 1.9e-7 and 5.0e-7.
+// That is for max(|x|, |y|) in [2^-126, 2^126): below, v_rcp_f32 overflows (two subnormal arguments give NaN or an
+// infinity, not an angle); from 2^126 on it underflows and the result, still a finite angle, can be off by pi / 4.
+// IEEE special cases are kept: signed zeros (atan2(+0,-0) = pi, atan2(-0,+0) = -0), NaN propagation, inf/inf.  About
+// half the instructions of the library routine; K3 is VALU-bound, so this is where its time goes.  The reference's own
+// np.arctan2 / libm results differ from each other by similar amounts.
 __device__ __forceinline__ float atan2_ps(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
@@ -125,8 +131,10 @@ __device__ __forceinline__ float atan2_ps(float y, float x) {
 }
 
 // acos for the planar-angle kernels: acos(|x|) = sqrt(1 - |x|) * P(|x|) with the degree-7 polynomial of Abramowitz &
-// Stegun 4.4.46 (|error| <= 2e-8 in exact arithmetic; 4.3e-7 absolute = 1 ulp of pi in fp32, checked over 4.2e6 points
-// incl. 1e-12 from +-1 -- the same size as the library routine's), reflected for negative arguments.  |x| > 1 gives NaN
+// Stegun 4.4.46 (|error| <= 2e-8 in exact arithmetic), reflected for negative arguments.  Against float64 on the MI355X
+// (tests/test_gpu_arith.py, 2.5e6 cosines incl. 2^-24 from +-1 and every float within 64 ulp of 0, +-0.5, +-1;
+// profiles/arith_probe_errors.json): 2.66e-7 for x >= 0 and 4.54e-7 = 1.05 ulp of pi for x < 0, held to the derived 5.1e-7
+// and 7.2e-7 -- the size of the library routine's error (3.1e-7).  acos_ps(1) = 0 and acos_ps(-1) = fl(pi) exactly.  |x| > 1 gives NaN
 // through the square root of a negative number, as acos without a clamp does in the reference (geometry.py:64-71); NaN
 // propagates.  14 instructions instead of the library's ~40: K3's planar-angle path is VALU-issue bound.
 __device__ __forceinline__ float acos_ps(float x) {

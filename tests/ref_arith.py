@@ -53,6 +53,53 @@ def fma_f32(a, b, c):
     return out.astype(F32)
 
 
+def _nudge(v, ulps):
+    """Non-negative v moved one float32 step up (ulps = +1) or down (-1): a 1-ulp-off hardware result.  Zero, infinity
+    and NaN stay (the instructions return those exactly)."""
+    v = np.asarray(v, dtype=F32)
+    if ulps == 0:
+        return v
+    with np.errstate(over="ignore", invalid="ignore"):
+        moved = np.nextafter(v, F32(np.inf) if ulps > 0 else F32(0))
+        return np.where(np.isfinite(v) & (v > 0), moved, v).astype(F32)
+
+
+def atan2_ps_model(y, x, rcp_ulps=0):
+    """atan2_ps (csrc/ps_common.hpp) operation for operation in float32, with v_rcp_f32 modelled as the correctly rounded
+    reciprocal moved by ``rcp_ulps`` steps (the instruction is good to 1 ulp)."""
+    y = np.asarray(y, dtype=F32)
+    x = np.asarray(x, dtype=F32)
+    with np.errstate(all="ignore"):
+        ax, ay = np.abs(x), np.abs(y)
+        mx, mn = np.fmax(ax, ay), np.fmin(ax, ay)
+        a = mn * _nudge((1.0 / mx.astype(F64)).astype(F32), rcp_ulps)
+        a = np.where(mx == 0, F32(0), a)
+        a = np.where(mn == F32(np.inf), F32(1), a).astype(F32)
+        s = a * a
+        p = F32(0.0028340641874819994)
+        for c in (-0.016005029901862144, 0.042587608098983765, -0.07495445758104324, 0.10636754333972931,
+                  -0.14202570915222168, 0.19992484152317047, -0.3333306610584259, 1.0):
+            p = fma_f32(p, s, F32(c))
+        r = a * p
+        r = np.where(ay > ax, F32(1.5707963267948966) - r, r)
+        r = np.where(np.signbit(x), F32(3.141592653589793) - r, r)
+        r = np.where(np.isnan(x) | np.isnan(y), F32(np.nan), r)
+        return np.copysign(r, y).astype(F32)
+
+
+def acos_ps_model(x, sqrt_ulps=0):
+    """acos_ps (csrc/ps_common.hpp) operation for operation in float32, with v_sqrt_f32 modelled as the correctly rounded
+    square root moved by ``sqrt_ulps`` steps."""
+    x = np.asarray(x, dtype=F32)
+    with np.errstate(all="ignore"):
+        ax = np.abs(x)
+        p = F32(-0.0012624911)
+        for c in (0.0066700901, -0.0170881256, 0.0308918810, -0.0501743046, 0.0889789874, -0.2145988016, 1.5707963050):
+            p = fma_f32(p, ax, F32(c))
+        r = p * _nudge(np.sqrt(F32(1.0) - ax), sqrt_ulps)
+        return np.where(np.signbit(x), F32(3.141592653589793) - r, r).astype(F32)
+
+
 def dot_ref(a, b):
     """(a * b).sum(-1) over a last axis of 3: products rounded first, then (p0 + p1) + p2."""
     a = np.asarray(a, dtype=F32)

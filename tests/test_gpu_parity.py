@@ -1307,9 +1307,10 @@ def test_k3_sweep_kernels_bit_identical_to_the_one_column_kernel(SB, N, faithful
     (vector stores for even N, the 64-apart column layout with dword stores for odd N) and for a 4-byte-misaligned output
     (always the dword layout; short chains: the one-column kernel) are both held to it; full launches and an odd row range.
     `faithful`: the same in the reference's order of operations (`set_exact_angles(True)`, round 5): there the one-column
-    kernel CALLS the device library (atan2f, acosf, the compiler's IEEE division) per element while the sweep kernels run
-    the library's instruction sequences restated in packed form (k3_arith.hpp: atan2_lib_vn, acos_lib_vn, div_ieee_vn) --
-    this identity is what pins the restatement to the library."""
+    kernel runs the scalar restatements of the device library (k3_arith.hpp: atan2_lib, acos_lib) and the compiler's IEEE
+    division per element while the sweep kernels run the same instruction sequences in packed form (atan2_lib_vn,
+    acos_lib_vn, div_ieee_vn) -- this identity pins the packed forms to the scalar ones at kernel level;
+    tests/test_gpu_arith.py pins both to the library's atan2f / acosf themselves."""
     from protstruc_amd import ops
     B = 3
     xyz, _ = synth(900 + N, B, N)

@@ -1,4 +1,4 @@
-"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h).
+"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h and include/protstruc_contacts.h).
 
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
@@ -141,6 +141,18 @@ SIGNATURES = {
     "ps_affine_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
 }
 
+# The closest-atom entry points (K31 / K32) are declared in include/protstruc_contacts.h, a header with a version of its
+# own (PS_CONTACTS_API), so that adding them changed neither PS_ABI_VERSION nor a declaration of protstruc_hip.h.
+EXPECTED_CONTACTS_API = 1  # PS_CONTACTS_API of include/protstruc_contacts.h
+_c_i16p = ctypes.c_void_p
+
+# name -> (restype, argtypes); mirrors include/protstruc_contacts.h one to one
+CONTACT_SIGNATURES = {
+    "ps_contacts_api": (_c_int, []),
+    "ps_closest_atoms_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_i16p, _c_int, _c_int, _c_int, ctypes.c_float, _c_stream]),
+    "ps_closest_atoms_backward_f32": (_c_int, [_c_f32p, _c_i16p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
+}
+
 _lib = None
 
 
@@ -194,6 +206,14 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = restype
         fn.argtypes = argtypes
+    for name, (restype, argtypes) in CONTACT_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+    contacts = lib.ps_contacts_api()
+    if contacts != EXPECTED_CONTACTS_API:
+        raise HipLibraryError(f"{LIB_PATH} has contacts API version {contacts}, this package binds version "
+                              f"{EXPECTED_CONTACTS_API}: rebuild with `python -m protstruc_amd.build --force`")
     _lib = lib
     return lib
 

@@ -788,6 +788,57 @@ def set_side_chain_torsions(xyz, chi, residue_type, atom_mask=None, chi_select=N
     return _SetSideChainTorsions.apply(xyz, chi, residue_type, atom_mask, chi_select, bool(relative), chi_atoms, chi_last)
 
 
+class ClosestAtoms(NamedTuple):
+    """How close every pair of residues comes, and between which atoms (``closest_atom_distances``)."""
+    dist: torch.Tensor     # (B,N,N) fp32: the smallest distance between an atom of i and an atom of j; +inf where none
+    atom_i: torch.Tensor   # (B,N,N) int16: the slot of the row residue's atom; -1 where none
+    atom_j: torch.Tensor   # (B,N,N) int16: the slot of the column residue's atom; -1 where none
+
+
+class _ClosestAtoms(torch.autograd.Function):
+    """ops.closest_atoms with ops.closest_atoms_backward as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, xyz, atom_mask, cutoff):
+        dist, pair = ops.closest_atoms(xyz, atom_mask, cutoff)
+        ctx.save_for_backward(xyz, pair)
+        ctx.dtype = xyz.dtype
+        ctx.mark_non_differentiable(pair)
+        return dist, pair
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_dist, _grad_pair):
+        xyz, pair = ctx.saved_tensors
+        return ops.closest_atoms_backward(xyz, pair, grad_dist).to(ctx.dtype), None, None
+
+
+def closest_atom_distances(xyz, atom_mask=None, cutoff=float("inf")) -> ClosestAtoms:
+    """The smallest distance between any atom of residue i and any atom of residue j of ``xyz`` (B,N,A,3), with the atom
+    pair that attains it: ``ClosestAtoms(dist (B,N,N) fp32, atom_i (B,N,N) int16, atom_j (B,N,N) int16)`` -- what contact
+    maps, interface residues and the fraction of native contacts are defined by.  Only atoms in ``atom_mask`` (B,N,A; None =
+    all) take part, and NaN under the mask never reaches a result.  Squared distances are compared in double on the
+    float32 coordinates; among equal ones the lower slot of the earlier residue wins, then the lower slot of the later
+    one, so the result is defined bit for bit and exactly symmetric: ``dist[b,j,i] = dist[b,i,j]``, ``atom_i[b,j,i] =
+    atom_j[b,i,j]``.  ``atom_i`` is always a slot of the row residue and ``atom_j`` one of the column residue.  Where no
+    atom pair counts -- a residue without atoms, or nothing within ``cutoff`` (inclusive) -- ``dist`` is +inf and both
+    slots are -1.  On the diagonal ``dist`` is 0 and both slots are the residue's lowest present one.  A finite ``cutoff``
+    lets the kernel skip residue pairs that are far apart.  One HIP kernel (``ops.closest_atoms``); the (B,N,N,A,A) tensor
+    of ``pairwise_distance_matrix`` is never built.
+
+    Differentiable with respect to ``xyz`` (a second HIP kernel, ``ops.closest_atoms_backward``, deterministic): the
+    gradient of ``dist[b,i,j]`` flows to its two recorded atoms only, as for ``amin``; entries that are +inf, and pairs
+    at distance 0 -- the diagonal --, pass none, so masking with ``torch.where(dist.isfinite(), ...)`` downstream is safe.
+    No double backward.  Tensors on the GPU."""
+    ops.check_closest_atoms_shapes(xyz, atom_mask, cutoff)
+    A = xyz.shape[2]
+    dist, pair = _ClosestAtoms.apply(xyz, atom_mask, float(cutoff))
+    none = pair < 0
+    atom_i = torch.div(pair, A, rounding_mode="floor").masked_fill(none, -1)
+    atom_j = torch.remainder(pair, A).masked_fill(none, -1)
+    return ClosestAtoms(dist, atom_i, atom_j)
+
+
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):
     """chain_breaks as a (B, L) bool array / tensor ("the chain ends after residue i"), or None.  Accepts a list of
     residue indices (every structure), a list of B such lists, or a (B, L) ((L,) unbatched) boolean array / tensor."""

@@ -1599,6 +1599,74 @@ def nearest_neighbors(points: torch.Tensor, k: int, point_mask: Optional[torch.T
     return idx, dist, count
 
 
+CLOSEST_MAX_ATOMS = 64          # PS_CLOSEST_MAX_ATOMS of include/protstruc_contacts.h: a residue's presence word is 64 bits
+CLOSEST_MAX_RESIDUES = 2 ** 20  # PS_CLOSEST_MAX_RESIDUES
+
+
+def check_closest_atoms_shapes(xyz, atom_mask=None, cutoff=_INF, pair=None, grad_dist=None) -> None:
+    """Shape rules of ``closest_atoms`` / ``closest_atoms_backward``, on shapes, dtypes, devices and the scalar only (no
+    launch): ValueError.  ``xyz`` (B,N,A,3) floating point with ``B <= 65535``, ``1 <= N <= CLOSEST_MAX_RESIDUES`` and ``1 <=
+    A <= CLOSEST_MAX_ATOMS``; ``atom_mask`` (B,N,A); ``cutoff`` non-negative, +inf allowed; for the backward pass ``pair``
+    (B,N,N) integers and ``grad_dist`` (B,N,N) floating point."""
+    B, N, A = _xyz_dims(xyz)
+    shape = (B, N, A, 3)
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if not 1 <= N <= CLOSEST_MAX_RESIDUES:
+        raise ValueError(f"1 .. 2^{CLOSEST_MAX_RESIDUES.bit_length() - 1} residues per structure, got {N}")
+    if not 1 <= A <= CLOSEST_MAX_ATOMS:
+        raise ValueError(f"1 .. {CLOSEST_MAX_ATOMS} atom slots per residue, got {A}")
+    _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
+    if float(cutoff) != _INF:
+        _check_scalar(cutoff, "cutoff", "non-negative")
+    _check_optional(pair, (B, N, N), "pair", "xyz", shape, integer=True)
+    if grad_dist is not None:
+        _check_float_tensor(grad_dist, (B, N, N), "grad_dist", f"xyz {shape}")
+    _same_device(xyz, atom_mask=atom_mask, pair=pair, grad_dist=grad_dist)
+
+
+def closest_atoms(xyz: torch.Tensor, atom_mask: Optional[torch.Tensor] = None, cutoff: float = _INF):
+    """K31.  The closest atoms of every pair of residues, fused: ``(dist (B,N,N) fp32, pair (B,N,N) int16)``.  Over every
+    atom a of residue i and atom c of residue j that are in ``atom_mask`` (B,N,A; None = all), ``d2 = (dx*dx + dy*dy) +
+    dz*dz`` in double on the float32 coordinates; non-finite ``d2`` are skipped, the minimum under ``(d2, a, c)`` -- ties
+    to the lower a, then the lower c, for i <= j -- counts where ``d2 <= cutoff^2``: ``dist = sqrt(d2)`` rounded to float32
+    once and ``pair = a * A + c``; ``dist = +inf`` and ``pair = -1`` where nothing counts.  Entry (j,i) mirrors (i,j): the
+    same ``dist`` bits and ``pair = c * A + a``, so ``pair[b,r,s]`` reads (atom of r, atom of s).  The diagonal is not
+    special (0.0 and the lowest present slot twice).  NaN under the mask never reaches a result; a finite ``cutoff`` lets
+    the kernel skip residue pairs that are far apart without changing a bit.  Nothing of size N*N*A*A is built;
+    deterministic (include/protstruc_contacts.h)."""
+    check_closest_atoms_shapes(xyz, atom_mask, cutoff)
+    x, am = _f32c(xyz, "xyz"), _u8c(atom_mask, "atom_mask")
+    B, N, A = x.shape[:3]
+    with _on(x.device):
+        dist = torch.empty(B, N, N, dtype=torch.float32, device=x.device)   # the kernel writes every element
+        pair = torch.empty(B, N, N, dtype=torch.int16, device=x.device)
+        if B:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_closest_atoms_f32", _ptr(x), _ptr(am), _ptr(dist), _ptr(pair), B, N, A, float(cutoff), _stream(x))
+    return dist, pair
+
+
+def closest_atoms_backward(xyz: torch.Tensor, pair: torch.Tensor, grad_dist: torch.Tensor) -> torch.Tensor:
+    """K32.  Vector-Jacobian product of ``closest_atoms`` towards the coordinates in one launch: ``grad_xyz`` (B,N,A,3)
+    fp32 from ``pair`` (B,N,N), as the forward pass returned it, and the upstream ``grad_dist`` (B,N,N).  Slot a of residue
+    i collects ``(g[i,j] + g[j,i]) (Xia - Xjc) / |Xia - Xjc|`` over the j != i whose recorded pair is (a, c), over j
+    ascending in double, rounded once; a pair of -1 (any value outside [0, A*A)) and a distance of 0 contribute nothing,
+    so the gradient at ``dist = +inf`` is dropped; exact zeros in the slots that win no pair.  No atomics, deterministic
+    (include/protstruc_contacts.h)."""
+    check_closest_atoms_shapes(xyz, None, _INF, pair, grad_dist)
+    x, g = _f32c(xyz, "xyz"), _f32c(grad_dist, "grad_dist")
+    B, N, A = x.shape[:3]
+    _require_device(pair, "pair")
+    if pair.dtype != torch.int16:   # wider integers: everything out of range becomes -1 first, so that none wraps into it
+        pair = torch.where((pair >= 0) & (pair < A * A), pair, torch.full_like(pair, -1)).to(torch.int16)
+    p = pair.contiguous()
+    with _on(x.device):
+        out = torch.empty(B, N, A, 3, dtype=torch.float32, device=x.device)
+        if B:
+            _launch("ps_closest_atoms_backward_f32", _ptr(x), _ptr(p), _ptr(g), _ptr(out), B, N, A, _stream(x))
+    return out
+
+
 EDGE_MAX_PAIRS = 64   # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
 EDGE_MAX_RBF = 64     # PS_EDGE_MAX_RBF: the centres travel in the kernel's arguments
 

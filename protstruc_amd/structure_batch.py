@@ -634,6 +634,68 @@ class StructureBatch:
         return geometry.nearest_neighbors(self.xyz.reshape(B, N * A, 3), k, takes_part, exclude=residue,
                                           cutoff=float("inf") if cutoff is None else cutoff)
 
+    # ------------------------------------------------------------------ residue contacts
+    def closest_atom_distances(self, atoms="all", cutoff: Optional[float] = None):
+        """How close every pair of residues comes (``geometry.closest_atom_distances``): ``geometry.ClosestAtoms(dist,
+        atom_i, atom_j)``, each (B,N,N) -- the smallest distance between a chosen atom of residue i and one of residue j,
+        and the two atom slots that attain it (slots of this batch's full atom axis, whatever ``atoms`` selects).  An atom
+        takes part where it is present, its residue is in the residue mask and its slot is among ``atoms`` (``"all"``:
+        every slot); the selection is folded into the atom mask, no coordinate is copied, and NaN coordinates of missing
+        atoms never reach the result.  ``dist`` is +inf and the slots -1 where a residue has no such atom or, with
+        ``cutoff`` (A, inclusive), where the residues are further apart.  Exactly symmetric; equal distances go to the
+        lower slots.  One HIP kernel; differentiable with respect to this batch's coordinates where they require grad (a
+        second HIP kernel backwards; +inf entries pass no gradient)."""
+        from . import geometry
+
+        chosen = torch.zeros(self.max_n_atoms_per_residue, dtype=torch.bool, device=self.device)
+        chosen[self._atom_slots(atoms)] = True
+        return geometry.closest_atom_distances(self.xyz, self._present_atoms() & chosen,
+                                               float("inf") if cutoff is None else cutoff)
+
+    def residue_contacts(self, cutoff: float = 5.0, atoms="all", other_chains_only: bool = False,
+                         min_separation: int = 1) -> torch.Tensor:
+        """The contact map, (B,N,N) bool: residues i and j have two chosen atoms within ``cutoff`` A of each other
+        (inclusive; :meth:`closest_atom_distances`).  The diagonal is False, as is every pair with a residue that is
+        masked or has none of the ``atoms``.  ``other_chains_only`` keeps the pairs of different chains only;
+        ``min_separation`` drops the pairs of one chain that are fewer than that many positions apart along the residue
+        axis (1: only the residue itself).  Symmetric.  Not differentiable."""
+        if isinstance(min_separation, bool) or not isinstance(min_separation, (int, np.integer)) or min_separation < 0:
+            raise ValueError(f"min_separation must be a non-negative integer, got {min_separation!r}")
+        N = self.n_residues
+        with torch.no_grad():
+            dist = self.closest_atom_distances(atoms, cutoff).dist
+        position = torch.arange(N, device=self.device)
+        apart = (position[:, None] - position[None, :]).abs()
+        chain = self._chain_keys()
+        other = chain[:, :, None] != chain[:, None, :]
+        keep = other if other_chains_only else other | (apart >= int(min_separation))[None]
+        return torch.isfinite(dist) & keep & (apart > 0)[None]
+
+    def interface_residues(self, cutoff: float = 5.0, atoms="all") -> torch.Tensor:
+        """(B,N) bool: the residue has a chosen atom within ``cutoff`` A of one of a residue of another chain -- the
+        interface, epitope or paratope residues of a complex.  All False for a structure of one chain."""
+        return self.residue_contacts(cutoff, atoms, other_chains_only=True).any(dim=-1)
+
+    def fraction_native_contacts(self, native: "StructureBatch", cutoff: float = 5.0, atoms="all"):
+        """Fnat of CAPRI and DockQ: ``(fnat (B,) float32, n_native (B,) int64)``.  Of the pairs of residues of different
+        chains that are in contact in ``native`` (:meth:`residue_contacts` with ``other_chains_only``; every unordered
+        pair once), ``n_native`` of them, ``fnat`` is the fraction that is in contact in this batch too; NaN where
+        ``n_native`` is 0.  ``native`` has this batch's shape and chain layout (ValueError otherwise)."""
+        if not isinstance(native, StructureBatch):
+            raise TypeError("native must be a StructureBatch")
+        if tuple(native.xyz.shape) != tuple(self.xyz.shape):
+            raise ValueError(f"native has coordinates of shape {tuple(native.xyz.shape)}, this batch {tuple(self.xyz.shape)}")
+        if native.device != self.device:
+            raise ValueError(f"native lives on {native.device}, this batch on {self.device}")
+        if not torch.equal(native._chain_keys(), self._chain_keys()):
+            raise ValueError("native has another chain layout: the chain index of every residue must be the same")
+        upper = torch.ones(self.n_residues, self.n_residues, dtype=torch.bool, device=self.device).triu(1)
+        want = native.residue_contacts(cutoff, atoms, other_chains_only=True) & upper
+        have = self.residue_contacts(cutoff, atoms, other_chains_only=True) & want
+        n_native = want.sum(dim=(1, 2))
+        fnat = have.sum(dim=(1, 2)).to(torch.float64) / n_native.to(torch.float64)     # 0 / 0 = NaN
+        return fnat.to(torch.float32), n_native
+
     # ------------------------------------------------------------------ edge features
     def _edge_offsets(self, idx: torch.Tensor, max_offset: int) -> torch.Tensor:
         """(B,N,k) int64 class of every edge of ``idx`` (padding -1): ``clip(r_i - r_j + max_offset, 0, 2 max_offset)``

@@ -1,4 +1,5 @@
-"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h and include/protstruc_contacts.h).
+"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h, include/protstruc_contacts.h and
+include/protstruc_pairhead.h).
 
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
@@ -153,6 +154,20 @@ CONTACT_SIGNATURES = {
     "ps_closest_atoms_backward_f32": (_c_int, [_c_f32p, _c_i16p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
 }
 
+# The pair-head entry points (K33 - K36) are declared in include/protstruc_pairhead.h, again with a version of their own
+# (PS_PAIRHEAD_API): PS_ABI_VERSION, PS_CONTACTS_API and every earlier declaration stay as they were.
+EXPECTED_PAIRHEAD_API = 1  # PS_PAIRHEAD_API of include/protstruc_pairhead.h
+
+# name -> (restype, argtypes); mirrors include/protstruc_pairhead.h one to one.  breaks is a HOST array of floats
+PAIRHEAD_SIGNATURES = {
+    "ps_pairhead_api": (_c_int, []),
+    "ps_pair_bins_f32": (_c_int, [_c_int] + [_c_f32p] * 6 + [_c_u8p, _c_u8p, ctypes.c_void_p, _c_int, _c_u8p, _c_f32p, _c_int,
+                                  _c_int, _c_stream]),
+    "ps_binned_cross_entropy_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, ctypes.c_void_p, _c_int, _c_int, _c_int, _c_stream]),
+    "ps_binned_cross_entropy_backward_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
+    "ps_binned_expectation_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
+}
+
 _lib = None
 
 
@@ -214,6 +229,14 @@ def load():
     if contacts != EXPECTED_CONTACTS_API:
         raise HipLibraryError(f"{LIB_PATH} has contacts API version {contacts}, this package binds version "
                               f"{EXPECTED_CONTACTS_API}: rebuild with `python -m protstruc_amd.build --force`")
+    for name, (restype, argtypes) in PAIRHEAD_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+    pairhead = lib.ps_pairhead_api()
+    if pairhead != EXPECTED_PAIRHEAD_API:
+        raise HipLibraryError(f"{LIB_PATH} has pair-head API version {pairhead}, this package binds version "
+                              f"{EXPECTED_PAIRHEAD_API}: rebuild with `python -m protstruc_amd.build --force`")
     _lib = lib
     return lib
 

@@ -30,7 +30,7 @@ def sources():
 
 def _deps():
     return sources() + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + \
-        [os.path.join(HERE, "..", "include", name) for name in ("protstruc_hip.h", "protstruc_contacts.h")]
+        [os.path.join(HERE, "..", "include", name) for name in ("protstruc_hip.h", "protstruc_contacts.h", "protstruc_pairhead.h")]
 
 
 def source_hash():

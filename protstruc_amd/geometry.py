@@ -839,6 +839,152 @@ def closest_atom_distances(xyz, atom_mask=None, cutoff=float("inf")) -> ClosestA
     return ClosestAtoms(dist, atom_i, atom_j)
 
 
+# ---- the pair heads: distogram, predicted aligned error, pTM (K33 - K36) -----------------------------------------------------
+def _linspace_breaks(first: float, last: float, n_bins: int, what: str) -> torch.Tensor:
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 2 <= n_bins <= ops.PAIRHEAD_MAX_BINS:
+        raise ValueError(f"{what}: 2 .. {ops.PAIRHEAD_MAX_BINS} bins, got {n_bins!r}")
+    return torch.from_numpy(np.linspace(float(first), float(last), int(n_bins) - 1, dtype=np.float64).astype(np.float32))
+
+
+def distogram_breaks(first: float = 2.3125, last: float = 21.6875, n_bins: int = 64) -> torch.Tensor:
+    """The ``n_bins - 1`` bin edges of a distogram head, ``linspace(first, last, n_bins - 1)`` as float32 on the host
+    (AlphaFold 2's defaults): bin 0 is everything up to ``first``, the last bin everything beyond ``last``."""
+    return _linspace_breaks(first, last, n_bins, "distogram_breaks")
+
+
+def aligned_error_breaks(max_bin: float = 31.0, n_bins: int = 64) -> torch.Tensor:
+    """The ``n_bins - 1`` bin edges of a predicted-aligned-error head, ``linspace(0, max_bin, n_bins - 1)`` as float32 on the
+    host (AlphaFold 2's defaults)."""
+    return _linspace_breaks(0.0, max_bin, n_bins, "aligned_error_breaks")
+
+
+def aligned_error_bin_centers(max_bin: float = 31.0, n_bins: int = 64) -> torch.Tensor:
+    """The ``n_bins`` bin centres that go with ``aligned_error_breaks``: every break plus half a step, and the last of these
+    plus a whole step for the open last bin (AlphaFold 2's ``_calculate_bin_centers``); float64 on the host."""
+    breaks = aligned_error_breaks(max_bin, n_bins).double()
+    step = breaks[1] - breaks[0] if breaks.numel() > 1 else breaks[0]
+    centers = breaks + step / 2
+    return torch.cat([centers, centers[-1:] + step])
+
+
+class _BinnedCrossEntropy(torch.autograd.Function):
+    """ops.binned_cross_entropy (K34) with ops.binned_cross_entropy_backward (K35) as its vector-Jacobian product."""
+
+    @staticmethod
+    def forward(ctx, logits, bins):
+        row_loss, row_count = ops.binned_cross_entropy(logits, bins)
+        # nothing of the forward's arithmetic is kept: the backward kernel recomputes the softmax from the logits
+        ctx.save_for_backward(logits, bins)
+        ctx.dtype = logits.dtype
+        ctx.mark_non_differentiable(row_count)
+        return row_loss, row_count
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_row, _grad_count):
+        logits, bins = ctx.saved_tensors
+        return ops.binned_cross_entropy_backward(logits, bins, grad_row).to(ctx.dtype), None
+
+
+def binned_cross_entropy(logits, bins, eps: float = 1e-6) -> torch.Tensor:
+    """Mean cross-entropy of ``logits`` (B,N,N,C) against the labels ``bins`` (B,N,N) per structure, ``(B,)`` fp32: the sum
+    of ``lse(x_ij) - x_ij[bins_ij]`` over the pairs whose label is in ``[0, C)`` divided by ``eps`` plus their number.  A
+    label outside the range -- the 255 of ``ops.pair_bins_*`` -- is "no target": the pair counts nowhere and its logits,
+    NaN included, never reach the loss or a gradient.  Differentiable with respect to ``logits`` only; forward and
+    backward are one pass over the logits each (``ops.binned_cross_entropy``, ``ops.binned_cross_entropy_backward``) and
+    neither builds a log-softmax or softmax tensor.  A structure without a labelled pair has loss 0 and zero gradients.
+    No double backward."""
+    ops._check_scalar(eps, "eps", "non-negative")
+    row_loss, row_count = _BinnedCrossEntropy.apply(logits, bins.detach())
+    return (row_loss.double().sum(dim=1) / (float(eps) + row_count.sum(dim=1).double())).float()
+
+
+def distogram_loss(logits, points, point_mask=None, breaks=None, eps: float = 1e-6) -> torch.Tensor:
+    """AlphaFold 2's distogram loss per structure, ``(B,)``: ``binned_cross_entropy`` of ``logits`` (B,N,N,C) against the
+    bins of the distances between ``points`` (B,N,3) -- pseudo-beta atoms, usually -- over the pairs both of whose points
+    are in ``point_mask`` (B,N; None = all), the diagonal included.  ``breaks``: ``C - 1`` bin edges, default
+    ``distogram_breaks(n_bins=C)``.  The bins are piecewise constant in the coordinates, so ``points`` is used detached and
+    the gradient flows to ``logits`` only.  Two fused passes (``ops.pair_bins_distance``, K34); the only (B,N,N) tensor is
+    the byte per pair that holds the bin."""
+    C = logits.shape[-1]
+    table = distogram_breaks(n_bins=C) if breaks is None else breaks
+    bins = ops.pair_bins_distance(points.detach(), table, point_mask, point_mask)
+    return binned_cross_entropy(logits, bins, eps)
+
+
+def aligned_error(rot, trans, points, target_rot, target_trans, target_points, frame_mask=None, point_mask=None) -> torch.Tensor:
+    """The aligned-error matrix between a prediction and a target, ``(B,N,N)`` fp32: ``e[b,i,j] = |R_i^T (x_j - t_i) - R*_i^T
+    (x*_j - t*_i)|``, the error of point j seen from frame i -- what FAPE averages and a PAE head is trained on.  ``rot``
+    (B,N,3,3) has the basis vectors as columns; ``points`` (B,N,3).  +inf where frame i is not in ``frame_mask`` or point j
+    not in ``point_mask`` (B,N; None = all).  Computed in double on the float32 inputs and rounded once; not differentiable
+    (every input is used detached)."""
+    operands = [t.detach() for t in (rot, trans, points, target_rot, target_trans, target_points)]
+    return ops.pair_bins_aligned_error(*operands, aligned_error_breaks(), frame_mask, point_mask, return_value=True)[1]
+
+
+def aligned_error_loss(logits, rot, trans, points, target_rot, target_trans, target_points, frame_mask=None, point_mask=None,
+                       breaks=None, eps: float = 1e-8) -> torch.Tensor:
+    """AlphaFold 2's predicted-aligned-error loss per structure, ``(B,)``: ``binned_cross_entropy`` of ``logits`` (B,N,N,C)
+    against the bins of ``aligned_error`` over the pairs (frame i in ``frame_mask``, point j in ``point_mask``).
+    ``breaks``: ``C - 1`` bin edges, default ``aligned_error_breaks(n_bins=C)``.  The bins are piecewise constant in the
+    geometry, so all six geometry inputs are used detached and the gradient flows to ``logits`` only."""
+    C = logits.shape[-1]
+    table = aligned_error_breaks(n_bins=C) if breaks is None else breaks
+    operands = [t.detach() for t in (rot, trans, points, target_rot, target_trans, target_points)]
+    bins = ops.pair_bins_aligned_error(*operands, table, frame_mask, point_mask)
+    return binned_cross_entropy(logits, bins, eps)
+
+
+def predicted_aligned_error(logits, max_bin: float = 31.0) -> torch.Tensor:
+    """The expected aligned error under a PAE head's ``logits`` (B,N,N,C), ``(B,N,N)`` fp32: ``sum_k softmax(x_ij)_k c_k`` with
+    the bin centres ``aligned_error_bin_centers(max_bin, C)``.  One pass (``ops.binned_expectation``); not differentiable."""
+    B, C = logits.shape[0], logits.shape[-1]
+    centers = aligned_error_bin_centers(max_bin, C).to(device=logits.device, dtype=torch.float32)
+    return ops.binned_expectation(logits.detach(), centers.expand(B, 1, C))[0]
+
+
+def contact_probability(logits, cutoff: float = 8.0, breaks=None) -> torch.Tensor:
+    """The probability a distogram head's ``logits`` (B,N,N,C) give to a distance of at most ``cutoff``, ``(B,N,N)`` fp32:
+    the softmax mass of the bins whose upper edge is ``<= cutoff`` (the open last bin has none).  ``breaks``: the ``C - 1``
+    edges, default ``distogram_breaks(n_bins=C)``.  One pass (``ops.binned_expectation``); not differentiable."""
+    B, C = logits.shape[0], logits.shape[-1]
+    table = ops._check_breaks(distogram_breaks(n_bins=C) if breaks is None else breaks)
+    if table.size != C - 1:
+        raise ValueError(f"{C - 1} breaks for logits of {C} bins, got {table.size}")
+    ops._check_scalar(cutoff, "cutoff", "non-negative")
+    inside = np.zeros(C, dtype=np.float32)
+    inside[:C - 1] = table <= np.float32(cutoff)
+    return ops.binned_expectation(logits.detach(), torch.from_numpy(inside).to(logits.device).expand(B, 1, C))[0]
+
+
+def predicted_tm_score(logits, residue_mask, chain_idx=None, interface: bool = False, max_bin: float = 31.0) -> torch.Tensor:
+    """AlphaFold's predicted TM-score (pTM; ipTM with ``interface``) per structure, ``(B,)`` fp32, from a PAE head's
+    ``logits`` (B,N,N,C), exactly its formula: with ``n`` the residues in ``residue_mask`` (B,N), ``d0 = 1.24 (max(n, 19) -
+    15)^(1/3) - 1.8`` per structure; the term of a pair is ``sum_k softmax(x_ij)_k / (1 + (c_k / d0)^2)`` over the bin
+    centres ``c_k`` (one pass over the logits, ``ops.binned_expectation``); the pair mask ``pm`` is ``mask_i mask_j``, times
+    ``chain_i != chain_j`` (``chain_idx`` (B,N)) with ``interface``; per row ``sum_j term pm / (1e-8 + sum_j pm)``, times
+    ``mask_i``; the result is the maximum over ``i``.  The (B,N,N) tail is plain torch in float64.  Not differentiable."""
+    ops.check_binned_shapes(logits)
+    B, N, _, C = logits.shape
+    ops._check_optional(residue_mask, (B, N), "residue_mask", "logits", tuple(logits.shape))
+    if interface and chain_idx is None:
+        raise ValueError("interface=True needs chain_idx")
+    ops._check_optional(chain_idx, (B, N), "chain_idx", "logits", tuple(logits.shape))
+    mask = (residue_mask.to(logits.device) != 0).double()
+    n = mask.sum(dim=1).clamp(min=19.0)
+    d0 = 1.24 * (n - 15.0) ** (1.0 / 3.0) - 1.8
+    centers = aligned_error_bin_centers(max_bin, C).to(logits.device)
+    kernel = 1.0 / (1.0 + (centers[None, :] / d0[:, None]) ** 2)                     # (B,C) float64
+    term = ops.binned_expectation(logits.detach(), kernel.float()[:, None, :])[0].double()
+    pair = mask[:, :, None] * mask[:, None, :]
+    if interface:
+        chain = torch.nan_to_num(chain_idx.to(logits.device).double(), nan=-1.0)
+        pair = pair * (chain[:, :, None] != chain[:, None, :])
+    term = torch.where(pair > 0, term, torch.zeros_like(term))       # whatever the logits of the padding hold stays out
+    per_row = term.sum(dim=-1) / (1e-8 + pair.sum(dim=-1))
+    return (per_row * mask).amax(dim=1).float()
+
+
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):
     """chain_breaks as a (B, L) bool array / tensor ("the chain ends after residue i"), or None.  Accepts a list of
     residue indices (every structure), a list of B such lists, or a (B, L) ((L,) unbatched) boolean array / tensor."""

@@ -1667,6 +1667,185 @@ def closest_atoms_backward(xyz: torch.Tensor, pair: torch.Tensor, grad_dist: tor
     return out
 
 
+PAIRHEAD_MAX_RESIDUES = 2 ** 20  # PS_PAIRHEAD_MAX_RESIDUES of include/protstruc_pairhead.h
+PAIRHEAD_MAX_BREAKS = 127        # PS_PAIRHEAD_MAX_BREAKS: every bin index and the "no target" label fit a byte
+PAIRHEAD_MAX_BINS = 128          # PS_PAIRHEAD_MAX_BINS
+PAIRHEAD_MAX_TABLES = 4          # PS_PAIRHEAD_MAX_TABLES
+PAIRHEAD_NO_TARGET = 255         # PS_PAIRHEAD_NO_TARGET: the bin of a pair without a target
+
+
+def _check_breaks(breaks) -> np.ndarray:
+    """``breaks`` as the float32 host array the launcher reads: 1 .. PAIRHEAD_MAX_BREAKS finite, non-negative, strictly
+    increasing numbers; ValueError otherwise."""
+    arr = np.ascontiguousarray(_host_f32(breaks, "breaks"))
+    if not 1 <= arr.size <= PAIRHEAD_MAX_BREAKS:
+        raise ValueError(f"1 .. {PAIRHEAD_MAX_BREAKS} breaks, got {arr.size}")
+    if not (np.isfinite(arr).all() and (arr >= 0).all() and (np.diff(arr) > 0).all()):
+        raise ValueError("breaks must be finite, non-negative and strictly increasing")
+    return arr
+
+
+def _pair_batch(B: int, N: int) -> None:
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if not 1 <= N <= PAIRHEAD_MAX_RESIDUES:
+        raise ValueError(f"1 .. 2^{PAIRHEAD_MAX_RESIDUES.bit_length() - 1} residues per structure, got {N}")
+
+
+def check_pair_bins_shapes(points, breaks, row_mask=None, col_mask=None, rot=None, trans=None, target_rot=None,
+                           target_trans=None, target_points=None) -> None:
+    """Shape rules of ``pair_bins_distance`` / ``pair_bins_aligned_error``, on shapes, dtypes, devices and the host table
+    only (no launch): ValueError.  ``points`` (B,N,3) floating point with ``B <= 65535`` and ``1 <= N <=
+    PAIRHEAD_MAX_RESIDUES``; the masks (B,N); ``breaks`` 1 .. ``PAIRHEAD_MAX_BREAKS`` finite, non-negative, strictly
+    increasing numbers; with ``rot`` given (the aligned error) ``rot`` and ``target_rot`` (B,N,3,3), ``trans``,
+    ``target_trans`` and ``target_points`` (B,N,3), all floating point."""
+    shape = tuple(points.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"points must have shape (batch, residues, 3), got {shape}")
+    if not points.dtype.is_floating_point:
+        raise ValueError(f"points must be a floating-point tensor, got {points.dtype}")
+    B, N = shape[:2]
+    _pair_batch(B, N)
+    _check_breaks(breaks)
+    _check_optional(row_mask, (B, N), "row_mask", "points", shape)
+    _check_optional(col_mask, (B, N), "col_mask", "points", shape)
+    frames = {}
+    if rot is not None:
+        frames = {"rot": (rot, (B, N, 3, 3)), "trans": (trans, (B, N, 3)), "target_rot": (target_rot, (B, N, 3, 3)),
+                  "target_trans": (target_trans, (B, N, 3)), "target_points": (target_points, (B, N, 3))}
+        for name, (t, want) in frames.items():
+            _check_float_tensor(t, want, name, f"points {shape}")
+    _same_device(points, row_mask=row_mask, col_mask=col_mask, **{name: t for name, (t, _) in frames.items()})
+
+
+def _pair_bins(mode, floats, row_mask, col_mask, breaks, return_value):
+    points = floats[0]
+    B, N = points.shape[:2]
+    rm, cm = _u8c(row_mask, "row_mask"), _u8c(col_mask, "col_mask")
+    table = _check_breaks(breaks)
+    with _on(points.device):
+        bins = torch.empty(B, N, N, dtype=torch.uint8, device=points.device)    # the kernel writes every element
+        value = torch.empty(B, N, N, dtype=torch.float32, device=points.device) if return_value else None
+        if B:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_pair_bins_f32", mode, *[_ptr(t) for t in floats], _ptr(rm), _ptr(cm), table.ctypes.data, int(table.size),
+                    _ptr(bins), _ptr(value), B, N, _stream(points))
+    return (bins, value) if return_value else bins
+
+
+def pair_bins_distance(points: torch.Tensor, breaks, row_mask: Optional[torch.Tensor] = None,
+                       col_mask: Optional[torch.Tensor] = None, return_value: bool = False):
+    """K33, distance mode.  The distogram bin of every pair of ``points`` (B,N,3): ``bins`` (B,N,N) uint8 with ``bins[b,i,j] =
+    #{k : d2 > breaks[k]^2}`` -- AlphaFold's ``sum(d2 > sq_breaks)`` --, where ``d2 = (dx*dx + dy*dy) + dz*dz`` with ``dx = xj -
+    xi`` and the squared breaks are formed in double on the float32 inputs, so the bin is defined bit for bit.  ``breaks`` is
+    a host sequence of 1 .. 127 finite, non-negative, strictly increasing numbers.  Where ``row_mask[b,i] * col_mask[b,j]``
+    (B,N; None = all) is 0 or ``d2`` is not finite the bin is ``PAIRHEAD_NO_TARGET`` (255); NaN under a mask never reaches
+    an output.  With ``return_value`` also ``value`` (B,N,N) fp32, ``sqrt(d2)`` rounded to float32 once, +inf where the
+    bin is 255 (include/protstruc_pairhead.h)."""
+    check_pair_bins_shapes(points, breaks, row_mask, col_mask)
+    return _pair_bins(0, [_f32c(points, "points")] + [None] * 5, row_mask, col_mask, breaks, return_value)
+
+
+def pair_bins_aligned_error(rot: torch.Tensor, trans: torch.Tensor, points: torch.Tensor, target_rot: torch.Tensor,
+                            target_trans: torch.Tensor, target_points: torch.Tensor, breaks,
+                            frame_mask: Optional[torch.Tensor] = None, point_mask: Optional[torch.Tensor] = None,
+                            return_value: bool = False):
+    """K33, aligned-error mode.  The bin of the aligned error ``|R_i^T (x_j - t_i) - R*_i^T (x*_j - t*_i)|`` of every (frame i,
+    point j): ``bins`` (B,N,N) uint8, counted over ``breaks`` as in ``pair_bins_distance``, the error's square formed in
+    double on the float32 inputs in a stated order.  ``rot`` (B,N,3,3) has the basis vectors as columns, as ``frames``
+    returns it; ``points`` (B,N,3) is one point per residue.  The row mask is ``frame_mask``, the column mask
+    ``point_mask`` (B,N; None = all); 255 where either is 0 or the error is not finite.  With ``return_value`` also the
+    error itself, (B,N,N) fp32, +inf where the bin is 255 (include/protstruc_pairhead.h)."""
+    check_pair_bins_shapes(points, breaks, frame_mask, point_mask, rot, trans, target_rot, target_trans, target_points)
+    floats = [_f32c(t, name) for t, name in ((points, "points"), (rot, "rot"), (trans, "trans"), (target_points, "target_points"),
+                                             (target_rot, "target_rot"), (target_trans, "target_trans"))]
+    return _pair_bins(1, floats, frame_mask, point_mask, breaks, return_value)
+
+
+def check_binned_shapes(logits, bins=None, grad_row=None, values=None) -> None:
+    """Shape rules of ``binned_cross_entropy``, ``binned_cross_entropy_backward`` and ``binned_expectation``, on shapes,
+    dtypes and devices only (no launch): ValueError.  ``logits`` (B,N,N,C) floating point with ``B <= 65535``, ``1 <= N <=
+    PAIRHEAD_MAX_RESIDUES`` and ``2 <= C <= PAIRHEAD_MAX_BINS``; ``bins`` (B,N,N) integers; ``grad_row`` (B,N) floating
+    point; ``values`` (B,V,C) floating point with ``1 <= V <= PAIRHEAD_MAX_TABLES``."""
+    shape = tuple(logits.shape)
+    if len(shape) != 4 or shape[1] != shape[2]:
+        raise ValueError(f"logits must have shape (batch, residues, residues, bins), got {shape}")
+    if not logits.dtype.is_floating_point:
+        raise ValueError(f"logits must be a floating-point tensor, got {logits.dtype}")
+    B, N, _, C = shape
+    _pair_batch(B, N)
+    if not 2 <= C <= PAIRHEAD_MAX_BINS:
+        raise ValueError(f"2 .. {PAIRHEAD_MAX_BINS} bins, got {C}")
+    _check_optional(bins, (B, N, N), "bins", "logits", shape, integer=True)
+    if grad_row is not None:
+        _check_float_tensor(grad_row, (B, N), "grad_row", f"logits {shape}")
+    if values is not None:
+        vshape = tuple(values.shape)
+        if len(vshape) != 3 or vshape[0] != B or vshape[2] != C:
+            raise ValueError(f"values must have shape ({B}, tables, {C}) to match logits {shape}, got {vshape}")
+        if not 1 <= vshape[1] <= PAIRHEAD_MAX_TABLES:
+            raise ValueError(f"1 .. {PAIRHEAD_MAX_TABLES} value tables, got {vshape[1]}")
+        if not values.dtype.is_floating_point:
+            raise ValueError(f"values must be a floating-point tensor, got {values.dtype}")
+    _same_device(logits, bins=bins, grad_row=grad_row, values=values)
+
+
+def _bins_u8(bins: torch.Tensor, C: int) -> torch.Tensor:
+    _require_device(bins, "bins")
+    if bins.dtype != torch.uint8:   # wider integers: everything outside [0, C) becomes 255 first, so that nothing wraps into range
+        bins = torch.where((bins >= 0) & (bins < C), bins, torch.full_like(bins, PAIRHEAD_NO_TARGET)).to(torch.uint8)
+    return bins.contiguous()
+
+
+def binned_cross_entropy(logits: torch.Tensor, bins: torch.Tensor):
+    """K34.  Cross-entropy of ``logits`` (B,N,N,C) against the labels ``bins`` (B,N,N), summed per row in one pass over the
+    logits: ``(row_loss (B,N) fp32, row_count (B,N) int32)`` with ``row_loss[b,i] = sum_j lse(x_ij) - x_ij[bins_ij]`` over
+    the ``j`` whose label is in ``[0, C)`` and ``row_count`` their number.  A label outside ``[0, C)`` -- the 255 of "no
+    target" -- contributes nothing and the logits there, NaN included, never reach the sum; ``-inf`` logits are legal.
+    Labels that are not uint8 are mapped to uint8 first, everything outside ``[0, C)`` to 255.  Per pair fp32; across
+    ``j`` double in a fixed order, rounded once: no atomics, deterministic.  No log-softmax tensor is built
+    (include/protstruc_pairhead.h)."""
+    check_binned_shapes(logits, bins)
+    x = _f32c(logits, "logits")
+    B, N, _, C = x.shape
+    b = _bins_u8(bins, C)
+    with _on(x.device):
+        row_loss = torch.empty(B, N, dtype=torch.float32, device=x.device)   # the kernel writes every element
+        row_count = torch.empty(B, N, dtype=torch.int32, device=x.device)
+        if B:
+            _launch("ps_binned_cross_entropy_f32", _ptr(x), _ptr(b), _ptr(row_loss), _ptr(row_count), B, N, C, _stream(x))
+    return row_loss, row_count
+
+
+def binned_cross_entropy_backward(logits: torch.Tensor, bins: torch.Tensor, grad_row: torch.Tensor) -> torch.Tensor:
+    """K35.  Vector-Jacobian product of ``binned_cross_entropy`` towards the logits: ``grad_logits`` (B,N,N,C) fp32 with
+    ``grad_row[b,i] * (softmax(x_ij)_k - [k == bins_ij])`` and exact zeros, all C of them, where the label is outside
+    ``[0, C)``.  One pass: reads the logits once and writes every element once (include/protstruc_pairhead.h)."""
+    check_binned_shapes(logits, bins, grad_row)
+    x, g = _f32c(logits, "logits"), _f32c(grad_row, "grad_row")
+    B, N, _, C = x.shape
+    b = _bins_u8(bins, C)
+    with _on(x.device):
+        out = torch.empty(B, N, N, C, dtype=torch.float32, device=x.device)
+        if B:
+            _launch("ps_binned_cross_entropy_backward_f32", _ptr(x), _ptr(b), _ptr(g), _ptr(out), B, N, C, _stream(x))
+    return out
+
+
+def binned_expectation(logits: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    """K36.  Expectations under the softmax of ``logits`` (B,N,N,C): ``out`` (V,B,N,N) fp32 with ``out[v,b,i,j] = sum_k
+    softmax(x_ij)_k * values[b,v,k]`` for the ``1 <= V <= 4`` tables ``values`` (B,V,C).  One pass over the logits serves all
+    tables; no softmax tensor is built (include/protstruc_pairhead.h)."""
+    check_binned_shapes(logits, values=values)
+    x, v = _f32c(logits, "logits"), _f32c(values, "values")
+    B, N, _, C = x.shape
+    V = v.shape[1]
+    with _on(x.device):
+        out = torch.empty(V, B, N, N, dtype=torch.float32, device=x.device)
+        if B:
+            _launch("ps_binned_expectation_f32", _ptr(x), _ptr(v), _ptr(out), B, N, C, V, _stream(x))
+    return out
+
+
 EDGE_MAX_PAIRS = 64   # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
 EDGE_MAX_RBF = 64     # PS_EDGE_MAX_RBF: the centres travel in the kernel's arguments
 

@@ -696,6 +696,88 @@ class StructureBatch:
         fnat = have.sum(dim=(1, 2)).to(torch.float64) / n_native.to(torch.float64)     # 0 / 0 = NaN
         return fnat.to(torch.float32), n_native
 
+    # ------------------------------------------------------------------ pair heads
+    def _pseudo_beta(self):
+        """(points (B,N,3), mask (B,N)): CB where the residue has one, else CA (glycine), with the mask to match"""
+        present = self._present_atoms()
+        ca = int(ATOM.CA)
+        cb = int(ATOM.CB)
+        if self.max_n_atoms_per_residue <= cb:
+            return self.xyz[:, :, ca], present[:, :, ca]
+        has_cb = present[:, :, cb]
+        points = torch.where(has_cb[:, :, None], self.xyz[:, :, cb], self.xyz[:, :, ca])
+        return points, has_cb | present[:, :, ca]
+
+    def distogram_loss(self, logits: torch.Tensor, breaks=None) -> torch.Tensor:
+        """AlphaFold 2's distogram loss of a distogram head's ``logits`` (B,N,N,C) against this batch, (B,)
+        (``geometry.distogram_loss``): the cross-entropy against the bins of the distances between pseudo-beta atoms -- CB
+        where present, else CA -- over the pairs of residues that have one.  ``breaks``: ``C - 1`` bin edges (default 2.3125
+        .. 21.6875 A).  Differentiable with respect to ``logits``; the coordinates only choose the bins."""
+        from . import geometry
+
+        points, mask = self._pseudo_beta()
+        return geometry.distogram_loss(logits, points, mask, breaks)
+
+    def _aligned_error_operands(self, target: "StructureBatch", a1: str, a2: str, a3: str, atom: str):
+        """Frames, points and masks of this batch and of ``target`` as :meth:`frame_aligned_point_error` builds them: the
+        Gram-Schmidt frames of (a1, a2, a3) with the origin at ``a2``, ``atom`` of every residue as its point, the frame
+        mask the residues whose three frame atoms are present in both batches, the point mask those whose ``atom`` is."""
+        B, N, A = self.xyz.shape[:3]
+        if target.get_batch_size() != 1 and B != target.get_batch_size():
+            raise ValueError("Batch size of the two structures must be the same.")
+        txyz = target.get_xyz().detach().to(self.device)
+        if tuple(txyz.shape[1:]) != (N, A, 3):
+            raise ValueError(f"target coordinates {tuple(txyz.shape)} do not match this batch's {tuple(self.xyz.shape)}")
+        s1, s2, s3, sp = int(ATOM[a1]), int(ATOM[a2]), int(ATOM[a3]), int(ATOM[atom])
+        present = torch.ones(B, N, A, dtype=torch.bool, device=self.device)
+        for m in (self.atom_mask, target.get_atom_mask()):
+            if m is not None:
+                present = present & (m.to(self.device) != 0)      # (1,N,A) of a single-structure target broadcasts
+        frame_mask = present[:, :, s1] & present[:, :, s2] & present[:, :, s3]
+        if txyz.shape[0] != B:
+            txyz = txyz.expand(B, N, A, 3).contiguous()
+        with torch.no_grad():
+            rot, trans = ops.frames(self.xyz.detach(), s1, s2, s3, s2)
+            target_rot, target_trans = ops.frames(txyz, s1, s2, s3, s2)
+        return (rot, trans, self.xyz.detach()[:, :, sp], target_rot, target_trans, txyz[:, :, sp], frame_mask, present[:, :, sp])
+
+    def aligned_error(self, target: "StructureBatch", a1: str = "N", a2: str = "CA", a3: str = "C",
+                      atom: str = "CA") -> torch.Tensor:
+        """The aligned-error matrix of this batch against ``target``, (B,N,N) (``geometry.aligned_error``): the error of
+        residue j's ``atom`` seen from residue i's frame, ``|R_i^T (x_j - t_i) - R*_i^T (x*_j - t*_i)|`` -- the training
+        target of a PAE head.  Frames and masks as in :meth:`frame_aligned_point_error`; +inf where frame i or point j is
+        missing in either batch.  A single-structure target serves the whole batch.  Not differentiable."""
+        from . import geometry
+
+        return geometry.aligned_error(*self._aligned_error_operands(target, a1, a2, a3, atom))
+
+    def aligned_error_loss(self, logits: torch.Tensor, target: "StructureBatch", a1: str = "N", a2: str = "CA", a3: str = "C",
+                           atom: str = "CA", breaks=None) -> torch.Tensor:
+        """AlphaFold 2's predicted-aligned-error loss of a PAE head's ``logits`` (B,N,N,C), (B,)
+        (``geometry.aligned_error_loss``): the cross-entropy against the bins of :meth:`aligned_error` of this batch -- the
+        prediction -- against ``target``.  ``breaks``: ``C - 1`` bin edges (default 0 .. 31 A).  Differentiable with
+        respect to ``logits``; the coordinates only choose the bins."""
+        from . import geometry
+
+        *operands, frame_mask, point_mask = self._aligned_error_operands(target, a1, a2, a3, atom)
+        return geometry.aligned_error_loss(logits, *operands, frame_mask, point_mask, breaks)
+
+    def predicted_aligned_error(self, logits: torch.Tensor) -> torch.Tensor:
+        """The expected aligned error under a PAE head's ``logits`` (B,N,N,C), (B,N,N)
+        (``geometry.predicted_aligned_error``); +inf where either residue is outside this batch's residue mask."""
+        from . import geometry
+
+        pae = geometry.predicted_aligned_error(logits)
+        inside = self.residue_mask[:, :, None] & self.residue_mask[:, None, :]
+        return pae.masked_fill(~inside, float("inf"))
+
+    def predicted_tm_score(self, logits: torch.Tensor, interface: bool = False) -> torch.Tensor:
+        """AlphaFold's predicted TM-score of a PAE head's ``logits`` (B,N,N,C) over this batch's residue mask, (B,)
+        (``geometry.predicted_tm_score``); with ``interface`` over the pairs of residues of different chains only (ipTM)."""
+        from . import geometry
+
+        return geometry.predicted_tm_score(logits, self.residue_mask, self._chain_keys(), interface)
+
     # ------------------------------------------------------------------ edge features
     def _edge_offsets(self, idx: torch.Tensor, max_offset: int) -> torch.Tensor:
         """(B,N,k) int64 class of every edge of ``idx`` (padding -1): ``clip(r_i - r_j + max_offset, 0, 2 max_offset)``

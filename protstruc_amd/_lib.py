@@ -1,5 +1,5 @@
-"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h, include/protstruc_contacts.h and
-include/protstruc_pairhead.h).
+"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h, include/protstruc_contacts.h,
+include/protstruc_pairhead.h and include/protstruc_superpose.h).
 
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
@@ -168,6 +168,29 @@ PAIRHEAD_SIGNATURES = {
     "ps_binned_expectation_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
 }
 
+# The superposition entry points (K37 - K40) are declared in include/protstruc_superpose.h, with a version of their own
+# (PS_SUPERPOSE_API): PS_ABI_VERSION, PS_CONTACTS_API, PS_PAIRHEAD_API and every earlier declaration stay as they were.
+EXPECTED_SUPERPOSE_API = 1  # PS_SUPERPOSE_API of include/protstruc_superpose.h
+
+
+class SuperposeObjective(ctypes.Structure):
+    """``ps_superpose_objective`` of include/protstruc_superpose.h, field for field."""
+    _fields_ = [("kind", ctypes.c_int), ("param", ctypes.c_float)]
+
+
+# name -> (restype, argtypes); mirrors include/protstruc_superpose.h one to one.  objectives is a HOST array of
+# SuperposeObjective (a ctypes array, or its address)
+SUPERPOSE_SIGNATURES = {
+    "ps_superpose_api": (_c_int, []),
+    "ps_superpose_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p] + [_c_f32p] * 4 + [_c_int, _c_int, _c_int, _c_stream]),
+    "ps_superpose_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p] + [_c_f32p] * 7 + [_c_int, _c_int, _c_int, _c_stream]),
+    "ps_superpose_search_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, _c_f32p, ctypes.c_void_p, _c_int] + [_c_f32p] * 4 +
+                                [_c_int, _c_int, _c_stream]),
+    "ps_superpose_seed_count": (_c_int, [_c_int]),
+    "ps_superpose_seed": (_c_int, [_c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
+    "ps_superpose_workspace_floats": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+}
+
 _lib = None
 
 
@@ -237,6 +260,14 @@ def load():
     if pairhead != EXPECTED_PAIRHEAD_API:
         raise HipLibraryError(f"{LIB_PATH} has pair-head API version {pairhead}, this package binds version "
                               f"{EXPECTED_PAIRHEAD_API}: rebuild with `python -m protstruc_amd.build --force`")
+    for name, (restype, argtypes) in SUPERPOSE_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+    superpose = lib.ps_superpose_api()
+    if superpose != EXPECTED_SUPERPOSE_API:
+        raise HipLibraryError(f"{LIB_PATH} has superposition API version {superpose}, this package binds version "
+                              f"{EXPECTED_SUPERPOSE_API}: rebuild with `python -m protstruc_amd.build --force`")
     _lib = lib
     return lib
 

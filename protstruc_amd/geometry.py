@@ -18,7 +18,9 @@ hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward
 that turns its indices into edge features; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
 features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``); ``side_chain_torsions``
 measures chi1 .. chi4, differentiably in the coordinates, and ``set_side_chain_torsions`` turns the side chains to given
-angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards).
+angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards); ``superposition_rmsd`` is the
+RMSD after optimal superposition, differentiable in both point sets (``ops.superpose`` / ``ops.superpose_backward``), and
+``tm_score``, ``gdt`` and ``superposition_scores`` are maxima over superpositions by a seeded search (``ops.superpose_search``).
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -983,6 +985,158 @@ def predicted_tm_score(logits, residue_mask, chain_idx=None, interface: bool = F
     term = torch.where(pair > 0, term, torch.zeros_like(term))       # whatever the logits of the padding hold stays out
     per_row = term.sum(dim=-1) / (1e-8 + pair.sum(dim=-1))
     return (per_row * mask).amax(dim=1).float()
+
+
+# ---- superposition scores: aligned RMSD, TM-score, GDT (K37 - K40) -------------------------------------------------------------
+class SuperpositionRMSD(NamedTuple):
+    """The RMSD after optimal superposition with the transform that attains it (``superposition_rmsd``)."""
+    rmsd: torch.Tensor     # (B,) fp32; NaN where no point counts
+    rot: torch.Tensor      # (B,3,3) fp32: a proper rotation
+    trans: torch.Tensor    # (B,3) fp32: R a + t lies on b
+
+
+class SuperpositionScore(NamedTuple):
+    """A score maximised over superpositions with the transform that attains it (``tm_score``)."""
+    score: torch.Tensor    # (B,) fp32
+    rot: torch.Tensor      # (B,3,3) fp32
+    trans: torch.Tensor    # (B,3) fp32
+
+
+class SuperpositionScores(NamedTuple):
+    """TM-score, GDT-TS and GDT-HA of one search (``superposition_scores``), each (B,) fp32."""
+    tm: torch.Tensor
+    gdt_ts: torch.Tensor
+    gdt_ha: torch.Tensor
+
+
+GDT_TS_CUTOFFS = (1.0, 2.0, 4.0, 8.0)
+GDT_HA_CUTOFFS = (0.5, 1.0, 2.0, 4.0)
+
+
+class _SuperpositionRMSD(torch.autograd.Function):
+    """ops.superpose with ops.superpose_backward as the vector-Jacobian product of its rmsd."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, mask):
+        R, t, rmsd, wsum = ops.superpose(a, b, weight, mask)
+        ctx.save_for_backward(a, b, weight, mask, R, t, rmsd, wsum)
+        ctx.dtypes = (a.dtype, b.dtype)
+        ctx.mark_non_differentiable(R, t)
+        return rmsd, R, t
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_rmsd, _grad_rot, _grad_trans):
+        a, b, weight, mask, R, t, rmsd, wsum = ctx.saved_tensors
+        grad_a, grad_b = ops.superpose_backward(a, b, weight, mask, R, t, rmsd, wsum, grad_rmsd)
+        if grad_b is None and ctx.needs_input_grad[1]:
+            raise RuntimeError("superposition_rmsd: a target shared by the batch, b (1,M,3), is a constant and gets no gradient")
+        return (grad_a.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None,
+                grad_b.to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None, None, None)
+
+
+def superposition_rmsd(a, b, weight=None, mask=None) -> SuperpositionRMSD:
+    """The RMSD of ``a`` (B,M,3) against ``b`` (B,M,3), or (1,M,3) as one target for all, after the optimal weighted
+    superposition: ``SuperpositionRMSD(rmsd (B,), rot (B,3,3), trans (B,3))`` with ``rmsd = sqrt(sum w |rot a + trans - b|^2 /
+    sum w)`` over the points in ``mask`` (B,M; None = all) with ``weight`` (B,M; None = 1) above 0.  The fit and the residuals
+    are double arithmetic on the float32 inputs (one HIP kernel, ``ops.superpose``): identical structures give an RMSD at
+    the rounding of the coordinates, and NaN under the mask reaches nothing.  No counted point: NaN.
+
+    Differentiable in ``a`` and ``b`` through ``rmsd`` only (a second kernel, ``ops.superpose_backward``): at the optimum the
+    derivative through the transform vanishes, so the gradient is the one of the residuals at a fixed transform.  ``rot``,
+    ``trans`` and ``weight`` get no gradient; a structure with ``rmsd = 0`` passes none (the gradient of a norm at 0), nor does
+    one without points.  No double backward.  Tensors on the GPU."""
+    ops.check_superpose_shapes(a, b, weight, mask)
+    weight = None if weight is None else weight.detach()
+    return SuperpositionRMSD(*_SuperpositionRMSD.apply(a, b, weight, mask))
+
+
+def tm_d0(length):
+    """The distance scale of the TM-score for a target of ``length`` residues: ``1.24 cbrt(L - 15) - 1.8`` for L > 21, else
+    0.5, and never below 0.5.  A number gives a float, a tensor a float64 tensor."""
+    if isinstance(length, torch.Tensor):
+        L = length.double()
+        return torch.where(L > 21, (1.24 * torch.sign(L - 15.0) * (L - 15.0).abs() ** (1.0 / 3.0) - 1.8).clamp(min=0.5),
+                           torch.full_like(L, 0.5))
+    L = float(length)
+    return max(0.5, float(1.24 * np.cbrt(L - 15.0) - 1.8)) if L > 21 else 0.5
+
+
+def _search_operands(a, b, mask, l_norm):
+    B, M, _ = ops.check_superpose_shapes(a, b, None, mask, None, None, ops.SUPERPOSE_MAX_POINTS)
+    a, b = a.detach(), b.detach()
+    if l_norm is None:      # the number of points that count, and 1 for a structure without any (its score is 0 anyway)
+        l_norm = (torch.full((B,), float(M), device=a.device) if mask is None
+                  else (mask.to(a.device) != 0).sum(dim=1).clamp(min=1).float())
+    else:
+        l_norm = torch.as_tensor(l_norm, dtype=torch.float32, device=a.device).expand(B).contiguous()
+    return a, b, mask, l_norm
+
+
+def _search(a, b, mask, l_norm, d0, cutoffs, with_tm):
+    """One launch of ``ops.superpose_search`` with the objectives (TM at d0 if ``with_tm``, then a count per cutoff) where one
+    d0 serves the batch -- it is given, or every structure's ``tm_d0(l_norm)`` is the same --, else one launch per distinct
+    d0 over the structures that share it.  The default d0 is read from ``l_norm`` on the host."""
+    counts = [(ops.SUPERPOSE_COUNT, float(c)) for c in cutoffs]
+    if not with_tm:
+        return ops.superpose_search(a, b, mask, l_norm, counts)
+    B = a.shape[0]
+    scales = [float(d0)] * B if d0 is not None else [tm_d0(x) for x in l_norm.tolist()]
+    distinct = sorted(set(scales))
+    if len(distinct) <= 1:
+        return ops.superpose_search(a, b, mask, l_norm, [(ops.SUPERPOSE_TM, distinct[0] if distinct else 1.0)] + counts)
+    n_obj = 1 + len(counts)
+    score = torch.empty(B, n_obj, dtype=torch.float32, device=a.device)
+    rot = torch.empty(B, n_obj, 3, 3, dtype=torch.float32, device=a.device)
+    trans = torch.empty(B, n_obj, 3, dtype=torch.float32, device=a.device)
+    for value in distinct:
+        idx = torch.tensor([k for k, x in enumerate(scales) if x == value], device=a.device)
+        part = ops.superpose_search(a[idx], b[idx] if b.shape[0] == B else b, None if mask is None else mask[idx], l_norm[idx],
+                                    [(ops.SUPERPOSE_TM, value)] + counts)
+        score[idx], rot[idx], trans[idx] = part
+    return score, rot, trans
+
+
+def tm_score(a, b, mask=None, l_norm=None, d0=None) -> SuperpositionScore:
+    """The TM-score of the model ``a`` (B,M,3) against the target ``b`` (B,M,3) with the residue correspondence given:
+    ``SuperpositionScore(score (B,), rot (B,3,3), trans (B,3))``, ``score = max over superpositions of sum_i 1 / (1 + d_i^2 /
+    d0^2) / l_norm`` over the points in ``mask`` (B,M; None = all).  ``l_norm`` (B,) or a number defaults to the number of
+    points that count; ``d0`` defaults to ``tm_d0(l_norm)`` per structure, which is read on the host (pass ``d0`` to keep the
+    call free of a synchronisation).  The maximum is taken by the library's seeded search (``ops.superpose_search``,
+    include/protstruc_superpose.h), one wave per seed: it is not the TM-score program's search -- another seed schedule,
+    the selection radius doubled where that adds 0.5 -- and there is no sequence alignment.  Deterministic; not
+    differentiable."""
+    a, b, mask, l_norm = _search_operands(a, b, mask, l_norm)
+    score, rot, trans = _search(a, b, mask, l_norm, d0, (), True)
+    return SuperpositionScore(*(x[:, 0].clone(memory_format=torch.contiguous_format) for x in (score, rot, trans)))
+
+
+def gdt(a, b, mask=None, l_norm=None, cutoffs=GDT_TS_CUTOFFS) -> torch.Tensor:
+    """The global distance test of ``a`` (B,M,3) against ``b`` (B,M,3), (B,) fp32: the mean over ``cutoffs`` of the largest
+    fraction of points (of ``l_norm``, default the points in ``mask``) within the cutoff of their partner under one
+    superposition -- the maximum over the superpositions the library's seeded search visits (``tm_score``), one launch with
+    one objective per cutoff.  Not LGA's search; no sequence alignment.  Not differentiable."""
+    a, b, mask, l_norm = _search_operands(a, b, mask, l_norm)
+    return _search(a, b, mask, l_norm, None, cutoffs, False)[0].mean(dim=1)
+
+
+def gdt_ts(a, b, mask=None, l_norm=None) -> torch.Tensor:
+    """GDT-TS: ``gdt`` with the cutoffs 1, 2, 4 and 8 A."""
+    return gdt(a, b, mask, l_norm, GDT_TS_CUTOFFS)
+
+
+def gdt_ha(a, b, mask=None, l_norm=None) -> torch.Tensor:
+    """GDT-HA: ``gdt`` with the cutoffs 0.5, 1, 2 and 4 A."""
+    return gdt(a, b, mask, l_norm, GDT_HA_CUTOFFS)
+
+
+def superposition_scores(a, b, mask=None, l_norm=None) -> SuperpositionScores:
+    """``SuperpositionScores(tm, gdt_ts, gdt_ha)`` of ``a`` (B,M,3) against ``b`` (B,M,3), each (B,), from a single launch of
+    six objectives -- TM at ``tm_d0(l_norm)`` and the counts within 0.5, 1, 2, 4 and 8 A -- where one d0 serves the batch
+    (``tm_score``); the same numbers as ``tm_score``, ``gdt_ts`` and ``gdt_ha`` give one by one."""
+    a, b, mask, l_norm = _search_operands(a, b, mask, l_norm)
+    score = _search(a, b, mask, l_norm, None, (0.5, 1.0, 2.0, 4.0, 8.0), True)[0]
+    return SuperpositionScores(score[:, 0].clone(memory_format=torch.contiguous_format), score[:, 2:6].mean(dim=1), score[:, 1:5].mean(dim=1))
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

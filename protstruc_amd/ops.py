@@ -1846,6 +1846,126 @@ def binned_expectation(logits: torch.Tensor, values: torch.Tensor) -> torch.Tens
     return out
 
 
+SUPERPOSE_MAX_POINTS = 2048     # PS_SUPERPOSE_MAX_POINTS of include/protstruc_superpose.h: the search keeps a structure's pairs in LDS
+SUPERPOSE_MAX_OBJECTIVES = 8    # PS_SUPERPOSE_MAX_OBJECTIVES
+SUPERPOSE_TM = 0                # PS_SUPERPOSE_TM: the objective 1 / (1 + d^2 / d0^2), param d0
+SUPERPOSE_COUNT = 1             # PS_SUPERPOSE_COUNT: the objective [d <= c], param c
+
+
+def check_superpose_shapes(a, b, weight=None, mask=None, grad_rmsd=None, l_norm=None, max_points=None) -> Tuple[int, int, bool]:
+    """Shape rules of ``superpose``, ``superpose_backward`` and ``superpose_search``, on shapes, dtypes and devices only (no
+    launch): ValueError.  ``a`` (B,M,3) floating point with ``B <= 65535`` and ``M >= 1`` (``M <= max_points`` where given);
+    ``b`` (B,M,3), or (1,M,3) as one target for all; ``weight`` (B,M) floating point; ``mask`` (B,M); ``grad_rmsd`` and
+    ``l_norm`` (B,) floating point.  Returns (B, M, one target for all)."""
+    shape = tuple(a.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"a must have shape (batch, points, 3), got {shape}")
+    if not a.dtype.is_floating_point:
+        raise ValueError(f"a must be a floating-point tensor, got {a.dtype}")
+    B, M = shape[:2]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if M < 1 or (max_points is not None and M > max_points):
+        raise ValueError(f"1 .. {max_points if max_points is not None else 'any number of'} points per structure, got {M}")
+    if tuple(b.shape) != shape and tuple(b.shape) != (1, M, 3):
+        raise ValueError(f"b must have shape {shape} or {(1, M, 3)} to match a, got {tuple(b.shape)}")
+    if not b.dtype.is_floating_point:
+        raise ValueError(f"b must be a floating-point tensor, got {b.dtype}")
+    if weight is not None:
+        _check_float_tensor(weight, (B, M), "weight", f"a {shape}")
+    _check_optional(mask, (B, M), "mask", "a", shape)
+    for name, t in (("grad_rmsd", grad_rmsd), ("l_norm", l_norm)):
+        if t is not None:
+            _check_float_tensor(t, (B,), name, f"a {shape}")
+    _same_device(a, b=b, weight=weight, mask=mask, grad_rmsd=grad_rmsd, l_norm=l_norm)
+    return B, M, tuple(b.shape) != shape
+
+
+def superpose(a: torch.Tensor, b: torch.Tensor, weight: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+    """K37.  The weighted optimal superposition of ``a`` (B,M,3) onto ``b`` (B,M,3), or (1,M,3) as one target for all, with
+    its RMSD: ``(R (B,3,3), t (B,3), rmsd (B,), wsum (B,))`` fp32.  Over the points with ``mask`` (B,M; None = all) set and
+    ``weight`` (B,M; None = 1) above 0: weighted centroids, the covariance about them, the 3x3 solve of ``kabsch`` -- always
+    a proper rotation --, and ``rmsd = sqrt(sum w |R a + t - b|^2 / sum w)`` from a pass of its own over the residuals, all in
+    double on the float32 inputs, so identical inputs give an RMSD at the rounding of the coordinates.  ``wsum = sum w``;
+    where it is 0, ``R``, ``t`` and ``rmsd`` are NaN.  Entries under the mask and coordinates at weight 0 are never read
+    (include/protstruc_superpose.h)."""
+    B, M, shared = check_superpose_shapes(a, b, weight, mask)
+    x, y, w, m = _f32c(a, "a"), _f32c(b, "b"), _f32c_opt(weight, "weight"), _u8c(mask, "mask")
+    dev = x.device
+    with _on(dev):
+        R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)       # the kernel writes every element
+        t = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        rmsd = torch.empty(B, dtype=torch.float32, device=dev)
+        wsum = torch.empty(B, dtype=torch.float32, device=dev)
+        if B:   # empty input: nothing to launch (an empty tensor has no device pointer)
+            _launch("ps_superpose_f32", _ptr(x), _ptr(y), _ptr(w), _ptr(m), _ptr(R), _ptr(t), _ptr(rmsd), _ptr(wsum), B, M,
+                    int(shared), _stream(x))
+    return R, t, rmsd, wsum
+
+
+def superpose_backward(a: torch.Tensor, b: torch.Tensor, weight: Optional[torch.Tensor], mask: Optional[torch.Tensor],
+                       R: torch.Tensor, t: torch.Tensor, rmsd: torch.Tensor, wsum: torch.Tensor, grad_rmsd: torch.Tensor):
+    """K38.  Vector-Jacobian product of ``superpose``'s ``rmsd`` towards the points: ``(grad_a (B,M,3), grad_b (B,M,3))``
+    fp32, ``grad_b`` None where ``b`` is one target for all (a constant).  At the optimum the derivative through ``R`` and
+    ``t`` vanishes: ``grad_a_i = g w_i R^T e_i / (wsum rmsd)`` and ``grad_b_i = -g w_i e_i / (wsum rmsd)`` with ``e_i = R a_i +
+    t - b_i``.  ``R``, ``t`` and the weights get no gradient.  Exact zeros under the mask, at weight 0, and for a
+    structure whose ``rmsd`` is 0 or not finite or whose ``R`` holds NaN; every element is written once.  ``R``, ``t``, ``rmsd``
+    and ``wsum`` are what ``superpose`` returned for the same inputs (include/protstruc_superpose.h)."""
+    B, M, shared = check_superpose_shapes(a, b, weight, mask, grad_rmsd)
+    x, y, w, m = _f32c(a, "a"), _f32c(b, "b"), _f32c_opt(weight, "weight"), _u8c(mask, "mask")
+    dev = x.device
+    for name, value, want in (("R", R, (B, 3, 3)), ("t", t, (B, 3)), ("rmsd", rmsd, (B,)), ("wsum", wsum, (B,))):
+        _check_out(value, want, name, dev)
+    g = _f32c(grad_rmsd, "grad_rmsd")
+    with _on(dev):
+        grad_a = torch.empty(B, M, 3, dtype=torch.float32, device=dev)
+        grad_b = None if shared else torch.empty(B, M, 3, dtype=torch.float32, device=dev)
+        if B:
+            _launch("ps_superpose_backward_f32", _ptr(x), _ptr(y), _ptr(w), _ptr(m), _ptr(R), _ptr(t), _ptr(rmsd), _ptr(wsum),
+                    _ptr(g), _ptr(grad_a), _ptr(grad_b), B, M, int(shared), _stream(x))
+    return grad_a, grad_b
+
+
+def _check_objectives(objectives):
+    """``objectives`` -- 1 .. SUPERPOSE_MAX_OBJECTIVES pairs (kind, param) -- as the host array the launcher reads"""
+    pairs = [(int(kind), float(param)) for kind, param in objectives]
+    if not 1 <= len(pairs) <= SUPERPOSE_MAX_OBJECTIVES:
+        raise ValueError(f"1 .. {SUPERPOSE_MAX_OBJECTIVES} objectives, got {len(pairs)}")
+    for kind, param in pairs:
+        if kind not in (SUPERPOSE_TM, SUPERPOSE_COUNT):
+            raise ValueError(f"an objective's kind is SUPERPOSE_TM (0) or SUPERPOSE_COUNT (1), got {kind}")
+        _check_scalar(param, "an objective's param", "positive")
+    return (_lib.SuperposeObjective * len(pairs))(*[_lib.SuperposeObjective(kind, param) for kind, param in pairs])
+
+
+def superpose_search(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tensor], l_norm: torch.Tensor, objectives):
+    """K39 / K40.  The seeded search for the superposition of ``a`` (B,M,3) onto ``b`` (B,M,3) that maximises each of up to
+    eight ``objectives`` -- a host sequence of ``(kind, param)``: ``(SUPERPOSE_TM, d0)`` sums ``1 / (1 + d^2 / d0^2)`` over the
+    points, ``(SUPERPOSE_COUNT, c)`` counts the points with ``d <= c`` --: ``(score (B,n_obj), R (B,n_obj,3,3), t (B,n_obj,3))``
+    fp32, ``score`` the best sum divided by ``l_norm`` (B,), with the transform that attains it.  ``M <=
+    SUPERPOSE_MAX_POINTS``; the points are those with ``mask`` (B,M; None = all) set, and entries under the mask are never
+    read.  The procedure -- fragment seeds, iterated selection within a radius, at most 20 fits per chain -- is defined in
+    include/protstruc_superpose.h and is deterministic: no atomics, repeated runs agree bit for bit.  A structure without
+    points scores 0 with NaN transforms.  Not differentiable."""
+    B, M, shared = check_superpose_shapes(a, b, None, mask, None, l_norm, SUPERPOSE_MAX_POINTS)
+    table = _check_objectives(objectives)
+    n_obj = len(table)
+    x, y, m, ln = _f32c(a, "a"), _f32c(b, "b"), _u8c(mask, "mask"), _f32c(l_norm, "l_norm")
+    if shared:
+        y = y.expand(B, M, 3).contiguous()
+    dev = x.device
+    with _on(dev):
+        score = torch.empty(B, n_obj, dtype=torch.float32, device=dev)       # the kernels write every element
+        R = torch.empty(B, n_obj, 3, 3, dtype=torch.float32, device=dev)
+        t = torch.empty(B, n_obj, 3, dtype=torch.float32, device=dev)
+        if B:
+            floats = _lib.load().ps_superpose_workspace_floats(B, M, n_obj)
+            workspace = torch.empty(floats, dtype=torch.float32, device=dev)
+            _launch("ps_superpose_search_f32", _ptr(x), _ptr(y), _ptr(m), _ptr(ln), ctypes.addressof(table), n_obj,
+                    _ptr(workspace), _ptr(score), _ptr(R), _ptr(t), B, M, _stream(x))
+    return score, R, t
+
+
 EDGE_MAX_PAIRS = 64   # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
 EDGE_MAX_RBF = 64     # PS_EDGE_MAX_RBF: the centres travel in the kernel's arguments
 

@@ -778,6 +778,73 @@ class StructureBatch:
 
         return geometry.predicted_tm_score(logits, self.residue_mask, self._chain_keys(), interface)
 
+    # ------------------------------------------------------------------ superposition scores
+    def _paired_with(self, target: "StructureBatch"):
+        """(target coordinates (B,N,A,3), atoms present here and in ``target`` (B,N,A), atoms present in ``target``
+        (B,N,A)); a single-structure target serves the whole batch."""
+        B, N, A = self.xyz.shape[:3]
+        if target.get_batch_size() != 1 and B != target.get_batch_size():
+            raise ValueError("Batch size of the two structures must be the same.")
+        txyz = target.get_xyz().detach().to(self.device)
+        if tuple(txyz.shape[1:]) != (N, A, 3):
+            raise ValueError(f"target coordinates {tuple(txyz.shape)} do not match this batch's {tuple(self.xyz.shape)}")
+        there = target._present_atoms().to(self.device).expand(B, N, A)
+        return txyz.expand(B, N, A, 3), self._present_atoms() & there, there
+
+    def rmsd(self, target: "StructureBatch", atoms=("CA",), superimpose: bool = True):
+        """The RMSD of this batch against ``target`` over the named ``atoms`` (``"all"``: every slot) that are present in
+        both.  ``superimpose=True``: after the optimal superposition, ``SuperpositionRMSD(rmsd (B,), rot (B,3,3), trans (B,3))``
+        (``geometry.superposition_rmsd``, HIP kernels forwards and backwards) -- differentiable with respect to this
+        batch's coordinates through ``rmsd``; the target is a constant.  ``superimpose=False``: as the structures lie,
+        (B,), plain torch on the masked atoms.  A structure without a common atom gives NaN."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        txyz, both, _ = self._paired_with(target)
+        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+        chosen[self._atom_slots(atoms)] = True
+        mask = (both & chosen).reshape(B, N * A)
+        if superimpose:
+            return geometry.superposition_rmsd(self.xyz.reshape(B, N * A, 3), txyz.reshape(B, N * A, 3), None, mask)
+        diff = torch.where(mask[:, :, None], self.xyz.reshape(B, N * A, 3) - txyz.reshape(B, N * A, 3), torch.zeros((), device=self.device))
+        return ((diff.double() ** 2).sum(dim=(1, 2)) / mask.sum(dim=1)).sqrt().float()      # 0 / 0 = NaN
+
+    def _score_operands(self, target: "StructureBatch", atom: str):
+        if not ATOM.is_valid(atom):
+            raise ValueError(f"Atom {atom} is not valid.")
+        s = self._atom_slots((atom,))[0]
+        txyz, both, there = self._paired_with(target)
+        l_norm = there[:, :, s].sum(dim=1).clamp(min=1).float()
+        return self.xyz.detach()[:, :, s], txyz[:, :, s], both[:, :, s], l_norm
+
+    def tm_score(self, target: "StructureBatch", atom: str = "CA"):
+        """The TM-score of this batch -- the model -- against ``target``, residue i of one being residue i of the other:
+        ``SuperpositionScore(score (B,), rot (B,3,3), trans (B,3))`` (``geometry.tm_score``).  The pairs are the residues
+        whose ``atom`` is present in both batches; the score is normalised by, and d0 taken from, the number of residues
+        whose ``atom`` is present in the target.  Not differentiable."""
+        from . import geometry
+
+        return geometry.tm_score(*self._score_operands(target, atom))
+
+    def gdt_ts(self, target: "StructureBatch", atom: str = "CA") -> torch.Tensor:
+        """GDT-TS of this batch against ``target``, (B,) (``geometry.gdt_ts``); pairs and normalisation as :meth:`tm_score`."""
+        from . import geometry
+
+        return geometry.gdt_ts(*self._score_operands(target, atom))
+
+    def gdt_ha(self, target: "StructureBatch", atom: str = "CA") -> torch.Tensor:
+        """GDT-HA of this batch against ``target``, (B,) (``geometry.gdt_ha``); pairs and normalisation as :meth:`tm_score`."""
+        from . import geometry
+
+        return geometry.gdt_ha(*self._score_operands(target, atom))
+
+    def superposition_scores(self, target: "StructureBatch", atom: str = "CA"):
+        """``SuperpositionScores(tm, gdt_ts, gdt_ha)`` of this batch against ``target`` from one search of six objectives
+        (``geometry.superposition_scores``); pairs and normalisation as :meth:`tm_score`."""
+        from . import geometry
+
+        return geometry.superposition_scores(*self._score_operands(target, atom))
+
     # ------------------------------------------------------------------ edge features
     def _edge_offsets(self, idx: torch.Tensor, max_offset: int) -> torch.Tensor:
         """(B,N,k) int64 class of every edge of ``idx`` (padding -1): ``clip(r_i - r_j + max_offset, 0, 2 max_offset)``

@@ -1,5 +1,5 @@
 """ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h, include/protstruc_contacts.h,
-include/protstruc_pairhead.h and include/protstruc_superpose.h).
+include/protstruc_pairhead.h, include/protstruc_superpose.h and include/protstruc_structalign.h).
 
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
@@ -191,6 +191,22 @@ SUPERPOSE_SIGNATURES = {
     "ps_superpose_workspace_floats": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
 }
 
+# The structure-alignment entry points (K41 - K44) are declared in include/protstruc_structalign.h, with a version of their
+# own (PS_STRUCTALIGN_API): PS_ABI_VERSION, the other headers' versions and every earlier declaration stay as they were.
+EXPECTED_STRUCTALIGN_API = 1  # PS_STRUCTALIGN_API of include/protstruc_structalign.h
+_c_i32p = ctypes.c_void_p
+
+# name -> (restype, argtypes); mirrors include/protstruc_structalign.h one to one
+STRUCTALIGN_SIGNATURES = {
+    "ps_structalign_api": (_c_int, []),
+    "ps_structalign_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "ps_nw_align_f32": (_c_int, [_c_f32p, _c_u8p, _c_u8p, ctypes.c_float, ctypes.c_void_p, _c_i32p, _c_i32p, _c_f32p, _c_int, _c_int,
+                                 _c_int, _c_stream]),
+    "ps_ca_secondary_structure_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, _c_int, _c_int, _c_stream]),
+    "ps_structure_align_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_f32p, _c_int, ctypes.c_void_p, _c_i32p, _c_i32p,
+                                        _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
+}
+
 _lib = None
 
 
@@ -268,6 +284,14 @@ def load():
     if superpose != EXPECTED_SUPERPOSE_API:
         raise HipLibraryError(f"{LIB_PATH} has superposition API version {superpose}, this package binds version "
                               f"{EXPECTED_SUPERPOSE_API}: rebuild with `python -m protstruc_amd.build --force`")
+    for name, (restype, argtypes) in STRUCTALIGN_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+    structalign = lib.ps_structalign_api()
+    if structalign != EXPECTED_STRUCTALIGN_API:
+        raise HipLibraryError(f"{LIB_PATH} has structure-alignment API version {structalign}, this package binds version "
+                              f"{EXPECTED_STRUCTALIGN_API}: rebuild with `python -m protstruc_amd.build --force`")
     _lib = lib
     return lib
 

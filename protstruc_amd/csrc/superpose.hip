@@ -21,77 +21,14 @@
 // workspace; seeds past the structure's count write S = -inf.
 // ---- K40, one wave per (structure, objective): lanes stride over the slots keeping the greatest S (the first on ties),
 // a butterfly over (S, seed) with the same order, then lanes 0 .. 11 copy the winner's R and t.
-#include "ps_common.hpp"
-#include "kabsch_solve.hpp"
-
-#include <math.h>
-
-#include "../../include/protstruc_superpose.h"
+#include "superpose_chain.hpp"
 
 namespace {
 
+using namespace ps_chain;       // the seed table, the transform helpers and the chain: superpose_chain.hpp
+
 constexpr int SP_WAVES = 4;
 constexpr int SP_THREADS = PS_WAVE * SP_WAVES;
-constexpr int SP_MAX_LENGTHS = 10;        // n >> k reaches 4 at k = 9 for n = 2048
-constexpr int SP_STRIDE_ROUNDS = 8;       // rounds of stride doubling: far more than 2048 points need
-
-// ---- the seed table (host and device) ----------------------------------------------------------------------------------------
-struct SeedTable {
-    int n_lengths, total;
-    int len[SP_MAX_LENGTHS], stride[SP_MAX_LENGTHS], count[SP_MAX_LENGTHS];
-};
-
-PS_HOST_DEVICE inline int seeds_of_length(int n, int len, int stride) { return 1 + (n - len + stride - 1) / stride; }
-
-PS_HOST_DEVICE inline void seed_table(int n, SeedTable& T) {
-    T.n_lengths = 0;
-    T.total = 0;
-#pragma unroll
-    for (int k = 0; k < SP_MAX_LENGTHS; ++k) T.len[k] = 0, T.stride[k] = 1, T.count[k] = 0;
-    if (n <= 0 || n > PS_SUPERPOSE_MAX_POINTS) return;
-    bool done = false;
-    int last = 0;
-#pragma unroll
-    for (int k = 0; k < SP_MAX_LENGTHS; ++k) {
-        int L = n >> k;
-        L = L > 4 ? L : 4;
-        if (n < 4) L = n;
-        if (!done && L != last) {
-            const int j = T.n_lengths;
-            T.len[j] = L;
-            T.stride[j] = L / 2 > 1 ? L / 2 : 1;
-            T.count[j] = seeds_of_length(n, L, T.stride[j]);
-            T.total += T.count[j];
-            T.n_lengths = j + 1;
-            last = L;
-        }
-        done = done || L <= 4;
-    }
-    for (int round = 0; round < SP_STRIDE_ROUNDS; ++round)
-#pragma unroll
-        for (int j = SP_MAX_LENGTHS - 1; j >= 0; --j)
-            if (j < T.n_lengths && T.total > PS_SUPERPOSE_MAX_SEEDS) {
-                T.total -= T.count[j];
-                T.stride[j] *= 2;
-                T.count[j] = seeds_of_length(n, T.len[j], T.stride[j]);
-                T.total += T.count[j];
-            }
-}
-
-PS_HOST_DEVICE inline bool seed_fragment(const SeedTable& T, int n, int s, int& start, int& len) {
-    bool found = false;
-    start = 0, len = 0;
-#pragma unroll
-    for (int j = 0; j < SP_MAX_LENGTHS; ++j) {
-        if (!found && j < T.n_lengths && s >= 0 && s < T.count[j]) {
-            len = T.len[j];
-            start = s == T.count[j] - 1 ? n - len : s * T.stride[j];
-            found = true;
-        }
-        s -= T.count[j];
-    }
-    return found;
-}
 
 // the slots a structure of up to M points needs: the largest seed count of any n <= M.  Filled once, never changed after.
 struct SeedSlots {
@@ -113,13 +50,6 @@ int seed_slots(int M) {
 }
 
 // ---- reductions ------------------------------------------------------------------------------------------------------------
-// sum over the wave, the same bits in every lane: a + b and b + a are the same number, so both partners of every step agree
-__device__ __forceinline__ double wave_all_sum(double v) {
-#pragma unroll
-    for (int o = PS_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // sums over the workgroup of four waves, the same bits in every thread; red holds NV * SP_WAVES doubles
 template <int NV>
 __device__ __forceinline__ void block_all_sum(double (&v)[NV], double* red) {
@@ -134,24 +64,6 @@ __device__ __forceinline__ void block_all_sum(double (&v)[NV], double* red) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = ((red[k * SP_WAVES] + red[k * SP_WAVES + 1]) + red[k * SP_WAVES + 2]) + red[k * SP_WAVES + 3];
 }
-
-struct Xform {
-    double R[9], t[3];
-};
-
-// t = cb - R ca, component by component
-__device__ __forceinline__ void set_translation(Xform& T, const double* ca, const double* cb) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) T.t[c] = cb[c] - ((T.R[c * 3] * ca[0] + T.R[c * 3 + 1] * ca[1]) + T.R[c * 3 + 2] * ca[2]);
-}
-
-// e = R a + t - b
-__device__ __forceinline__ void residual(const Xform& T, const double* a, const double* b, double* e) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) e[c] = (((T.R[c * 3] * a[0] + T.R[c * 3 + 1] * a[1]) + T.R[c * 3 + 2] * a[2]) + T.t[c]) - b[c];
-}
-
-__device__ __forceinline__ double norm2(const double* e) { return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]; }
 
 // ---- K37 / K38 -------------------------------------------------------------------------------------------------------------
 // the weight of point k as a double: 0 under the mask (the weight is then not read) and for a weight that is not > 0
@@ -287,69 +199,6 @@ struct Cloud {       // a structure's n compacted pairs in LDS: six planes of M 
     }
 };
 
-// the Kabsch fit of the points whose bit is set in the lanes' words; at least one is
-__device__ __forceinline__ void fit_selected(const Cloud& C, int lane, uint32_t sel, Xform& T) {
-    double s7[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < C.J; ++j)
-        if ((sel >> j) & 1u) {
-            double a[3], b[3];
-            C.load(j * PS_WAVE + lane, a, b);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s7[c] += a[c], s7[3 + c] += b[c];
-            s7[6] += 1.0;
-        }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) s7[k] = wave_all_sum(s7[k]);
-    const double ca[3] = {s7[0] / s7[6], s7[1] / s7[6], s7[2] / s7[6]}, cb[3] = {s7[3] / s7[6], s7[4] / s7[6], s7[5] / s7[6]};
-    double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < C.J; ++j)
-        if ((sel >> j) & 1u) {
-            double a[3], b[3];
-            C.load(j * PS_WAVE + lane, a, b);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a[c] -= ca[c], b[c] -= cb[c];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) h[i * 3 + k] += a[i] * b[k];
-        }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) h[k] = wave_all_sum(h[k]);
-    ps_kabsch_solve(h, T.R);
-    set_translation(T, ca, cb);
-}
-
-// one pass over the points under T: the lanes' selection words for d^2 < rr2, the number selected (wave-uniform) and,
-// with SCORE, the objective's sum S (the same bits in every lane)
-template <bool SCORE>
-__device__ __forceinline__ int sweep(const Cloud& C, int lane, const Xform& T, int kind, double p2, double rr2, uint32_t& sel,
-                                     double& S) {
-    double acc = 0.0;
-    uint32_t bits = 0;
-    int count = 0;
-    for (int j = 0; j < C.J; ++j) {
-        const int i = j * PS_WAVE + lane;
-        const bool ok = i < C.n;
-        double d2 = (double)INFINITY;
-        if (ok) {
-            double a[3], b[3], e[3];
-            C.load(i, a, b);
-            residual(T, a, b, e);
-            d2 = norm2(e);
-        }
-        if (SCORE) {
-            const double term = kind == PS_SUPERPOSE_TM ? 1.0 / (1.0 + d2 / p2) : (d2 <= p2 ? 1.0 : 0.0);
-            acc += ok ? term : 0.0;
-        }
-        const bool in = ok && d2 < rr2;
-        bits |= in ? (1u << j) : 0u;
-        count += __popcll(__ballot(in));
-    }
-    if (SCORE) S = wave_all_sum(acc);
-    sel = bits;
-    return count;
-}
-
 __device__ __forceinline__ void write_entry(float* __restrict__ entry, double S, const Xform& T) {
     uint32_t* __restrict__ words = reinterpret_cast<uint32_t*>(entry);
     words[0] = (uint32_t)__double2loint(S);
@@ -418,32 +267,9 @@ __global__ __launch_bounds__(SP_THREADS) void superpose_chains(const float* __re
         return;
     }
     const Cloud C{planes, M, n, (M + PS_WAVE - 1) / PS_WAVE};
-    const int kind = obj.kind[o], need = n < 3 ? n : 3;
-    const double p2 = obj.p2[o];
-    uint32_t previous = 0, everyone = 0;
-    for (int j = 0; j < C.J; ++j) {
-        const int i = j * PS_WAVE + lane;
-        previous |= (i >= start && i < start + len) ? (1u << j) : 0u;
-        everyone |= i < n ? (1u << j) : 0u;
-    }
-    fit_selected(C, lane, previous, T);
-    double best = -(double)INFINITY;
-    Xform kept = T;
-    for (int it = 0; it < PS_SUPERPOSE_MAX_ITERATIONS; ++it) {
-        double rr = it == 0 ? obj.r1[o] : obj.r[o], S = 0.0, unused = 0.0;
-        uint32_t sel;
-        int count = sweep<true>(C, lane, T, kind, p2, rr * rr, sel, S);
-        if (S > best) best = S, kept = T;
-        for (int k = 0; k < PS_SUPERPOSE_MAX_DOUBLINGS; ++k) {
-            if (count >= need) break;
-            rr = 2.0 * rr;
-            count = sweep<false>(C, lane, T, kind, p2, rr * rr, sel, unused);
-        }
-        if (count < need) sel = everyone;
-        if (__ballot(sel != previous) == 0) break;
-        previous = sel;
-        fit_selected(C, lane, sel, T);
-    }
+    double best;
+    Xform kept;
+    run_chain(C, lane, start, len, obj.kind[o], obj.p2[o], obj.r1[o], obj.r[o], best, kept);
     if (lane == 0) write_entry(entry, best, kept);
 }
 

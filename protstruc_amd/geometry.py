@@ -21,6 +21,8 @@ measures chi1 .. chi4, differentiably in the coordinates, and ``set_side_chain_t
 angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards); ``superposition_rmsd`` is the
 RMSD after optimal superposition, differentiable in both point sets (``ops.superpose`` / ``ops.superpose_backward``), and
 ``tm_score``, ``gdt`` and ``superposition_scores`` are maxima over superpositions by a seeded search (``ops.superpose_search``).
+``structure_alignment`` aligns two structures of different lengths without a given correspondence (``ops.structure_align``:
+dynamic programming alternated with that search), with ``needleman_wunsch`` and ``ca_secondary_structure`` as its parts.
 Type polymorphism follows the reference's ``with_tensor`` decorator
 (decorator.py:5-53): numpy arrays in -> numpy arrays out (float64 is computed in
 float32, as there), any tensor in -> tensor out.  Tensors must live on (or are
@@ -1104,7 +1106,8 @@ def tm_score(a, b, mask=None, l_norm=None, d0=None) -> SuperpositionScore:
     points that count; ``d0`` defaults to ``tm_d0(l_norm)`` per structure, which is read on the host (pass ``d0`` to keep the
     call free of a synchronisation).  The maximum is taken by the library's seeded search (``ops.superpose_search``,
     include/protstruc_superpose.h), one wave per seed: it is not the TM-score program's search -- another seed schedule,
-    the selection radius doubled where that adds 0.5 -- and there is no sequence alignment.  Deterministic; not
+    the selection radius doubled where that adds 0.5 -- and there is no sequence alignment: for two structures whose
+    correspondence is not known (other lengths, insertions, another chain) use ``structure_alignment``.  Deterministic; not
     differentiable."""
     a, b, mask, l_norm = _search_operands(a, b, mask, l_norm)
     score, rot, trans = _search(a, b, mask, l_norm, d0, (), True)
@@ -1115,7 +1118,8 @@ def gdt(a, b, mask=None, l_norm=None, cutoffs=GDT_TS_CUTOFFS) -> torch.Tensor:
     """The global distance test of ``a`` (B,M,3) against ``b`` (B,M,3), (B,) fp32: the mean over ``cutoffs`` of the largest
     fraction of points (of ``l_norm``, default the points in ``mask``) within the cutoff of their partner under one
     superposition -- the maximum over the superpositions the library's seeded search visits (``tm_score``), one launch with
-    one objective per cutoff.  Not LGA's search; no sequence alignment.  Not differentiable."""
+    one objective per cutoff.  Not LGA's search; no sequence alignment (``structure_alignment`` finds a correspondence where
+    none is given).  Not differentiable."""
     a, b, mask, l_norm = _search_operands(a, b, mask, l_norm)
     return _search(a, b, mask, l_norm, None, cutoffs, False)[0].mean(dim=1)
 
@@ -1137,6 +1141,79 @@ def superposition_scores(a, b, mask=None, l_norm=None) -> SuperpositionScores:
     a, b, mask, l_norm = _search_operands(a, b, mask, l_norm)
     score = _search(a, b, mask, l_norm, None, (0.5, 1.0, 2.0, 4.0, 8.0), True)[0]
     return SuperpositionScores(score[:, 0].clone(memory_format=torch.contiguous_format), score[:, 2:6].mean(dim=1), score[:, 1:5].mean(dim=1))
+
+
+# ---- structure alignment without a given correspondence (K41 - K44) ---------------------------------------------------------------
+class Alignment(NamedTuple):
+    """The alignment of one Needleman-Wunsch pass (``needleman_wunsch``)."""
+    map: torch.Tensor          # (B,Ma) int32: the column slot aligned to a row slot, or -1; strictly increasing
+    n_aligned: torch.Tensor    # (B,) int32
+    value: torch.Tensor        # (B,) fp32: the corner value of the DP table
+
+
+class StructureAlignment(NamedTuple):
+    """The alignment of two structures of different lengths (``structure_alignment``)."""
+    map: torch.Tensor            # (B,Ma) int32: the slot of b aligned to a slot of a, or -1; strictly increasing
+    n_aligned: torch.Tensor      # (B,) int32
+    tm_a: torch.Tensor           # (B,) fp32: the TM-score of the aligned pairs normalised by the length of a
+    tm_b: torch.Tensor           # (B,) fp32: ... by the length of b
+    rmsd: torch.Tensor           # (B,) fp32: the RMSD of the aligned pairs after their own optimal superposition
+    rot: torch.Tensor            # (B,3,3) fp32: the transform of tm_b, rot a + trans lies on b
+    trans: torch.Tensor          # (B,3) fp32
+    search_score: torch.Tensor   # (B,) fp32: what the alignment maximised, at the search's d0, per min(n_a, n_b)
+    start: torch.Tensor          # (B,) int32: the start that gave the alignment, 0 threading, 1 secondary structure
+
+
+def needleman_wunsch(score, gap, mask_a=None, mask_b=None) -> Alignment:
+    """One Needleman-Wunsch pass with TM-align's gap rule over ``score`` (B,Ma,Mb): ``Alignment(map (B,Ma) int32, n_aligned
+    (B,), value (B,))`` (one HIP kernel, ``ops.nw_align``; the recurrence and its ties are defined bit for bit in
+    include/protstruc_structalign.h).  ``gap <= 0`` is charged for leaving an aligned pair; ``mask_a`` (B,Ma) and ``mask_b``
+    (B,Mb) select the rows and columns (None = all).  Not differentiable."""
+    return Alignment(*ops.nw_align(score.detach(), gap, mask_a, mask_b))
+
+
+def ca_secondary_structure(points, mask=None) -> torch.Tensor:
+    """TM-align's secondary structure of CA traces ``points`` (B,M,3), (B,M) int8: 1 helix, 2 strand, 3 turn, 0 otherwise, -1
+    under ``mask`` (``ops.ca_secondary_structure``).  Chain breaks are not looked at."""
+    return ops.ca_secondary_structure(points.detach(), mask)
+
+
+def structure_alignment(a, b, mask_a=None, mask_b=None, d0=None, use_secondary_structure=True) -> StructureAlignment:
+    """Align ``a`` (B,Ma,3) onto ``b`` (B,Mb,3) -- CA traces of different lengths -- WITHOUT a given correspondence, in the
+    manner of TM-align: ``StructureAlignment(map, n_aligned, tm_a, tm_b, rmsd, rot, trans, search_score, start)``.  The points
+    are the slots with ``mask_a`` (B,Ma) / ``mask_b`` (B,Mb) set (None = all); ``map`` (B,Ma) holds for a slot of ``a`` the
+    slot of ``b`` aligned to it, or -1.  Two starts -- the best gapless threading, and a Needleman-Wunsch alignment of the
+    secondary structure (left out with ``use_secondary_structure=False``) -- are each refined by alternating a
+    Needleman-Wunsch pass over the TM terms ``1 / (1 + d^2 / d0^2)`` under the current transform with the seeded
+    superposition search over the aligned pairs (``ops.structure_align``, HIP kernels; include/protstruc_structalign.h is
+    the definition).  ``d0`` (a number or (B,)) is the scale of that search and defaults to ``tm_d0(min(n_a, n_b))``, which is
+    evaluated on the device: the alignment itself reads nothing on the host, and ``search_score`` is its best sum per
+    ``min(n_a, n_b)``.
+
+    ``tm_a`` and ``tm_b`` are ``tm_score`` of the aligned pairs normalised by ``n_a`` and by ``n_b`` (its default d0 is read on
+    the host: these two calls synchronise), ``rot`` / ``trans`` are those of ``tm_b``, and ``rmsd`` is ``superposition_rmsd`` of the
+    aligned pairs.  A pair with an empty side gives a map of -1, scores 0 and NaN elsewhere.  Not TM-align itself: two
+    starts instead of five, this library's search instead of TM-score's, no circular permutation.  Deterministic; not
+    differentiable."""
+    B, Ma, Mb = ops.check_structalign_shapes(a, b, mask_a, mask_b)
+    a, b = a.detach(), b.detach()
+    dev = a.device
+    n_a = torch.full((B,), Ma, device=dev) if mask_a is None else (mask_a.to(dev) != 0).sum(dim=1)
+    n_b = torch.full((B,), Mb, device=dev) if mask_b is None else (mask_b.to(dev) != 0).sum(dim=1)
+    if d0 is None:
+        scale = tm_d0(torch.minimum(n_a, n_b)).float()
+    else:
+        if not isinstance(d0, torch.Tensor):
+            ops._check_scalar(d0, "d0", "positive")
+        scale = torch.as_tensor(d0, dtype=torch.float32, device=dev).expand(B).contiguous()
+    found, n_aligned, score, _, _, _, start = ops.structure_align(a, b, mask_a, mask_b, scale, use_secondary_structure)
+    paired = found >= 0
+    partner = b[torch.arange(B, device=dev)[:, None], found.clamp(min=0).long()]       # (B,Ma,3): b through the map
+    partner = torch.where(paired[:, :, None], partner, torch.zeros((), dtype=b.dtype, device=dev))
+    tm_b = tm_score(a, partner, paired, n_b.clamp(min=1).float())
+    tm_a = tm_score(a, partner, paired, n_a.clamp(min=1).float())
+    rmsd = superposition_rmsd(a, partner, None, paired).rmsd
+    return StructureAlignment(found, n_aligned, tm_a.score, tm_b.score, rmsd, tm_b.rot, tm_b.trans, score, start)
 
 
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):

@@ -1966,7 +1966,124 @@ def superpose_search(a: torch.Tensor, b: torch.Tensor, mask: Optional[torch.Tens
     return score, R, t
 
 
-EDGE_MAX_PAIRS = 64   # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
+STRUCTALIGN_MAX_POINTS = 1024   # PS_STRUCTALIGN_MAX_POINTS of include/protstruc_structalign.h: both structures and the DP front live in LDS
+
+
+def check_structalign_shapes(a, b, mask_a=None, mask_b=None, d0=None) -> Tuple[int, int, int]:
+    """Shape rules of ``structure_align``, on shapes, dtypes and devices only (no launch): ValueError.  ``a`` (B,Ma,3) and ``b``
+    (B,Mb,3) floating point with ``B <= 65535`` and ``1 <= Ma, Mb <= STRUCTALIGN_MAX_POINTS``; ``mask_a`` (B,Ma), ``mask_b``
+    (B,Mb); ``d0`` (B,) floating point.  Returns (B, Ma, Mb)."""
+    for name, x in (("a", a), ("b", b)):
+        shape = tuple(x.shape)
+        if len(shape) != 3 or shape[2] != 3:
+            raise ValueError(f"{name} must have shape (batch, points, 3), got {shape}")
+        if not x.dtype.is_floating_point:
+            raise ValueError(f"{name} must be a floating-point tensor, got {x.dtype}")
+        if not 1 <= shape[1] <= STRUCTALIGN_MAX_POINTS:
+            raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} points per structure, got {shape[1]} in {name}")
+    B, Ma, Mb = a.shape[0], a.shape[1], b.shape[1]
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if b.shape[0] != B:
+        raise ValueError(f"b must have the batch size of a, {B}, got {b.shape[0]}")
+    _check_optional(mask_a, (B, Ma), "mask_a", "a", tuple(a.shape))
+    _check_optional(mask_b, (B, Mb), "mask_b", "b", tuple(b.shape))
+    if d0 is not None:
+        _check_float_tensor(d0, (B,), "d0", f"a {tuple(a.shape)}")
+    _same_device(a, b=b, mask_a=mask_a, mask_b=mask_b, d0=d0)
+    return B, Ma, Mb
+
+
+def _structalign_workspace(B: int, Ma: int, Mb: int, device) -> torch.Tensor:
+    return torch.empty(_lib.load().ps_structalign_workspace_bytes(B, Ma, Mb), dtype=torch.uint8, device=device)
+
+
+def nw_align(score: torch.Tensor, gap: float, mask_a: Optional[torch.Tensor] = None, mask_b: Optional[torch.Tensor] = None):
+    """K41.  One Needleman-Wunsch pass with TM-align's gap rule over ``score`` (B,Ma,Mb) -- the gap penalty ``gap <= 0`` is
+    charged only for leaving an aligned pair --: ``(map (B,Ma) int32, n_aligned (B,) int32, value (B,) fp32)``.  The rows
+    and columns are the slots with ``mask_a`` (B,Ma) and ``mask_b`` (B,Mb) set (None = all); ``map`` holds for a slot of the
+    rows the slot of the columns aligned to it, or -1, and ``value`` the DP's corner value.  Scores at masked slots are never
+    read.  The recurrence, its ties and the trace back are defined bit for bit in include/protstruc_structalign.h; the
+    table is double.  ``Ma, Mb <= STRUCTALIGN_MAX_POINTS``."""
+    shape = tuple(score.shape)
+    if len(shape) != 3:
+        raise ValueError(f"score must have shape (batch, rows, columns), got {shape}")
+    if not score.dtype.is_floating_point:
+        raise ValueError(f"score must be a floating-point tensor, got {score.dtype}")
+    B, Ma, Mb = shape
+    if B > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {B}")
+    if not (1 <= Ma <= STRUCTALIGN_MAX_POINTS and 1 <= Mb <= STRUCTALIGN_MAX_POINTS):
+        raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} rows and columns, got {Ma} x {Mb}")
+    g = float(gap)
+    if not (g <= 0 and g > -_INF):
+        raise ValueError(f"gap must be <= 0 and finite, got {gap}")
+    _check_optional(mask_a, (B, Ma), "mask_a", "score", shape)
+    _check_optional(mask_b, (B, Mb), "mask_b", "score", shape)
+    _same_device(score, mask_a=mask_a, mask_b=mask_b)
+    x, ma, mb = _f32c(score, "score"), _u8c(mask_a, "mask_a"), _u8c(mask_b, "mask_b")
+    dev = x.device
+    with _on(dev):
+        out = torch.empty(B, Ma, dtype=torch.int32, device=dev)           # the kernel writes every element
+        n_aligned = torch.empty(B, dtype=torch.int32, device=dev)
+        value = torch.empty(B, dtype=torch.float32, device=dev)
+        if B:
+            workspace = _structalign_workspace(B, Ma, Mb, dev)
+            _launch("ps_nw_align_f32", _ptr(x), _ptr(ma), _ptr(mb), g, _ptr(workspace), _ptr(out), _ptr(n_aligned), _ptr(value),
+                    B, Ma, Mb, _stream(x))
+    return out, n_aligned, value
+
+
+def ca_secondary_structure(points: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K44.  TM-align's secondary structure of CA traces ``points`` (B,M,3): (B,M) int8 -- 1 helix, 2 strand, 3 turn, 0
+    anything else and the two points at either end, -1 under ``mask`` (B,M; None = all) -- from the six distances among
+    the points i-2 .. i+2 counted after masking.  Chain breaks are not looked at (include/protstruc_structalign.h).
+    ``M <= STRUCTALIGN_MAX_POINTS``."""
+    B, M = _points_dims(points, 65535, STRUCTALIGN_MAX_POINTS)
+    if M < 1:
+        raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} points per structure, got {M}")
+    _check_optional(mask, (B, M), "mask", "points", tuple(points.shape))
+    _same_device(points, mask=mask)
+    x, m = _f32c(points, "points"), _u8c(mask, "mask")
+    dev = x.device
+    with _on(dev):
+        labels = torch.empty(B, M, dtype=torch.int8, device=dev)          # the kernel writes every element
+        if B:
+            _launch("ps_ca_secondary_structure_f32", _ptr(x), _ptr(m), _ptr(labels), B, M, _stream(x))
+    return labels
+
+
+def structure_align(a: torch.Tensor, b: torch.Tensor, mask_a: Optional[torch.Tensor], mask_b: Optional[torch.Tensor],
+                    d0: torch.Tensor, use_secondary_structure: bool = True):
+    """K42 / K43.  The alignment of ``a`` (B,Ma,3) onto ``b`` (B,Mb,3) without a given correspondence: ``(map (B,Ma) int32,
+    n_aligned (B,) int32, score (B,) fp32, R (B,3,3), t (B,3), n_points (B,2) int32, start (B,) int32)``.  The points are the
+    slots with ``mask_a`` / ``mask_b`` set (None = all; entries under a mask are never read); ``map`` holds for a slot of ``a``
+    the slot of ``b`` aligned to it, or -1; ``score`` is the best ``sum 1 / (1 + d^2 / d0^2)`` over the aligned pairs divided by
+    ``min(n_a, n_b)``, with the transform ``R a + t`` that attains it; ``start`` says which start gave it (0 threading, 1
+    secondary structure).  ``d0`` (B,) is positive and finite.  Two starts, each refined by alternating a Needleman-Wunsch
+    pass over the TM terms with the seeded superposition search of ``superpose_search`` over the aligned pairs, as
+    include/protstruc_structalign.h defines it; deterministic, no host read.  ``Ma, Mb <= STRUCTALIGN_MAX_POINTS``.  A pair
+    with an empty side gives a map of -1, score 0 and NaN transforms.  Not differentiable."""
+    B, Ma, Mb = check_structalign_shapes(a, b, mask_a, mask_b, d0)
+    x, y, ma, mb, scale = _f32c(a, "a"), _f32c(b, "b"), _u8c(mask_a, "mask_a"), _u8c(mask_b, "mask_b"), _f32c(d0, "d0")
+    dev = x.device
+    with _on(dev):
+        out = torch.empty(B, Ma, dtype=torch.int32, device=dev)           # the kernels write every element
+        n_aligned = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+        t = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        n_points = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        start = torch.empty(B, dtype=torch.int32, device=dev)
+        if B:
+            workspace = _structalign_workspace(B, Ma, Mb, dev)
+            _launch("ps_structure_align_f32", _ptr(x), _ptr(ma), _ptr(y), _ptr(mb), _ptr(scale), int(bool(use_secondary_structure)),
+                    _ptr(workspace), _ptr(out), _ptr(n_aligned), _ptr(score), _ptr(R), _ptr(t), _ptr(n_points), _ptr(start), B, Ma,
+                    Mb, _stream(x))
+    return out, n_aligned, score, R, t, n_points, start
+
+
+EDGE_MAX_PAIRS = 64  # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
 EDGE_MAX_RBF = 64     # PS_EDGE_MAX_RBF: the centres travel in the kernel's arguments
 
 

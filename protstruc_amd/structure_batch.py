@@ -47,6 +47,20 @@ class EdgeFeatures(NamedTuple):
     rel_rot: Optional[torch.Tensor]     # (B,N,k,3,3) fp32: the neighbour's frame in the source residue's frame, or None
 
 
+class StructuralAlignment(NamedTuple):
+    """``geometry.StructureAlignment`` with the sequence identity of the aligned pairs (``StructureBatch.structural_alignment``)."""
+    map: torch.Tensor            # (B,N) int32: the residue of the target aligned to a residue of this batch, or -1
+    n_aligned: torch.Tensor      # (B,) int32
+    tm_a: torch.Tensor           # (B,) fp32: TM-score normalised by this batch's length
+    tm_b: torch.Tensor           # (B,) fp32: ... by the target's
+    rmsd: torch.Tensor           # (B,) fp32
+    rot: torch.Tensor            # (B,3,3) fp32: the transform of tm_b
+    trans: torch.Tensor          # (B,3) fp32
+    search_score: torch.Tensor   # (B,) fp32
+    start: torch.Tensor          # (B,) int32
+    identity: torch.Tensor       # (B,) fp32: the fraction of aligned pairs with the same residue type
+
+
 def _default_device() -> torch.device:
     if torch.cuda.is_available():
         return torch.device("cuda", torch.cuda.current_device())
@@ -844,6 +858,34 @@ class StructureBatch:
         from . import geometry
 
         return geometry.superposition_scores(*self._score_operands(target, atom))
+
+    def structural_alignment(self, target: "StructureBatch", atom: str = "CA", use_secondary_structure: bool = True):
+        """Align this batch onto ``target`` WITHOUT a residue correspondence, in the manner of TM-align
+        (``geometry.structure_alignment``): ``StructuralAlignment(map, n_aligned, tm_a, tm_b, rmsd, rot, trans, search_score,
+        start, identity)``.  The two batches have the same batch size (or ``target`` holds one structure for all) and may
+        have different numbers of residues; the points are the residues whose ``atom`` is present.  ``map`` (B,N) int32
+        holds for a residue of this batch the residue of ``target`` aligned to it, or -1; ``tm_a`` is normalised by this
+        batch's length and ``tm_b`` by the target's; ``identity`` (B,) is the fraction of aligned pairs with the same residue
+        type, from the two sequences (ValueError without them; NaN where nothing is aligned).  Not differentiable."""
+        from . import geometry
+
+        if not ATOM.is_valid(atom):
+            raise ValueError(f"Atom {atom} is not valid.")
+        B = self.get_batch_size()
+        if target.get_batch_size() not in (1, B):
+            raise ValueError("Batch size of the two structures must be the same.")
+        s, ts = self._atom_slots((atom,))[0], target._atom_slots((atom,))[0]
+        txyz = target.get_xyz().detach().to(self.device)[:, :, ts]
+        there = target._present_atoms().to(self.device)[:, :, ts]
+        Nt = txyz.shape[1]
+        mine = self._residue_types("structural_alignment").long()          # before anything is launched: ValueError without a sequence
+        theirs = target._residue_types("structural_alignment").long().to(self.device).expand(B, Nt)
+        found = geometry.structure_alignment(self.xyz.detach()[:, :, s], txyz.expand(B, Nt, 3), self._present_atoms()[:, :, s],
+                                             there.expand(B, Nt), None, use_secondary_structure)
+        paired = found.map >= 0
+        same = paired & (mine == torch.gather(theirs, 1, found.map.clamp(min=0).long()))
+        identity = same.sum(dim=1).float() / paired.sum(dim=1).float()          # 0 / 0 = NaN
+        return StructuralAlignment(*found, identity)
 
     # ------------------------------------------------------------------ edge features
     def _edge_offsets(self, idx: torch.Tensor, max_offset: int) -> torch.Tensor:

@@ -1,5 +1,6 @@
 """ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h, include/protstruc_contacts.h,
-include/protstruc_pairhead.h, include/protstruc_superpose.h and include/protstruc_structalign.h).
+include/protstruc_pairhead.h, include/protstruc_superpose.h, include/protstruc_structalign.h and
+include/protstruc_ensemble.h).
 
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
@@ -207,6 +208,18 @@ STRUCTALIGN_SIGNATURES = {
                                         _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
 }
 
+# The ensemble entry points (K45, K46) are declared in include/protstruc_ensemble.h, with a version of their own
+# (PS_ENSEMBLE_API): PS_ABI_VERSION, the other headers' versions and every earlier declaration stay as they were.
+EXPECTED_ENSEMBLE_API = 1  # PS_ENSEMBLE_API of include/protstruc_ensemble.h
+
+# name -> (restype, argtypes); mirrors include/protstruc_ensemble.h one to one
+ENSEMBLE_SIGNATURES = {
+    "ps_ensemble_api": (_c_int, []),
+    "ps_rmsd_matrix_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
+    "ps_cluster_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_float, ctypes.c_void_p] + [_c_i32p] * 4 + [_c_int, _c_int, _c_stream]),
+    "ps_cluster_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
+}
+
 _lib = None
 
 
@@ -292,6 +305,14 @@ def load():
     if structalign != EXPECTED_STRUCTALIGN_API:
         raise HipLibraryError(f"{LIB_PATH} has structure-alignment API version {structalign}, this package binds version "
                               f"{EXPECTED_STRUCTALIGN_API}: rebuild with `python -m protstruc_amd.build --force`")
+    for name, (restype, argtypes) in ENSEMBLE_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+    ensemble = lib.ps_ensemble_api()
+    if ensemble != EXPECTED_ENSEMBLE_API:
+        raise HipLibraryError(f"{LIB_PATH} has ensemble API version {ensemble}, this package binds version "
+                              f"{EXPECTED_ENSEMBLE_API}: rebuild with `python -m protstruc_amd.build --force`")
     _lib = lib
     return lib
 

@@ -31,7 +31,8 @@ def sources():
 def _deps():
     return sources() + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + \
         [os.path.join(HERE, "..", "include", name) for name in ("protstruc_hip.h", "protstruc_contacts.h", "protstruc_pairhead.h",
-                                                                 "protstruc_superpose.h", "protstruc_structalign.h")]
+                                                                 "protstruc_superpose.h", "protstruc_structalign.h",
+                                                                 "protstruc_ensemble.h")]
 
 
 def source_hash():

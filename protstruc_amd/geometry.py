@@ -1216,6 +1216,68 @@ def structure_alignment(a, b, mask_a=None, mask_b=None, d0=None, use_secondary_s
     return StructureAlignment(found, n_aligned, tm_a.score, tm_b.score, rmsd, tm_b.rot, tm_b.trans, score, start)
 
 
+# ---- ensembles: all-against-all superposed RMSD and clustering by a cutoff (K45, K46) ---------------------------------------------
+class PairwiseRMSD(NamedTuple):
+    """The matrix of RMSDs after optimal superposition between the members of two batches (``pairwise_rmsd``)."""
+    rmsd: torch.Tensor     # (Ba,Bb) fp32; NaN where a pair has no point in common
+    count: torch.Tensor    # (Ba,Bb) int32: the number of points the pair has in common
+
+
+class Clusters(NamedTuple):
+    """The clusters of a distance matrix (``cluster_by_cutoff``), the largest first."""
+    label: torch.Tensor        # (G,B) int32: the cluster of an item, -1 where it is not valid
+    center: torch.Tensor       # (G,B) int32: the centre of cluster c at [.., c]; -1 from n_clusters on
+    size: torch.Tensor         # (G,B) int32: the size of cluster c, never increasing; 0 from n_clusters on
+    n_clusters: torch.Tensor   # (G,) int32
+
+
+def _batch_mask(mask, B: int, M: int):
+    """a mask (B,M), or (M,) shared by the batch, as (B,M)"""
+    if mask is not None and mask.ndim == 1 and tuple(mask.shape) == (M,):
+        return mask.expand(B, M)
+    return mask
+
+
+def pairwise_rmsd(a, b=None, mask_a=None, mask_b=None) -> PairwiseRMSD:
+    """The RMSD after optimal superposition of every member of ``a`` (Ba,M,3) against every member of ``b`` (Bb,M,3):
+    ``PairwiseRMSD(rmsd (Ba,Bb) fp32, count (Ba,Bb) int32)``.  ``b`` None compares ``a`` with itself: a symmetric matrix with
+    an exactly zero diagonal, half the work.  The points of a pair are those that both ``mask_a`` and ``mask_b`` count --
+    each (B,M), or (M,) shared by its batch, None = all; in the self comparison ``mask_a`` serves both sides --, ``count``
+    says how many; a pair without any is NaN, and NaN under a structure's own mask reaches nothing.  One tiled HIP kernel in
+    double (``ops.rmsd_matrix``): the five sums of a pair over the common points, then the 3x3 solve of ``kabsch``; no
+    broadcast of the coordinates over the pairs, no batched SVD.  The RMSD of identical members is about 1e-6 A, not 0
+    (include/protstruc_ensemble.h gives the bound): ``superposition_rmsd`` remains the tool when that matters, and the one
+    that returns rotations -- against a chosen medoid, say.
+
+    Not differentiable: the outputs carry no graph, and inputs that require grad are detached."""
+    a = a.detach()
+    b = None if b is None else b.detach()
+    if a.ndim == 3:
+        mask_a = _batch_mask(mask_a, a.shape[0], a.shape[1])
+        if b is not None and b.ndim == 3:
+            mask_b = _batch_mask(mask_b, b.shape[0], b.shape[1])
+    return PairwiseRMSD(*ops.rmsd_matrix(a, b, mask_a, mask_b, return_count=True))
+
+
+def cluster_by_cutoff(D, cutoff, valid=None) -> Clusters:
+    """Cluster the items of a distance matrix ``D`` (B,B), or of G matrices (G,B,B), by the rule of Daura et al. (GROMACS'
+    ``cluster -method gromos``): ``Clusters(label, center, size, n_clusters)``.  Items are neighbours where ``D <= cutoff``
+    (the upper triangle decides; NaN is no neighbour).  Among the items still unassigned -- at first those of ``valid``
+    ((B,) / (G,B), None = all) -- the one with the most unassigned neighbours, the lowest index on ties, becomes the centre
+    of the next cluster and is taken out with its neighbours, until none is left.  ``label`` (.., B) holds every item's
+    cluster, -1 where it is not valid; ``center`` and ``size`` (.., B) are indexed by cluster number, padded with -1 and 0;
+    ``n_clusters`` is () / (G,).  The largest cluster is cluster 0, its centre ``center[..., 0]`` -- the medoid by this rule.
+    HIP kernels (``ops.cluster``), integer work defined bit for bit, no host read: usable inside a captured graph.
+    ``B <= ops.CLUSTER_MAX_ITEMS``.  Not differentiable."""
+    D = D.detach()
+    single = D.ndim == 2
+    if single:
+        D = D[None]
+        valid = None if valid is None else valid[None]
+    out = ops.cluster(D, cutoff, valid)
+    return Clusters(*(t[0] for t in out)) if single else Clusters(*out)
+
+
 def _chain_break_matrix(chain_breaks, B: int, L: int, batched: bool):
     """chain_breaks as a (B, L) bool array / tensor ("the chain ends after residue i"), or None.  Accepts a list of
     residue indices (every structure), a list of B such lists, or a (B, L) ((L,) unbatched) boolean array / tensor."""

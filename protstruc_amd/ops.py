@@ -2083,6 +2083,104 @@ def structure_align(a: torch.Tensor, b: torch.Tensor, mask_a: Optional[torch.Ten
     return out, n_aligned, score, R, t, n_points, start
 
 
+CLUSTER_MAX_ITEMS = 4096   # PS_CLUSTER_MAX_ITEMS of include/protstruc_ensemble.h: the degrees of a matrix live in LDS
+RMSD_MATRIX_MAX_POINTS = 2 ** 31 - 17   # PS_RMSD_MATRIX_MAX_POINTS: the points are walked in chunks of 16 by an int
+
+
+def check_rmsd_matrix_shapes(a, b=None, mask_a=None, mask_b=None) -> Tuple[int, int, int]:
+    """Shape rules of ``rmsd_matrix``, on shapes, dtypes and devices only (no launch): ValueError.  ``a`` (Ba,M,3) floating
+    point with ``Ba <= 65535`` and ``1 <= M <= RMSD_MATRIX_MAX_POINTS``; ``b`` (Bb,M,3) likewise, or None -- self mode, ``a`` against itself, which takes
+    no ``mask_b``; ``mask_a`` (Ba,M) and ``mask_b`` (Bb,M).  Returns (Ba, Bb, M)."""
+    shape = tuple(a.shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"a must have shape (batch, points, 3), got {shape}")
+    if not a.dtype.is_floating_point:
+        raise ValueError(f"a must be a floating-point tensor, got {a.dtype}")
+    Ba, M = shape[:2]
+    if not 1 <= M <= RMSD_MATRIX_MAX_POINTS:
+        raise ValueError(f"1 .. {RMSD_MATRIX_MAX_POINTS} points per structure, got {M}")
+    Bb = Ba
+    if b is None:
+        if mask_b is not None:
+            raise ValueError("mask_b needs a b: in self mode (b None) mask_a serves both sides")
+    else:
+        if len(tuple(b.shape)) != 3 or tuple(b.shape[1:]) != (M, 3):
+            raise ValueError(f"b must have shape (batch, {M}, 3) to match a {shape}, got {tuple(b.shape)}")
+        if not b.dtype.is_floating_point:
+            raise ValueError(f"b must be a floating-point tensor, got {b.dtype}")
+        Bb = b.shape[0]
+    if Ba > 65535 or Bb > 65535:
+        raise ValueError(f"at most 65535 structures per call, got {max(Ba, Bb)}")
+    _check_optional(mask_a, (Ba, M), "mask_a", "a", shape)
+    if b is not None:
+        _check_optional(mask_b, (Bb, M), "mask_b", "b", tuple(b.shape))
+    _same_device(a, b=b, mask_a=mask_a, mask_b=mask_b)
+    return Ba, Bb, M
+
+
+def rmsd_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, mask_a: Optional[torch.Tensor] = None,
+                mask_b: Optional[torch.Tensor] = None, return_count: bool = False):
+    """K45.  The RMSD after optimal superposition of every structure of ``a`` (Ba,M,3) against every structure of ``b``
+    (Bb,M,3): (Ba,Bb) fp32, and with ``return_count`` the number of points each pair has in common, (Ba,Bb) int32.  ``b`` None
+    is self mode: ``a`` against itself, only the tiles on and above the diagonal computed, both planes exactly symmetric and
+    the diagonal exactly 0.  The points of a pair are those that ``mask_a`` (Ba,M) and ``mask_b`` (Bb,M) both count (None =
+    all); a pair without any is NaN, and NaN under a structure's own mask reaches nothing.  One tiled double-precision HIP
+    kernel over the five sums of a pair, the 3x3 solve of ``kabsch`` as its epilogue; no atomics, and a sub-batch gives the
+    block of the full matrix bit for bit.  The RMSD of identical members is NOT 0 but about 1e-6 A (the formula is
+    ``E0 - 2 tr``; include/protstruc_ensemble.h states the bound) -- ``superpose`` remains the tool when that matters."""
+    Ba, Bb, M = check_rmsd_matrix_shapes(a, b, mask_a, mask_b)
+    x, y, ma, mb = _f32c(a, "a"), _f32c_opt(b, "b"), _u8c(mask_a, "mask_a"), _u8c(mask_b, "mask_b")
+    dev = x.device
+    with _on(dev):
+        rmsd = torch.empty(Ba, Bb, dtype=torch.float32, device=dev)       # the kernel writes every element
+        count = torch.empty(Ba, Bb, dtype=torch.int32, device=dev) if return_count else None
+        if Ba and Bb:   # an empty tensor has no device pointer, and NULL for b means self mode
+            _launch("ps_rmsd_matrix_f32", _ptr(x), _ptr(ma), _ptr(y), _ptr(mb), _ptr(rmsd), _ptr(count), Ba, Bb, M, _stream(x))
+    return (rmsd, count) if return_count else rmsd
+
+
+def check_cluster_shapes(D, cutoff, valid=None) -> Tuple[int, int]:
+    """Shape rules of ``cluster``, on shapes, dtypes and devices only (no launch): ValueError.  ``D`` (G,B,B) floating point
+    with ``G <= 65535`` and ``1 <= B <= CLUSTER_MAX_ITEMS``; ``cutoff`` a finite number; ``valid`` (G,B).  Returns (G, B)."""
+    shape = tuple(D.shape)
+    if len(shape) != 3 or shape[1] != shape[2]:
+        raise ValueError(f"D must have shape (matrices, items, items), got {shape}")
+    if not D.dtype.is_floating_point:
+        raise ValueError(f"D must be a floating-point tensor, got {D.dtype}")
+    G, B = shape[:2]
+    if G > 65535:
+        raise ValueError(f"at most 65535 matrices per call, got {G}")
+    if not 1 <= B <= CLUSTER_MAX_ITEMS:
+        raise ValueError(f"1 .. {CLUSTER_MAX_ITEMS} items per matrix, got {B}")
+    _check_scalar(cutoff, "cutoff", "finite")
+    _check_optional(valid, (G, B), "valid", "D", shape)
+    _same_device(D, valid=valid)
+    return G, B
+
+
+def cluster(D: torch.Tensor, cutoff: float, valid: Optional[torch.Tensor] = None):
+    """K46.  Clustering of the distance matrices ``D`` (G,B,B) by ``cutoff`` after Daura et al. ("gromos"): ``(label (G,B),
+    center (G,B), size (G,B), n_clusters (G,))`` int32.  Two items are neighbours where ``D[min(i,j), max(i,j)] <= cutoff`` --
+    only the upper triangle is read, NaN is no neighbour --; among the items still active (at first those of ``valid``
+    (G,B), None = all) the one with the most active neighbours, the lowest index on ties, becomes the centre of the next
+    cluster and leaves with its active neighbours, until none is left.  ``label`` is -1 at invalid items; ``center`` and
+    ``size`` are indexed by cluster number, -1 and 0 from ``n_clusters`` on; sizes never increase.  Integer work, defined bit
+    for bit (include/protstruc_ensemble.h); two launches, no host read.  ``B <= CLUSTER_MAX_ITEMS``."""
+    G, B = check_cluster_shapes(D, cutoff, valid)
+    x, v = _f32c(D, "D"), _u8c(valid, "valid")
+    dev = x.device
+    with _on(dev):
+        label = torch.empty(G, B, dtype=torch.int32, device=dev)          # the kernels write every element
+        center = torch.empty(G, B, dtype=torch.int32, device=dev)
+        size = torch.empty(G, B, dtype=torch.int32, device=dev)
+        n_clusters = torch.empty(G, dtype=torch.int32, device=dev)
+        if G:
+            workspace = torch.empty(_lib.load().ps_cluster_workspace_bytes(G, B), dtype=torch.uint8, device=dev)
+            _launch("ps_cluster_f32", _ptr(x), _ptr(v), float(cutoff), _ptr(workspace), _ptr(label), _ptr(center), _ptr(size),
+                    _ptr(n_clusters), G, B, _stream(x))
+    return label, center, size, n_clusters
+
+
 EDGE_MAX_PAIRS = 64  # PS_EDGE_MAX_PAIRS of include/protstruc_hip.h: a residue's k * P distances live in LDS
 EDGE_MAX_RBF = 64     # PS_EDGE_MAX_RBF: the centres travel in the kernel's arguments
 

@@ -887,6 +887,45 @@ class StructureBatch:
         identity = same.sum(dim=1).float() / paired.sum(dim=1).float()          # 0 / 0 = NaN
         return StructuralAlignment(*found, identity)
 
+    # ------------------------------------------------------------------ ensembles
+    def _ensemble_points(self, atoms):
+        """((B,P,3) points, (B,P) mask) of the named ``atoms``: with ``"all"`` (or every slot) the zero-copy (B, N*A, 3) view
+        of the coordinates, else the chosen slots gathered, (B, N*len(atoms), 3); the mask is the atoms present"""
+        B, N, A = self.xyz.shape[:3]
+        slots = self._atom_slots(atoms)
+        xyz, present = self.xyz.detach(), self._present_atoms()
+        if len(slots) != A:
+            xyz, present = xyz[:, :, slots], present[:, :, slots]
+        return xyz.reshape(B, N * len(slots), 3), present.reshape(B, N * len(slots))
+
+    def rmsd_matrix(self, other: Optional["StructureBatch"] = None, atoms=("CA",)):
+        """The RMSD after optimal superposition of every structure of this batch against every structure of ``other``
+        (None: against every other structure of this batch) over the named ``atoms`` (``"all"``: every slot, on the
+        zero-copy view of the coordinates): ``PairwiseRMSD(rmsd (B,Bo) fp32, count (B,Bo) int32)``
+        (``geometry.pairwise_rmsd``, one HIP kernel).  Atom k of residue i of one is atom k of residue i of the other, so
+        the two batches have the same number of residues; a pair is compared over the atoms present in both, ``count`` of
+        them, and is NaN without any.  Not differentiable."""
+        from . import geometry
+
+        points, mask = self._ensemble_points(atoms)
+        if other is None:
+            return geometry.pairwise_rmsd(points, None, mask, None)
+        if other.get_max_n_residues() != self.get_max_n_residues() or other.max_n_atoms_per_residue != self.max_n_atoms_per_residue:
+            raise ValueError(f"the other batch's coordinates {tuple(other.xyz.shape)} do not match this batch's "
+                             f"{tuple(self.xyz.shape)}: the same number of residues and atom slots is required")
+        theirs, their_mask = other._ensemble_points(atoms)
+        return geometry.pairwise_rmsd(points, theirs.to(self.device), mask, their_mask.to(self.device))
+
+    def cluster(self, cutoff: float = 2.0, atoms=("CA",)):
+        """Cluster the structures of this batch by their mutual superposed RMSD over ``atoms`` (:meth:`rmsd_matrix`) with
+        the rule of Daura et al. at ``cutoff`` A (``geometry.cluster_by_cutoff``): ``Clusters(label (B,), center (B,), size
+        (B,), n_clusters ())``.  ``center[0]`` is the medoid of the largest cluster.  A structure without any of the atoms is
+        no member of anything (label -1).  HIP kernels from the coordinates to the labels, no host read."""
+        from . import geometry
+
+        found = self.rmsd_matrix(None, atoms)
+        return geometry.cluster_by_cutoff(found.rmsd, cutoff, found.count.diagonal() > 0)
+
     # ------------------------------------------------------------------ edge features
     def _edge_offsets(self, idx: torch.Tensor, max_offset: int) -> torch.Tensor:
         """(B,N,k) int64 class of every edge of ``idx`` (padding -1): ``clip(r_i - r_j + max_offset, 0, 2 max_offset)``

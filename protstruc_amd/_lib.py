@@ -1,6 +1,4 @@
-"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h, include/protstruc_contacts.h,
-include/protstruc_pairhead.h, include/protstruc_superpose.h, include/protstruc_structalign.h and
-include/protstruc_ensemble.h).
+"""ctypes binding of libprotstruc_hip.so (C ABI: include/protstruc_hip.h and the side headers listed in ``FAMILIES``).
 
 There is deliberately no fallback: if the shared library is missing or a launch
 fails, the caller gets an exception -- never a silent CPU / eager-PyTorch path.
@@ -143,23 +141,42 @@ SIGNATURES = {
     "ps_affine_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
 }
 
-# The closest-atom entry points (K31 / K32) are declared in include/protstruc_contacts.h, a header with a version of its
-# own (PS_CONTACTS_API), so that adding them changed neither PS_ABI_VERSION nor a declaration of protstruc_hip.h.
-EXPECTED_CONTACTS_API = 1  # PS_CONTACTS_API of include/protstruc_contacts.h
+# ---- the side headers: one family of entry points each ------------------------------------------------------------------
+# A family is declared in a header of its own with a version of its own (``PS_<FAMILY>_API``, returned by
+# ``ps_<family>_api()``), so that adding it changes neither PS_ABI_VERSION nor any earlier declaration.  Here it is a
+# signature table, an expected version and one line of FAMILIES; ``load()`` and ``build._deps()`` take the rest from there.
 _c_i16p = ctypes.c_void_p
+_c_i32p = ctypes.c_void_p
 
-# name -> (restype, argtypes); mirrors include/protstruc_contacts.h one to one
+
+class Family(NamedTuple):
+    header: str        # file name under include/
+    signatures: str    # module attribute: name -> (restype, argtypes), mirrors the header one to one
+    version_fn: str    # the entry point that returns the library's version of the header
+    expected: str      # module attribute: the version this package binds
+    word: str          # what ``load()`` calls the family when it refuses a library
+
+
+FAMILIES = (   # in load order
+    Family("protstruc_contacts.h", "CONTACT_SIGNATURES", "ps_contacts_api", "EXPECTED_CONTACTS_API", "contacts"),
+    Family("protstruc_pairhead.h", "PAIRHEAD_SIGNATURES", "ps_pairhead_api", "EXPECTED_PAIRHEAD_API", "pair-head"),
+    Family("protstruc_superpose.h", "SUPERPOSE_SIGNATURES", "ps_superpose_api", "EXPECTED_SUPERPOSE_API", "superposition"),
+    Family("protstruc_structalign.h", "STRUCTALIGN_SIGNATURES", "ps_structalign_api", "EXPECTED_STRUCTALIGN_API",
+           "structure-alignment"),
+    Family("protstruc_ensemble.h", "ENSEMBLE_SIGNATURES", "ps_ensemble_api", "EXPECTED_ENSEMBLE_API", "ensemble"),
+)
+
+EXPECTED_CONTACTS_API = 1  # PS_CONTACTS_API: the closest-atom entry points (K31 / K32)
+
 CONTACT_SIGNATURES = {
     "ps_contacts_api": (_c_int, []),
     "ps_closest_atoms_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_i16p, _c_int, _c_int, _c_int, ctypes.c_float, _c_stream]),
     "ps_closest_atoms_backward_f32": (_c_int, [_c_f32p, _c_i16p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
 }
 
-# The pair-head entry points (K33 - K36) are declared in include/protstruc_pairhead.h, again with a version of their own
-# (PS_PAIRHEAD_API): PS_ABI_VERSION, PS_CONTACTS_API and every earlier declaration stay as they were.
-EXPECTED_PAIRHEAD_API = 1  # PS_PAIRHEAD_API of include/protstruc_pairhead.h
+EXPECTED_PAIRHEAD_API = 1  # PS_PAIRHEAD_API: the pair-head entry points (K33 - K36)
 
-# name -> (restype, argtypes); mirrors include/protstruc_pairhead.h one to one.  breaks is a HOST array of floats
+# breaks is a HOST array of floats
 PAIRHEAD_SIGNATURES = {
     "ps_pairhead_api": (_c_int, []),
     "ps_pair_bins_f32": (_c_int, [_c_int] + [_c_f32p] * 6 + [_c_u8p, _c_u8p, ctypes.c_void_p, _c_int, _c_u8p, _c_f32p, _c_int,
@@ -169,9 +186,7 @@ PAIRHEAD_SIGNATURES = {
     "ps_binned_expectation_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
 }
 
-# The superposition entry points (K37 - K40) are declared in include/protstruc_superpose.h, with a version of their own
-# (PS_SUPERPOSE_API): PS_ABI_VERSION, PS_CONTACTS_API, PS_PAIRHEAD_API and every earlier declaration stay as they were.
-EXPECTED_SUPERPOSE_API = 1  # PS_SUPERPOSE_API of include/protstruc_superpose.h
+EXPECTED_SUPERPOSE_API = 1  # PS_SUPERPOSE_API: the superposition entry points (K37 - K40)
 
 
 class SuperposeObjective(ctypes.Structure):
@@ -179,8 +194,7 @@ class SuperposeObjective(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("param", ctypes.c_float)]
 
 
-# name -> (restype, argtypes); mirrors include/protstruc_superpose.h one to one.  objectives is a HOST array of
-# SuperposeObjective (a ctypes array, or its address)
+# objectives is a HOST array of SuperposeObjective (a ctypes array, or its address)
 SUPERPOSE_SIGNATURES = {
     "ps_superpose_api": (_c_int, []),
     "ps_superpose_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p] + [_c_f32p] * 4 + [_c_int, _c_int, _c_int, _c_stream]),
@@ -192,12 +206,8 @@ SUPERPOSE_SIGNATURES = {
     "ps_superpose_workspace_floats": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
 }
 
-# The structure-alignment entry points (K41 - K44) are declared in include/protstruc_structalign.h, with a version of their
-# own (PS_STRUCTALIGN_API): PS_ABI_VERSION, the other headers' versions and every earlier declaration stay as they were.
-EXPECTED_STRUCTALIGN_API = 1  # PS_STRUCTALIGN_API of include/protstruc_structalign.h
-_c_i32p = ctypes.c_void_p
+EXPECTED_STRUCTALIGN_API = 1  # PS_STRUCTALIGN_API: the structure-alignment entry points (K41 - K44)
 
-# name -> (restype, argtypes); mirrors include/protstruc_structalign.h one to one
 STRUCTALIGN_SIGNATURES = {
     "ps_structalign_api": (_c_int, []),
     "ps_structalign_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
@@ -208,11 +218,8 @@ STRUCTALIGN_SIGNATURES = {
                                         _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
 }
 
-# The ensemble entry points (K45, K46) are declared in include/protstruc_ensemble.h, with a version of their own
-# (PS_ENSEMBLE_API): PS_ABI_VERSION, the other headers' versions and every earlier declaration stay as they were.
-EXPECTED_ENSEMBLE_API = 1  # PS_ENSEMBLE_API of include/protstruc_ensemble.h
+EXPECTED_ENSEMBLE_API = 1  # PS_ENSEMBLE_API: the ensemble entry points (K45, K46)
 
-# name -> (restype, argtypes); mirrors include/protstruc_ensemble.h one to one
 ENSEMBLE_SIGNATURES = {
     "ps_ensemble_api": (_c_int, []),
     "ps_rmsd_matrix_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
@@ -240,8 +247,15 @@ def _try_build_in_tree():
         print(f"[protstruc_amd] in-tree build failed: {exc}", flush=True)
 
 
+def _bind(lib, signatures):
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = restype
+        fn.argtypes = argtypes
+
+
 def load():
-    """Load the shared library once and type every entry point."""
+    """Load the shared library once, type every entry point and check every version."""
     global _lib
     if _lib is not None:
         return _lib
@@ -269,50 +283,13 @@ def load():
     if abi != EXPECTED_ABI:
         raise HipLibraryError(f"{LIB_PATH} has ABI version {abi}, this package binds version {EXPECTED_ABI}: "
                               "rebuild with `python -m protstruc_amd.build --force`")
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = restype
-        fn.argtypes = argtypes
-    for name, (restype, argtypes) in CONTACT_SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = restype
-        fn.argtypes = argtypes
-    contacts = lib.ps_contacts_api()
-    if contacts != EXPECTED_CONTACTS_API:
-        raise HipLibraryError(f"{LIB_PATH} has contacts API version {contacts}, this package binds version "
-                              f"{EXPECTED_CONTACTS_API}: rebuild with `python -m protstruc_amd.build --force`")
-    for name, (restype, argtypes) in PAIRHEAD_SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = restype
-        fn.argtypes = argtypes
-    pairhead = lib.ps_pairhead_api()
-    if pairhead != EXPECTED_PAIRHEAD_API:
-        raise HipLibraryError(f"{LIB_PATH} has pair-head API version {pairhead}, this package binds version "
-                              f"{EXPECTED_PAIRHEAD_API}: rebuild with `python -m protstruc_amd.build --force`")
-    for name, (restype, argtypes) in SUPERPOSE_SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = restype
-        fn.argtypes = argtypes
-    superpose = lib.ps_superpose_api()
-    if superpose != EXPECTED_SUPERPOSE_API:
-        raise HipLibraryError(f"{LIB_PATH} has superposition API version {superpose}, this package binds version "
-                              f"{EXPECTED_SUPERPOSE_API}: rebuild with `python -m protstruc_amd.build --force`")
-    for name, (restype, argtypes) in STRUCTALIGN_SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = restype
-        fn.argtypes = argtypes
-    structalign = lib.ps_structalign_api()
-    if structalign != EXPECTED_STRUCTALIGN_API:
-        raise HipLibraryError(f"{LIB_PATH} has structure-alignment API version {structalign}, this package binds version "
-                              f"{EXPECTED_STRUCTALIGN_API}: rebuild with `python -m protstruc_amd.build --force`")
-    for name, (restype, argtypes) in ENSEMBLE_SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = restype
-        fn.argtypes = argtypes
-    ensemble = lib.ps_ensemble_api()
-    if ensemble != EXPECTED_ENSEMBLE_API:
-        raise HipLibraryError(f"{LIB_PATH} has ensemble API version {ensemble}, this package binds version "
-                              f"{EXPECTED_ENSEMBLE_API}: rebuild with `python -m protstruc_amd.build --force`")
+    _bind(lib, SIGNATURES)
+    for family in FAMILIES:   # the tables, the expected versions and LIB_PATH are read from the module now, not at import
+        _bind(lib, globals()[family.signatures])
+        version, expected = getattr(lib, family.version_fn)(), globals()[family.expected]
+        if version != expected:
+            raise HipLibraryError(f"{LIB_PATH} has {family.word} API version {version}, this package binds version "
+                                  f"{expected}: rebuild with `python -m protstruc_amd.build --force`")
     _lib = lib
     return lib
 

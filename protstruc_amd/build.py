@@ -29,10 +29,11 @@ def sources():
 
 
 def _deps():
+    """Everything the library is compiled from: the sources and the public headers, protstruc_hip.h and one per family
+    of ``_lib.FAMILIES`` (protstruc_rccl.h belongs to the other library)."""
+    from ._lib import FAMILIES
     return sources() + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + \
-        [os.path.join(HERE, "..", "include", name) for name in ("protstruc_hip.h", "protstruc_contacts.h", "protstruc_pairhead.h",
-                                                                 "protstruc_superpose.h", "protstruc_structalign.h",
-                                                                 "protstruc_ensemble.h")]
+        [os.path.join(HERE, "..", "include", name) for name in ["protstruc_hip.h"] + [family.header for family in FAMILIES]]
 
 
 def source_hash():

@@ -121,9 +121,10 @@ def _check_float_tensor(t, shape, name: str, like: str) -> None:
         raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
 
 
-def _check_optional(t, shape, name: str, like: str = "", like_shape=None, integer: bool = False) -> None:
+def _check_optional(t, shape, name: str, like: str = "", like_shape=None, integer: bool = False,
+                    floating: bool = False) -> None:
     """An operand that may be None: its shape, a tuple -- the message ends "to match ``like`` ``like_shape``" where those are
-    given -- and, with ``integer``, its dtype."""
+    given -- and, with ``integer`` or ``floating``, its dtype."""
     if t is None:
         return
     if tuple(t.shape) != shape:
@@ -131,6 +132,35 @@ def _check_optional(t, shape, name: str, like: str = "", like_shape=None, intege
         raise ValueError(f"{name} must have shape {shape}{match}, got {tuple(t.shape)}")
     if integer and not _is_integer_tensor(t):
         raise ValueError(f"{name} must be an integer tensor, got {t.dtype}")
+    if floating and not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+
+
+MAX_BATCH = 65535   # structures per call: they are one dimension of the grid
+
+
+def _check_batch(B: int, what: str = "structures") -> None:
+    if B > MAX_BATCH:
+        raise ValueError(f"at most {MAX_BATCH} {what} per call, got {B}")
+
+
+def _check_count(n: int, lo: int, hi: Optional[int], what: str) -> None:
+    """``lo <= n <= hi`` -- ``hi`` None: no upper limit --, or ValueError: "lo .. hi ``what``, got n", and "at most hi
+    ``what``, got n" where ``lo`` is 0.  A power of two from 2^16 on is written 2^k."""
+    if n < lo or (hi is not None and n > hi):
+        top = "any number of" if hi is None else f"2^{hi.bit_length() - 1}" if hi >= 2 ** 16 and not hi & (hi - 1) else hi
+        raise ValueError((f"{lo} .. {top}" if lo else f"at most {top}") + f" {what}, got {n}")
+
+
+def _float_dims(t, name: str, axes: str, tail: tuple = (3,)) -> tuple:
+    """The shape of the floating-point tensor ``t``, which has the axes that ``axes`` names -- "batch, points, 3" -- the last
+    of them ``tail``; ValueError otherwise."""
+    shape = tuple(t.shape)
+    if len(shape) != axes.count(",") + 1 or shape[len(shape) - len(tail):] != tail:
+        raise ValueError(f"{name} must have shape ({axes}), got {shape}")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    return shape
 
 
 def _xyz_dims(xyz, floating: bool = True) -> Tuple[int, int, int]:
@@ -144,15 +174,14 @@ def _xyz_dims(xyz, floating: bool = True) -> Tuple[int, int, int]:
     return shape[:3]
 
 
-def _points_dims(points, max_batch: int, max_points: int) -> Tuple[int, int]:
+def _points_dims(points, max_points: int) -> Tuple[int, int]:
     """(B, M) of floating-point (batch, points, 3) points within the limits of a launch -- a grid dimension per
     structure, ``max_points`` (a power of two) points in one; ValueError otherwise."""
     shape = tuple(points.shape)
     if len(shape) != 3 or shape[2] != 3:
         raise ValueError(f"points must have shape (batch, points, 3), got {shape}")
     B, M = shape[:2]
-    if B > max_batch:
-        raise ValueError(f"at most {max_batch} structures per call, got {B}")
+    _check_batch(B)
     if M > max_points:
         raise ValueError(f"at most 2^{max_points.bit_length() - 1} points per structure, got {M}")
     if not points.dtype.is_floating_point:
@@ -769,8 +798,7 @@ def check_distmat_shapes(d_cb, omega, theta, phi, mask=None, chain_breaks=None, 
 
 def check_distmat_size(B: int, L: int) -> None:
     """The size limits of the K8 / K9 launches (a grid dimension per structure, 32-bit offsets in a structure)."""
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
+    _check_batch(B)
     if 9 * L ** 2 >= 2 ** 31:
         raise ValueError(f"L = {L} is too long (9 L^2 must stay below 2^31)")
 
@@ -815,8 +843,7 @@ def check_floyd_warshall_shape(D, G: int = 1) -> Tuple[int, int]:
     else:
         raise ValueError(f"D must have shape (batch, {G}, {G}, L, L)" + (" or (batch, L, L)" if G == 1 else "") +
                          f", got {shape}")
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
+    _check_batch(B)
     if (G * L) ** 2 >= 2 ** 31:
         raise ValueError(f"{G * L} nodes are too many ((G L)^2 must stay below 2^31)")
     return B, L
@@ -895,7 +922,7 @@ def check_smacof_shapes(D, G: int = 1, n_init: Optional[int] = None, max_iter: i
     else:
         K = 4 if n_init is None else n_init
     check_lengths(lengths, B, L)
-    if K > 65535 or B * K * G * L * 3 >= 2 ** 31:
+    if K > MAX_BATCH or B * K * G * L * 3 >= 2 ** 31:
         raise ValueError(f"{B} x {K} starts of {G * L} nodes are too many for one call")
     return B, L, K
 
@@ -973,8 +1000,7 @@ def check_backbone_coords_shape(X, n_atoms: int = 3) -> Tuple[int, int]:
     shape = tuple(X.shape)
     if len(shape) != 4 or shape[1] != n_atoms or shape[3] != 3:
         raise ValueError(f"coordinates must have shape (batch, {n_atoms}, L, 3), got {shape}")
-    if shape[0] > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {shape[0]}")
+    _check_batch(shape[0])
     return shape[0], shape[2]
 
 
@@ -1071,8 +1097,7 @@ def check_fape_shapes(rot, trans, points, target_rot, target_trans, target_point
     if len(pshape) != 3 or pshape[0] != B or pshape[2] != 3:
         raise ValueError(f"points must have shape ({B}, points, 3), got {pshape}")
     M = pshape[1]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
+    _check_batch(B)
     if N > 2 ** 30 or M > 2 ** 30:
         raise ValueError(f"at most 2^30 frames and points per structure, got {N} and {M}")
     like = f"rot {shape} and points {pshape}"
@@ -1182,7 +1207,7 @@ def check_lddt_shapes(points, target_points, point_mask=None, groups=None, cutof
     """Shape rules of ``lddt`` / ``lddt_backward``, on shapes, dtypes, devices and the scalars only (no launch):
     ValueError.  ``thresholds``: 1 to 8 strictly increasing floats in (0, 64]; ``cutoff`` positive and finite; ``groups``
     an integer tensor."""
-    B, M = _points_dims(points, 65535, 2 ** 30)
+    B, M = _points_dims(points, 2 ** 30)
     like = f"points {(B, M, 3)}"
     _check_float_tensor(target_points, (B, M, 3), "target_points", like)
     _check_optional(point_mask, (B, M), "point_mask")
@@ -1264,7 +1289,7 @@ def check_clash_shapes(points, radius, point_mask=None, groups=None, link=None, 
                        grad_E=None) -> None:
     """Shape rules of ``clash`` / ``clash_backward``, on shapes, dtypes, devices and the scalars only (no launch):
     ValueError.  ``groups`` and ``link`` are integer tensors; ``tolerance`` finite; ``eps`` non-negative and finite."""
-    B, M = _points_dims(points, 65535, 2 ** 30)
+    B, M = _points_dims(points, 2 ** 30)
     like = f"points {(B, M, 3)}"
     _check_float_tensor(radius, (B, M), "radius", like)
     _check_optional(point_mask, (B, M), "point_mask")
@@ -1417,10 +1442,8 @@ def check_dssp_shapes(xyz, complete, junction, donor=None, n_slot: int = 0, ca_s
     has at most ``DSSP_MAX_RESIDUES`` residues."""
     B, N, A = _xyz_dims(xyz)
     shape = (B, N, A, 3)
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if N > 2 ** 24:
-        raise ValueError(f"at most 2^24 residues per structure, got {N}")
+    _check_batch(B)
+    _check_count(N, 0, 2 ** 24, "residues per structure")
     if acceptor_idx is None:
         if A < 4:
             raise ValueError(f"xyz needs slots for N, CA, C and O, got {A} atoms per residue")
@@ -1489,7 +1512,7 @@ def check_sasa_shapes(points, radius, point_mask=None, isolate=None, sphere=None
     """Shape rules of ``solvent_accessibility``, on shapes, dtypes, devices and the scalar only (no launch): ValueError.
     ``isolate`` is an integer tensor; ``sphere`` a float32 (S,3) table with ``1 <= S <= SASA_MAX_SPHERE_POINTS`` (None is
     not checked: the layers above build it); ``probe`` non-negative and finite."""
-    B, M = _points_dims(points, 65535, 2 ** 24)
+    B, M = _points_dims(points, 2 ** 24)
     _check_float_tensor(radius, (B, M), "radius", f"points {(B, M, 3)}")
     _check_optional(point_mask, (B, M), "point_mask")
     _check_optional(isolate, (B, M), "isolate", integer=True)
@@ -1536,7 +1559,7 @@ def check_knn_shapes(points, k, point_mask=None, queries=None, query_mask=None, 
     ``1 <= k <= KNN_MAX_K``; ``cutoff`` positive, +inf allowed; ``exclude`` / ``query_exclude`` integer tensors.  Without
     ``queries`` (the self graph) ``query_mask`` and ``query_exclude`` are not given -- they are ``point_mask`` and
     ``exclude``; with ``queries``, ``exclude`` and ``query_exclude`` come together and ``include_self`` means nothing."""
-    B, M = _points_dims(points, 65535, 2 ** 24)
+    B, M = _points_dims(points, 2 ** 24)
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KNN_MAX_K:
         raise ValueError(f"k must be an integer in 1 .. {KNN_MAX_K}, got {k!r}")
     if float(cutoff) != _INF:
@@ -1554,8 +1577,7 @@ def check_knn_shapes(points, k, point_mask=None, queries=None, query_mask=None, 
         if not queries.dtype.is_floating_point:
             raise ValueError(f"queries must be a floating-point tensor, got {queries.dtype}")
         Q = shape[1]
-        if Q > 2 ** 24:
-            raise ValueError(f"at most 2^24 queries per structure, got {Q}")
+        _check_count(Q, 0, 2 ** 24, "queries per structure")
         _check_optional(query_mask, (B, Q), "query_mask", "queries", shape)
         _check_optional(query_exclude, (B, Q), "query_exclude", "queries", shape, integer=True)
         if (exclude is None) != (query_exclude is None):
@@ -1605,23 +1627,19 @@ CLOSEST_MAX_RESIDUES = 2 ** 20  # PS_CLOSEST_MAX_RESIDUES
 
 def check_closest_atoms_shapes(xyz, atom_mask=None, cutoff=_INF, pair=None, grad_dist=None) -> None:
     """Shape rules of ``closest_atoms`` / ``closest_atoms_backward``, on shapes, dtypes, devices and the scalar only (no
-    launch): ValueError.  ``xyz`` (B,N,A,3) floating point with ``B <= 65535``, ``1 <= N <= CLOSEST_MAX_RESIDUES`` and ``1 <=
+    launch): ValueError.  ``xyz`` (B,N,A,3) floating point with ``B <= MAX_BATCH``, ``1 <= N <= CLOSEST_MAX_RESIDUES`` and ``1 <=
     A <= CLOSEST_MAX_ATOMS``; ``atom_mask`` (B,N,A); ``cutoff`` non-negative, +inf allowed; for the backward pass ``pair``
     (B,N,N) integers and ``grad_dist`` (B,N,N) floating point."""
     B, N, A = _xyz_dims(xyz)
     shape = (B, N, A, 3)
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if not 1 <= N <= CLOSEST_MAX_RESIDUES:
-        raise ValueError(f"1 .. 2^{CLOSEST_MAX_RESIDUES.bit_length() - 1} residues per structure, got {N}")
-    if not 1 <= A <= CLOSEST_MAX_ATOMS:
-        raise ValueError(f"1 .. {CLOSEST_MAX_ATOMS} atom slots per residue, got {A}")
+    _check_batch(B)
+    _check_count(N, 1, CLOSEST_MAX_RESIDUES, "residues per structure")
+    _check_count(A, 1, CLOSEST_MAX_ATOMS, "atom slots per residue")
     _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
     if float(cutoff) != _INF:
         _check_scalar(cutoff, "cutoff", "non-negative")
     _check_optional(pair, (B, N, N), "pair", "xyz", shape, integer=True)
-    if grad_dist is not None:
-        _check_float_tensor(grad_dist, (B, N, N), "grad_dist", f"xyz {shape}")
+    _check_optional(grad_dist, (B, N, N), "grad_dist", "xyz", shape, floating=True)
     _same_device(xyz, atom_mask=atom_mask, pair=pair, grad_dist=grad_dist)
 
 
@@ -1678,44 +1696,35 @@ def _check_breaks(breaks) -> np.ndarray:
     """``breaks`` as the float32 host array the launcher reads: 1 .. PAIRHEAD_MAX_BREAKS finite, non-negative, strictly
     increasing numbers; ValueError otherwise."""
     arr = np.ascontiguousarray(_host_f32(breaks, "breaks"))
-    if not 1 <= arr.size <= PAIRHEAD_MAX_BREAKS:
-        raise ValueError(f"1 .. {PAIRHEAD_MAX_BREAKS} breaks, got {arr.size}")
+    _check_count(arr.size, 1, PAIRHEAD_MAX_BREAKS, "breaks")
     if not (np.isfinite(arr).all() and (arr >= 0).all() and (np.diff(arr) > 0).all()):
         raise ValueError("breaks must be finite, non-negative and strictly increasing")
     return arr
 
 
 def _pair_batch(B: int, N: int) -> None:
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if not 1 <= N <= PAIRHEAD_MAX_RESIDUES:
-        raise ValueError(f"1 .. 2^{PAIRHEAD_MAX_RESIDUES.bit_length() - 1} residues per structure, got {N}")
+    _check_batch(B)
+    _check_count(N, 1, PAIRHEAD_MAX_RESIDUES, "residues per structure")
 
 
 def check_pair_bins_shapes(points, breaks, row_mask=None, col_mask=None, rot=None, trans=None, target_rot=None,
                            target_trans=None, target_points=None) -> None:
     """Shape rules of ``pair_bins_distance`` / ``pair_bins_aligned_error``, on shapes, dtypes, devices and the host table
-    only (no launch): ValueError.  ``points`` (B,N,3) floating point with ``B <= 65535`` and ``1 <= N <=
+    only (no launch): ValueError.  ``points`` (B,N,3) floating point with ``B <= MAX_BATCH`` and ``1 <= N <=
     PAIRHEAD_MAX_RESIDUES``; the masks (B,N); ``breaks`` 1 .. ``PAIRHEAD_MAX_BREAKS`` finite, non-negative, strictly
     increasing numbers; with ``rot`` given (the aligned error) ``rot`` and ``target_rot`` (B,N,3,3), ``trans``,
     ``target_trans`` and ``target_points`` (B,N,3), all floating point."""
-    shape = tuple(points.shape)
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"points must have shape (batch, residues, 3), got {shape}")
-    if not points.dtype.is_floating_point:
-        raise ValueError(f"points must be a floating-point tensor, got {points.dtype}")
+    shape = _float_dims(points, "points", "batch, residues, 3")
     B, N = shape[:2]
     _pair_batch(B, N)
     _check_breaks(breaks)
     _check_optional(row_mask, (B, N), "row_mask", "points", shape)
     _check_optional(col_mask, (B, N), "col_mask", "points", shape)
-    frames = {}
-    if rot is not None:
-        frames = {"rot": (rot, (B, N, 3, 3)), "trans": (trans, (B, N, 3)), "target_rot": (target_rot, (B, N, 3, 3)),
-                  "target_trans": (target_trans, (B, N, 3)), "target_points": (target_points, (B, N, 3))}
-        for name, (t, want) in frames.items():
-            _check_float_tensor(t, want, name, f"points {shape}")
-    _same_device(points, row_mask=row_mask, col_mask=col_mask, **{name: t for name, (t, _) in frames.items()})
+    frames = {} if rot is None else dict(rot=rot, trans=trans, target_rot=target_rot, target_trans=target_trans,
+                                         target_points=target_points)
+    for name, t in frames.items():
+        _check_float_tensor(t, (B, N, 3, 3) if name.endswith("rot") else (B, N, 3), name, f"points {shape}")
+    _same_device(points, row_mask=row_mask, col_mask=col_mask, **frames)
 
 
 def _pair_bins(mode, floats, row_mask, col_mask, breaks, return_value):
@@ -1763,7 +1772,7 @@ def pair_bins_aligned_error(rot: torch.Tensor, trans: torch.Tensor, points: torc
 
 def check_binned_shapes(logits, bins=None, grad_row=None, values=None) -> None:
     """Shape rules of ``binned_cross_entropy``, ``binned_cross_entropy_backward`` and ``binned_expectation``, on shapes,
-    dtypes and devices only (no launch): ValueError.  ``logits`` (B,N,N,C) floating point with ``B <= 65535``, ``1 <= N <=
+    dtypes and devices only (no launch): ValueError.  ``logits`` (B,N,N,C) floating point with ``B <= MAX_BATCH``, ``1 <= N <=
     PAIRHEAD_MAX_RESIDUES`` and ``2 <= C <= PAIRHEAD_MAX_BINS``; ``bins`` (B,N,N) integers; ``grad_row`` (B,N) floating
     point; ``values`` (B,V,C) floating point with ``1 <= V <= PAIRHEAD_MAX_TABLES``."""
     shape = tuple(logits.shape)
@@ -1773,17 +1782,14 @@ def check_binned_shapes(logits, bins=None, grad_row=None, values=None) -> None:
         raise ValueError(f"logits must be a floating-point tensor, got {logits.dtype}")
     B, N, _, C = shape
     _pair_batch(B, N)
-    if not 2 <= C <= PAIRHEAD_MAX_BINS:
-        raise ValueError(f"2 .. {PAIRHEAD_MAX_BINS} bins, got {C}")
+    _check_count(C, 2, PAIRHEAD_MAX_BINS, "bins")
     _check_optional(bins, (B, N, N), "bins", "logits", shape, integer=True)
-    if grad_row is not None:
-        _check_float_tensor(grad_row, (B, N), "grad_row", f"logits {shape}")
+    _check_optional(grad_row, (B, N), "grad_row", "logits", shape, floating=True)
     if values is not None:
         vshape = tuple(values.shape)
         if len(vshape) != 3 or vshape[0] != B or vshape[2] != C:
             raise ValueError(f"values must have shape ({B}, tables, {C}) to match logits {shape}, got {vshape}")
-        if not 1 <= vshape[1] <= PAIRHEAD_MAX_TABLES:
-            raise ValueError(f"1 .. {PAIRHEAD_MAX_TABLES} value tables, got {vshape[1]}")
+        _check_count(vshape[1], 1, PAIRHEAD_MAX_TABLES, "value tables")
         if not values.dtype.is_floating_point:
             raise ValueError(f"values must be a floating-point tensor, got {values.dtype}")
     _same_device(logits, bins=bins, grad_row=grad_row, values=values)
@@ -1854,29 +1860,21 @@ SUPERPOSE_COUNT = 1             # PS_SUPERPOSE_COUNT: the objective [d <= c], pa
 
 def check_superpose_shapes(a, b, weight=None, mask=None, grad_rmsd=None, l_norm=None, max_points=None) -> Tuple[int, int, bool]:
     """Shape rules of ``superpose``, ``superpose_backward`` and ``superpose_search``, on shapes, dtypes and devices only (no
-    launch): ValueError.  ``a`` (B,M,3) floating point with ``B <= 65535`` and ``M >= 1`` (``M <= max_points`` where given);
+    launch): ValueError.  ``a`` (B,M,3) floating point with ``B <= MAX_BATCH`` and ``M >= 1`` (``M <= max_points`` where given);
     ``b`` (B,M,3), or (1,M,3) as one target for all; ``weight`` (B,M) floating point; ``mask`` (B,M); ``grad_rmsd`` and
     ``l_norm`` (B,) floating point.  Returns (B, M, one target for all)."""
-    shape = tuple(a.shape)
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"a must have shape (batch, points, 3), got {shape}")
-    if not a.dtype.is_floating_point:
-        raise ValueError(f"a must be a floating-point tensor, got {a.dtype}")
+    shape = _float_dims(a, "a", "batch, points, 3")
     B, M = shape[:2]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if M < 1 or (max_points is not None and M > max_points):
-        raise ValueError(f"1 .. {max_points if max_points is not None else 'any number of'} points per structure, got {M}")
+    _check_batch(B)
+    _check_count(M, 1, max_points, "points per structure")
     if tuple(b.shape) != shape and tuple(b.shape) != (1, M, 3):
         raise ValueError(f"b must have shape {shape} or {(1, M, 3)} to match a, got {tuple(b.shape)}")
     if not b.dtype.is_floating_point:
         raise ValueError(f"b must be a floating-point tensor, got {b.dtype}")
-    if weight is not None:
-        _check_float_tensor(weight, (B, M), "weight", f"a {shape}")
+    _check_optional(weight, (B, M), "weight", "a", shape, floating=True)
     _check_optional(mask, (B, M), "mask", "a", shape)
-    for name, t in (("grad_rmsd", grad_rmsd), ("l_norm", l_norm)):
-        if t is not None:
-            _check_float_tensor(t, (B,), name, f"a {shape}")
+    _check_optional(grad_rmsd, (B,), "grad_rmsd", "a", shape, floating=True)
+    _check_optional(l_norm, (B,), "l_norm", "a", shape, floating=True)
     _same_device(a, b=b, weight=weight, mask=mask, grad_rmsd=grad_rmsd, l_norm=l_norm)
     return B, M, tuple(b.shape) != shape
 
@@ -1929,8 +1927,7 @@ def superpose_backward(a: torch.Tensor, b: torch.Tensor, weight: Optional[torch.
 def _check_objectives(objectives):
     """``objectives`` -- 1 .. SUPERPOSE_MAX_OBJECTIVES pairs (kind, param) -- as the host array the launcher reads"""
     pairs = [(int(kind), float(param)) for kind, param in objectives]
-    if not 1 <= len(pairs) <= SUPERPOSE_MAX_OBJECTIVES:
-        raise ValueError(f"1 .. {SUPERPOSE_MAX_OBJECTIVES} objectives, got {len(pairs)}")
+    _check_count(len(pairs), 1, SUPERPOSE_MAX_OBJECTIVES, "objectives")
     for kind, param in pairs:
         if kind not in (SUPERPOSE_TM, SUPERPOSE_COUNT):
             raise ValueError(f"an objective's kind is SUPERPOSE_TM (0) or SUPERPOSE_COUNT (1), got {kind}")
@@ -1971,31 +1968,42 @@ STRUCTALIGN_MAX_POINTS = 1024   # PS_STRUCTALIGN_MAX_POINTS of include/protstruc
 
 def check_structalign_shapes(a, b, mask_a=None, mask_b=None, d0=None) -> Tuple[int, int, int]:
     """Shape rules of ``structure_align``, on shapes, dtypes and devices only (no launch): ValueError.  ``a`` (B,Ma,3) and ``b``
-    (B,Mb,3) floating point with ``B <= 65535`` and ``1 <= Ma, Mb <= STRUCTALIGN_MAX_POINTS``; ``mask_a`` (B,Ma), ``mask_b``
+    (B,Mb,3) floating point with ``B <= MAX_BATCH`` and ``1 <= Ma, Mb <= STRUCTALIGN_MAX_POINTS``; ``mask_a`` (B,Ma), ``mask_b``
     (B,Mb); ``d0`` (B,) floating point.  Returns (B, Ma, Mb)."""
     for name, x in (("a", a), ("b", b)):
-        shape = tuple(x.shape)
-        if len(shape) != 3 or shape[2] != 3:
-            raise ValueError(f"{name} must have shape (batch, points, 3), got {shape}")
-        if not x.dtype.is_floating_point:
-            raise ValueError(f"{name} must be a floating-point tensor, got {x.dtype}")
-        if not 1 <= shape[1] <= STRUCTALIGN_MAX_POINTS:
-            raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} points per structure, got {shape[1]} in {name}")
+        M = _float_dims(x, name, "batch, points, 3")[1]
+        if not 1 <= M <= STRUCTALIGN_MAX_POINTS:   # names the operand: not _check_count's words
+            raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} points per structure, got {M} in {name}")
     B, Ma, Mb = a.shape[0], a.shape[1], b.shape[1]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
+    _check_batch(B)
     if b.shape[0] != B:
         raise ValueError(f"b must have the batch size of a, {B}, got {b.shape[0]}")
     _check_optional(mask_a, (B, Ma), "mask_a", "a", tuple(a.shape))
     _check_optional(mask_b, (B, Mb), "mask_b", "b", tuple(b.shape))
-    if d0 is not None:
-        _check_float_tensor(d0, (B,), "d0", f"a {tuple(a.shape)}")
+    _check_optional(d0, (B,), "d0", "a", tuple(a.shape), floating=True)
     _same_device(a, b=b, mask_a=mask_a, mask_b=mask_b, d0=d0)
     return B, Ma, Mb
 
 
 def _structalign_workspace(B: int, Ma: int, Mb: int, device) -> torch.Tensor:
     return torch.empty(_lib.load().ps_structalign_workspace_bytes(B, Ma, Mb), dtype=torch.uint8, device=device)
+
+
+def check_nw_align_shapes(score, gap, mask_a=None, mask_b=None) -> Tuple[int, int, int]:
+    """Shape rules of ``nw_align``, on shapes, dtypes, devices and the scalar only (no launch): ValueError.  ``score``
+    (B,Ma,Mb) floating point with ``B <= MAX_BATCH`` and ``1 <= Ma, Mb <= STRUCTALIGN_MAX_POINTS``; ``gap <= 0`` and finite;
+    ``mask_a`` (B,Ma), ``mask_b`` (B,Mb).  Returns (B, Ma, Mb)."""
+    shape = _float_dims(score, "score", "batch, rows, columns", tail=())
+    B, Ma, Mb = shape
+    _check_batch(B)
+    if not (1 <= Ma <= STRUCTALIGN_MAX_POINTS and 1 <= Mb <= STRUCTALIGN_MAX_POINTS):
+        raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} rows and columns, got {Ma} x {Mb}")
+    if not -_INF < float(gap) <= 0:
+        raise ValueError(f"gap must be <= 0 and finite, got {gap}")
+    _check_optional(mask_a, (B, Ma), "mask_a", "score", shape)
+    _check_optional(mask_b, (B, Mb), "mask_b", "score", shape)
+    _same_device(score, mask_a=mask_a, mask_b=mask_b)
+    return shape
 
 
 def nw_align(score: torch.Tensor, gap: float, mask_a: Optional[torch.Tensor] = None, mask_b: Optional[torch.Tensor] = None):
@@ -2005,22 +2013,7 @@ def nw_align(score: torch.Tensor, gap: float, mask_a: Optional[torch.Tensor] = N
     rows the slot of the columns aligned to it, or -1, and ``value`` the DP's corner value.  Scores at masked slots are never
     read.  The recurrence, its ties and the trace back are defined bit for bit in include/protstruc_structalign.h; the
     table is double.  ``Ma, Mb <= STRUCTALIGN_MAX_POINTS``."""
-    shape = tuple(score.shape)
-    if len(shape) != 3:
-        raise ValueError(f"score must have shape (batch, rows, columns), got {shape}")
-    if not score.dtype.is_floating_point:
-        raise ValueError(f"score must be a floating-point tensor, got {score.dtype}")
-    B, Ma, Mb = shape
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if not (1 <= Ma <= STRUCTALIGN_MAX_POINTS and 1 <= Mb <= STRUCTALIGN_MAX_POINTS):
-        raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} rows and columns, got {Ma} x {Mb}")
-    g = float(gap)
-    if not (g <= 0 and g > -_INF):
-        raise ValueError(f"gap must be <= 0 and finite, got {gap}")
-    _check_optional(mask_a, (B, Ma), "mask_a", "score", shape)
-    _check_optional(mask_b, (B, Mb), "mask_b", "score", shape)
-    _same_device(score, mask_a=mask_a, mask_b=mask_b)
+    B, Ma, Mb = check_nw_align_shapes(score, gap, mask_a, mask_b)
     x, ma, mb = _f32c(score, "score"), _u8c(mask_a, "mask_a"), _u8c(mask_b, "mask_b")
     dev = x.device
     with _on(dev):
@@ -2029,9 +2022,19 @@ def nw_align(score: torch.Tensor, gap: float, mask_a: Optional[torch.Tensor] = N
         value = torch.empty(B, dtype=torch.float32, device=dev)
         if B:
             workspace = _structalign_workspace(B, Ma, Mb, dev)
-            _launch("ps_nw_align_f32", _ptr(x), _ptr(ma), _ptr(mb), g, _ptr(workspace), _ptr(out), _ptr(n_aligned), _ptr(value),
+            _launch("ps_nw_align_f32", _ptr(x), _ptr(ma), _ptr(mb), float(gap), _ptr(workspace), _ptr(out), _ptr(n_aligned), _ptr(value),
                     B, Ma, Mb, _stream(x))
     return out, n_aligned, value
+
+
+def check_ca_secondary_structure_shapes(points, mask=None) -> Tuple[int, int]:
+    """Shape rules of ``ca_secondary_structure``, on shapes, dtypes and devices only (no launch): ValueError.  ``points``
+    (B,M,3) floating point with ``B <= MAX_BATCH`` and ``1 <= M <= STRUCTALIGN_MAX_POINTS``; ``mask`` (B,M).  Returns (B, M)."""
+    B, M = _points_dims(points, STRUCTALIGN_MAX_POINTS)
+    _check_count(M, 1, STRUCTALIGN_MAX_POINTS, "points per structure")
+    _check_optional(mask, (B, M), "mask", "points", tuple(points.shape))
+    _same_device(points, mask=mask)
+    return B, M
 
 
 def ca_secondary_structure(points: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -2039,11 +2042,7 @@ def ca_secondary_structure(points: torch.Tensor, mask: Optional[torch.Tensor] = 
     anything else and the two points at either end, -1 under ``mask`` (B,M; None = all) -- from the six distances among
     the points i-2 .. i+2 counted after masking.  Chain breaks are not looked at (include/protstruc_structalign.h).
     ``M <= STRUCTALIGN_MAX_POINTS``."""
-    B, M = _points_dims(points, 65535, STRUCTALIGN_MAX_POINTS)
-    if M < 1:
-        raise ValueError(f"1 .. {STRUCTALIGN_MAX_POINTS} points per structure, got {M}")
-    _check_optional(mask, (B, M), "mask", "points", tuple(points.shape))
-    _same_device(points, mask=mask)
+    B, M = check_ca_secondary_structure_shapes(points, mask)
     x, m = _f32c(points, "points"), _u8c(mask, "mask")
     dev = x.device
     with _on(dev):
@@ -2089,16 +2088,11 @@ RMSD_MATRIX_MAX_POINTS = 2 ** 31 - 17   # PS_RMSD_MATRIX_MAX_POINTS: the points 
 
 def check_rmsd_matrix_shapes(a, b=None, mask_a=None, mask_b=None) -> Tuple[int, int, int]:
     """Shape rules of ``rmsd_matrix``, on shapes, dtypes and devices only (no launch): ValueError.  ``a`` (Ba,M,3) floating
-    point with ``Ba <= 65535`` and ``1 <= M <= RMSD_MATRIX_MAX_POINTS``; ``b`` (Bb,M,3) likewise, or None -- self mode, ``a`` against itself, which takes
+    point with ``Ba <= MAX_BATCH`` and ``1 <= M <= RMSD_MATRIX_MAX_POINTS``; ``b`` (Bb,M,3) likewise, or None -- self mode, ``a`` against itself, which takes
     no ``mask_b``; ``mask_a`` (Ba,M) and ``mask_b`` (Bb,M).  Returns (Ba, Bb, M)."""
-    shape = tuple(a.shape)
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"a must have shape (batch, points, 3), got {shape}")
-    if not a.dtype.is_floating_point:
-        raise ValueError(f"a must be a floating-point tensor, got {a.dtype}")
+    shape = _float_dims(a, "a", "batch, points, 3")
     Ba, M = shape[:2]
-    if not 1 <= M <= RMSD_MATRIX_MAX_POINTS:
-        raise ValueError(f"1 .. {RMSD_MATRIX_MAX_POINTS} points per structure, got {M}")
+    _check_count(M, 1, RMSD_MATRIX_MAX_POINTS, "points per structure")
     Bb = Ba
     if b is None:
         if mask_b is not None:
@@ -2109,8 +2103,7 @@ def check_rmsd_matrix_shapes(a, b=None, mask_a=None, mask_b=None) -> Tuple[int, 
         if not b.dtype.is_floating_point:
             raise ValueError(f"b must be a floating-point tensor, got {b.dtype}")
         Bb = b.shape[0]
-    if Ba > 65535 or Bb > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {max(Ba, Bb)}")
+    _check_batch(max(Ba, Bb))
     _check_optional(mask_a, (Ba, M), "mask_a", "a", shape)
     if b is not None:
         _check_optional(mask_b, (Bb, M), "mask_b", "b", tuple(b.shape))
@@ -2141,17 +2134,15 @@ def rmsd_matrix(a: torch.Tensor, b: Optional[torch.Tensor] = None, mask_a: Optio
 
 def check_cluster_shapes(D, cutoff, valid=None) -> Tuple[int, int]:
     """Shape rules of ``cluster``, on shapes, dtypes and devices only (no launch): ValueError.  ``D`` (G,B,B) floating point
-    with ``G <= 65535`` and ``1 <= B <= CLUSTER_MAX_ITEMS``; ``cutoff`` a finite number; ``valid`` (G,B).  Returns (G, B)."""
+    with ``G <= MAX_BATCH`` and ``1 <= B <= CLUSTER_MAX_ITEMS``; ``cutoff`` a finite number; ``valid`` (G,B).  Returns (G, B)."""
     shape = tuple(D.shape)
     if len(shape) != 3 or shape[1] != shape[2]:
         raise ValueError(f"D must have shape (matrices, items, items), got {shape}")
     if not D.dtype.is_floating_point:
         raise ValueError(f"D must be a floating-point tensor, got {D.dtype}")
     G, B = shape[:2]
-    if G > 65535:
-        raise ValueError(f"at most 65535 matrices per call, got {G}")
-    if not 1 <= B <= CLUSTER_MAX_ITEMS:
-        raise ValueError(f"1 .. {CLUSTER_MAX_ITEMS} items per matrix, got {B}")
+    _check_batch(G, "matrices")
+    _check_count(B, 1, CLUSTER_MAX_ITEMS, "items per matrix")
     _check_scalar(cutoff, "cutoff", "finite")
     _check_optional(valid, (G, B), "valid", "D", shape)
     _same_device(D, valid=valid)
@@ -2225,10 +2216,8 @@ def check_edge_rbf_shapes(xyz, idx, atom_mask=None, pair_i=(), pair_j=(), center
     ``EDGE_MAX_PAIRS`` atom slots in [0, A); 1 .. ``EDGE_MAX_RBF`` ``centers``; ``sigma`` positive and finite; one of
     the two outputs wanted."""
     B, N, A = _xyz_dims(xyz)
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if N > 2 ** 24:
-        raise ValueError(f"at most 2^24 residues per structure, got {N}")
+    _check_batch(B)
+    _check_count(N, 0, 2 ** 24, "residues per structure")
     _check_neighbor_idx(idx, B, N, f"xyz {(B, N, A, 3)}")
     _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", (B, N, A, 3))
     try:
@@ -2280,15 +2269,10 @@ def edge_rbf(xyz: torch.Tensor, idx: torch.Tensor, atom_mask: Optional[torch.Ten
 
 def check_edge_frames_shapes(rot, trans, idx, frame_mask=None, want_pos=True, want_rot=True) -> None:
     """Shape rules of ``edge_frames``, on shapes, dtypes and devices only (no launch): ValueError."""
-    shape = tuple(rot.shape)
-    if len(shape) != 4 or shape[2:] != (3, 3):
-        raise ValueError(f"rot must have shape (batch, frames, 3, 3), got {shape}")
+    shape = _float_dims(rot, "rot", "batch, frames, 3, 3", tail=(3, 3))
     B, N = shape[:2]
-    if B > 65535:
-        raise ValueError(f"at most 65535 structures per call, got {B}")
-    if N > 2 ** 24:
-        raise ValueError(f"at most 2^24 frames per structure, got {N}")
-    _check_float_tensor(rot, shape, "rot", f"rot {shape}")
+    _check_batch(B)
+    _check_count(N, 0, 2 ** 24, "frames per structure")
     _check_float_tensor(trans, (B, N, 3), "trans", f"rot {shape}")
     _check_neighbor_idx(idx, B, N, f"rot {shape}")
     _check_optional(frame_mask, (B, N), "frame_mask", "rot", shape)
@@ -2374,10 +2358,8 @@ def _check_residue_type(residue_type, B: int, N: int, like: str) -> None:
 
 def _chi_dims(xyz) -> Tuple[int, int, int]:
     B, N, A = _xyz_dims(xyz)
-    if B * N > 2 ** 31:
-        raise ValueError(f"at most 2^31 residues per call, got {B * N}")
-    if not 1 <= A <= 64:
-        raise ValueError(f"1 .. 64 atom slots per residue, got {A}")
+    _check_count(B * N, 0, 2 ** 31, "residues per call")
+    _check_count(A, 1, 64, "atom slots per residue")
     return B, N, A
 
 
@@ -2409,8 +2391,7 @@ def _checked_chi(xyz, residue_type, atom_mask, chi_atoms, grad_chi, want_chi=Tru
     _check_residue_type(residue_type, B, N, f"xyz {shape}")
     _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
     atoms, _ = _chi_tables(chi_atoms, None, A, False)
-    if grad_chi is not None:
-        _check_float_tensor(grad_chi, (B, N, 4), "grad_chi", f"xyz {shape}")
+    _check_optional(grad_chi, (B, N, 4), "grad_chi", "xyz", shape, floating=True)
     if not (want_chi or want_mask):
         raise ValueError("nothing to compute: want_chi and want_mask are both False")
     _same_device(xyz, residue_type=residue_type, atom_mask=atom_mask, grad_chi=grad_chi)
@@ -2470,14 +2451,12 @@ def _checked_chi_set(xyz, chi, residue_type, atom_mask, chi_select, chi_atoms, c
     """``check_chi_set_shapes``; returns the validated host tables."""
     B, N, A = _chi_dims(xyz)
     shape = (B, N, A, 3)
-    if chi is not None:
-        _check_float_tensor(chi, (B, N, 4), "chi", f"xyz {shape}")
+    _check_optional(chi, (B, N, 4), "chi", "xyz", shape, floating=True)
     _check_residue_type(residue_type, B, N, f"xyz {shape}")
     _check_optional(atom_mask, (B, N, A), "atom_mask", "xyz", shape)
     _check_optional(chi_select, (B, N, 4), "chi_select", "xyz", shape)
     tables = _chi_tables(chi_atoms, chi_last, A, True)
-    if grad_out is not None:
-        _check_float_tensor(grad_out, shape, "grad_out", f"xyz {shape}")
+    _check_optional(grad_out, shape, "grad_out", "xyz", shape, floating=True)
     _same_device(xyz, chi=chi, residue_type=residue_type, atom_mask=atom_mask, chi_select=chi_select, grad_out=grad_out)
     return tables
 

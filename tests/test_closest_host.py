@@ -1,22 +1,20 @@
 """Closest-atom residue distances without a GPU: the float64 restatement tests/closest_ref.py against an independent brute
-force, its tie and mirror rules by hand, the C header include/protstruc_contacts.h against the binding and the library,
+force, its tie and mirror rules by hand, the entry points of include/protstruc_contacts.h,
 the argument checks of the launchers and of the shell, and the contact maps, interface residues and Fnat of a complex in
 numpy -- the values tests/test_gpu_closest.py holds StructureBatch to."""
 import ctypes
 import functools
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import closest_ref as R
+from tests.c_headers import declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "protstruc_contacts.h")
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
 
@@ -118,12 +116,7 @@ def test_lattice_case_has_the_boundary_on_both_sides():
     assert np.array_equal(np.isfinite(dist), free <= 5.0) and ((pair >= 0) == np.isfinite(dist)).all()
 
 
-# ---- the header ------------------------------------------------------------------------------------------------------------------
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ps_[a-z0-9_]+)\s*\(", text)))
-
-
+# ---- the header (tests/test_api_families.py holds it to the binding and the library) ------------------------------------------
 @pytest.fixture(scope="module")
 def lib():
     from protstruc_amd import _lib, build
@@ -131,30 +124,10 @@ def lib():
     return _lib.load()
 
 
-def test_header_is_c99():
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", HEADER], check=True)
-
-
-def test_header_binding_and_library_agree(lib):
-    from protstruc_amd import _lib, build
-    assert declared_symbols() == sorted(_lib.CONTACT_SIGNATURES)
-    assert declared_symbols() == ["ps_closest_atoms_backward_f32", "ps_closest_atoms_f32", "ps_contacts_api"]
-    raw = ctypes.CDLL(build.LIB_PATH)
-    for name in declared_symbols():
-        assert hasattr(raw, name), f"{name} is declared in include/protstruc_contacts.h but not exported"
-    api = int(re.search(r"#define PS_CONTACTS_API (\d+)", open(HEADER).read()).group(1))
-    assert lib.ps_contacts_api() == api == _lib.EXPECTED_CONTACTS_API
-    assert not set(_lib.CONTACT_SIGNATURES) & set(_lib.SIGNATURES)
-    deps = {os.path.basename(d) for d in build._deps()}
-    assert {"protstruc_contacts.h", "protstruc_hip.h", "closest_atoms.hip"} <= deps
-
-
-def test_a_library_with_another_contacts_api_is_refused(lib, monkeypatch):
-    from protstruc_amd import _lib
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "EXPECTED_CONTACTS_API", _lib.EXPECTED_CONTACTS_API + 1)
-    with pytest.raises(_lib.HipLibraryError, match="contacts API"):
-        _lib.load()
+def test_the_entry_points_of_the_header():
+    from protstruc_amd import build
+    assert declared_symbols("protstruc_contacts.h") == ["ps_closest_atoms_backward_f32", "ps_closest_atoms_f32", "ps_contacts_api"]
+    assert "closest_atoms.hip" in {os.path.basename(d) for d in build._deps()}
 
 
 def test_arguments_are_checked_before_any_launch(lib):

@@ -6,26 +6,20 @@ by arithmetic alone."""
 import ctypes
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import ensemble_ref as R
+from tests.c_headers import declared_symbols, header_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "protstruc_ensemble.h")
+HEADER = "protstruc_ensemble.h"
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 LAUNCHERS = ["ps_cluster_f32", "ps_rmsd_matrix_f32"]
 HOST_FUNCTIONS = ["ps_cluster_workspace_bytes", "ps_ensemble_api"]
 PDB_NAME = "1REX"      # tests/test_gpu_ensemble.py uses the same file
-
-
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ps_[a-z0-9_]+)\s*\(", text)))
 
 
 @pytest.fixture(scope="module")
@@ -42,36 +36,13 @@ def pdb_ensemble():
     return R.ensemble_of(xyz[0].numpy(), mask[0].numpy().astype(bool))
 
 
-# ---- the header ------------------------------------------------------------------------------------------------------------------
-def test_header_is_c99():
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", HEADER], check=True)
-
-
-def test_header_binding_and_library_agree(lib):
-    from protstruc_amd import _lib, build, ops
-    assert declared_symbols() == sorted(_lib.ENSEMBLE_SIGNATURES) == sorted(LAUNCHERS + HOST_FUNCTIONS)
-    raw = ctypes.CDLL(build.LIB_PATH)
-    for name in declared_symbols():
-        assert hasattr(raw, name), f"{name} is declared in include/protstruc_ensemble.h but not exported"
-    text = open(HEADER).read()
-    api = int(re.search(r"#define PS_ENSEMBLE_API (\d+)", text).group(1))
-    assert lib.ps_ensemble_api() == api == _lib.EXPECTED_ENSEMBLE_API
-    for other in (_lib.SIGNATURES, _lib.CONTACT_SIGNATURES, _lib.PAIRHEAD_SIGNATURES, _lib.SUPERPOSE_SIGNATURES, _lib.STRUCTALIGN_SIGNATURES):
-        assert not set(_lib.ENSEMBLE_SIGNATURES) & set(other)
-    assert _lib.EXPECTED_ABI == 16 and lib.ps_abi_version() == 16
-    deps = {os.path.basename(d) for d in build._deps()}
-    assert {"protstruc_ensemble.h", "ensemble.hip", "kabsch_solve.hpp"} <= deps
-    assert int(re.search(r"#define PS_CLUSTER_MAX_ITEMS (\d+)", text).group(1)) == ops.CLUSTER_MAX_ITEMS == 4096
-    assert int(re.search(r"#define PS_RMSD_MATRIX_MAX_POINTS (\d+)", text).group(1)) == ops.RMSD_MATRIX_MAX_POINTS == 2 ** 31 - 1 - 16
+# ---- the header (tests/test_api_families.py holds it to the binding and the library) ------------------------------------------
+def test_the_entry_points_and_the_caveat_of_the_header():
+    from protstruc_amd import build
+    assert declared_symbols(HEADER) == sorted(LAUNCHERS + HOST_FUNCTIONS)
+    assert {"ensemble.hip", "kabsch_solve.hpp"} <= {os.path.basename(d) for d in build._deps()}
+    text = header_text(HEADER)
     assert "NOT 0" in text and "ps_superpose_f32" in text, "the header states that identical members do not give an RMSD of 0"
-
-
-def test_a_library_with_another_ensemble_api_is_refused(lib, monkeypatch):
-    from protstruc_amd import _lib
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "EXPECTED_ENSEMBLE_API", _lib.EXPECTED_ENSEMBLE_API + 1)
-    with pytest.raises(_lib.HipLibraryError, match="ensemble API"):
-        _lib.load()
 
 
 # ---- argument checks -------------------------------------------------------------------------------------------------------------

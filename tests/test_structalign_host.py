@@ -6,24 +6,17 @@ import ctypes
 import itertools
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import structalign_ref as A
+from tests.c_headers import declared_symbols, macros
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "protstruc_structalign.h")
+HEADER = "protstruc_structalign.h"
 LAUNCHERS = ["ps_ca_secondary_structure_f32", "ps_nw_align_f32", "ps_structure_align_f32"]
 HOST_FUNCTIONS = ["ps_structalign_api", "ps_structalign_workspace_bytes"]
-
-
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ps_[a-z0-9_]+)\s*\(", text)))
 
 
 @pytest.fixture(scope="module")
@@ -33,37 +26,13 @@ def lib():
     return _lib.load()
 
 
-# ---- the header ------------------------------------------------------------------------------------------------------------------
-def test_header_is_c99():
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", HEADER], check=True)
-
-
-def test_header_binding_and_library_agree(lib):
-    from protstruc_amd import _lib, build, ops
-    assert declared_symbols() == sorted(_lib.STRUCTALIGN_SIGNATURES) == sorted(LAUNCHERS + HOST_FUNCTIONS)
-    raw = ctypes.CDLL(build.LIB_PATH)
-    for name in declared_symbols():
-        assert hasattr(raw, name), f"{name} is declared in include/protstruc_structalign.h but not exported"
-    exported = subprocess.run(["nm", "-D", "--defined-only", build.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert sorted(set(re.findall(r"\b(ps_(?:structalign|nw_align|ca_secondary|structure_align)\w*)", exported))) == declared_symbols()
-    text = open(HEADER).read()
-    api = int(re.search(r"#define PS_STRUCTALIGN_API (\d+)", text).group(1))
-    assert lib.ps_structalign_api() == api == _lib.EXPECTED_STRUCTALIGN_API
-    for other in (_lib.SIGNATURES, _lib.CONTACT_SIGNATURES, _lib.PAIRHEAD_SIGNATURES, _lib.SUPERPOSE_SIGNATURES):
-        assert not set(_lib.STRUCTALIGN_SIGNATURES) & set(other)
-    assert _lib.EXPECTED_ABI == 16 and lib.ps_abi_version() == 16 and lib.ps_superpose_api() == 1
-    deps = {os.path.basename(d) for d in build._deps()}
-    assert {"protstruc_structalign.h", "protstruc_superpose.h", "struct_align.hip", "superpose.hip", "superpose_chain.hpp"} <= deps
-    for macro, value in (("MAX_POINTS", ops.STRUCTALIGN_MAX_POINTS), ("MAX_POINTS", A.MAX_POINTS), ("MAX_ITERATIONS", A.MAX_ITERATIONS)):
-        assert int(re.search(rf"#define PS_STRUCTALIGN_{macro} (\d+)", text).group(1)) == value, macro
-
-
-def test_a_library_with_another_structalign_api_is_refused(lib, monkeypatch):
-    from protstruc_amd import _lib
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "EXPECTED_STRUCTALIGN_API", _lib.EXPECTED_STRUCTALIGN_API + 1)
-    with pytest.raises(_lib.HipLibraryError, match="structure-alignment API"):
-        _lib.load()
+# ---- the header (tests/test_api_families.py holds it to the binding and the library) ------------------------------------------
+def test_the_entry_points_and_constants_of_the_header(lib):
+    from protstruc_amd import build
+    assert declared_symbols(HEADER) == sorted(LAUNCHERS + HOST_FUNCTIONS)
+    assert lib.ps_superpose_api() == 1, "the alignment is built on this version of the superposition search"
+    assert {"protstruc_superpose.h", "struct_align.hip", "superpose.hip", "superpose_chain.hpp"} <= {os.path.basename(d) for d in build._deps()}
+    assert macros(HEADER)["PS_STRUCTALIGN_MAX_POINTS"] == A.MAX_POINTS and macros(HEADER)["PS_STRUCTALIGN_MAX_ITERATIONS"] == A.MAX_ITERATIONS
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,6 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,18 +13,14 @@ import torch
 
 from tests import align_ref
 from tests import superpose_ref as R
+from tests.c_headers import declared_symbols, header_text, macros
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "protstruc_superpose.h")
+HEADER = "protstruc_superpose.h"
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 LAUNCHERS = ["ps_superpose_backward_f32", "ps_superpose_f32", "ps_superpose_search_f32"]
 HOST_FUNCTIONS = ["ps_superpose_api", "ps_superpose_seed", "ps_superpose_seed_count", "ps_superpose_workspace_floats"]
 PDB_CASES = (("1REX", 11), ("1a3r_HL", 12))     # file, seed of the perturbed model: tests/test_gpu_superpose.py uses the same
-
-
-def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ps_[a-z0-9_]+)\s*\(", text)))
 
 
 @pytest.fixture(scope="module")
@@ -42,42 +37,18 @@ def pdb_case(name, seed):
     return R.structure_case(xyz[0].numpy(), mask[0].numpy(), seed)
 
 
-# ---- the header ------------------------------------------------------------------------------------------------------------------
-def test_header_is_c99():
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", HEADER], check=True)
-
-
-def test_header_binding_and_library_agree(lib):
-    from protstruc_amd import _lib, build, ops
-    assert declared_symbols() == sorted(_lib.SUPERPOSE_SIGNATURES) == sorted(LAUNCHERS + HOST_FUNCTIONS)
-    raw = ctypes.CDLL(build.LIB_PATH)
-    for name in declared_symbols():
-        assert hasattr(raw, name), f"{name} is declared in include/protstruc_superpose.h but not exported"
-    text = open(HEADER).read()
-    api = int(re.search(r"#define PS_SUPERPOSE_API (\d+)", text).group(1))
-    assert lib.ps_superpose_api() == api == _lib.EXPECTED_SUPERPOSE_API
-    for other in (_lib.SIGNATURES, _lib.CONTACT_SIGNATURES, _lib.PAIRHEAD_SIGNATURES):
-        assert not set(_lib.SUPERPOSE_SIGNATURES) & set(other)
-    assert _lib.EXPECTED_ABI == 16 and lib.ps_abi_version() == 16
-    deps = {os.path.basename(d) for d in build._deps()}
-    assert {"protstruc_superpose.h", "protstruc_pairhead.h", "protstruc_contacts.h", "protstruc_hip.h", "superpose.hip",
-            "kabsch_solve.hpp"} <= deps
-    for macro, value in (("MAX_POINTS", ops.SUPERPOSE_MAX_POINTS), ("MAX_OBJECTIVES", ops.SUPERPOSE_MAX_OBJECTIVES),
-                         ("TM", ops.SUPERPOSE_TM), ("COUNT", ops.SUPERPOSE_COUNT), ("MAX_POINTS", R.MAX_POINTS),
-                         ("MAX_SEEDS", R.MAX_SEEDS), ("MAX_ITERATIONS", R.MAX_ITERATIONS), ("MAX_DOUBLINGS", R.MAX_DOUBLINGS),
-                         ("MAX_OBJECTIVES", R.MAX_OBJECTIVES), ("TM", R.TM), ("COUNT", R.COUNT)):
-        assert int(re.search(rf"#define PS_SUPERPOSE_{macro} (\d+)", text).group(1)) == value, macro
-    body = re.search(r"typedef struct ps_superpose_objective \{(.*?)\} ps_superpose_objective;", text, flags=re.S).group(1)
+# ---- the header (tests/test_api_families.py holds it to the binding and the library) ------------------------------------------
+def test_the_entry_points_and_constants_of_the_header():
+    from protstruc_amd import _lib, build
+    assert declared_symbols(HEADER) == sorted(LAUNCHERS + HOST_FUNCTIONS)
+    assert {"superpose.hip", "kabsch_solve.hpp"} <= {os.path.basename(d) for d in build._deps()}
+    defined = macros(HEADER)
+    for macro, value in (("MAX_POINTS", R.MAX_POINTS), ("MAX_SEEDS", R.MAX_SEEDS), ("MAX_ITERATIONS", R.MAX_ITERATIONS),
+                         ("MAX_DOUBLINGS", R.MAX_DOUBLINGS), ("MAX_OBJECTIVES", R.MAX_OBJECTIVES), ("TM", R.TM), ("COUNT", R.COUNT)):
+        assert defined["PS_SUPERPOSE_" + macro] == value, macro
+    body = re.search(r"typedef struct ps_superpose_objective \{(.*?)\} ps_superpose_objective;", header_text(HEADER), flags=re.S).group(1)
     assert re.findall(r"(int|float)\s+(\w+)\s*;", body) == [("int", "kind"), ("float", "param")]
     assert [f for f, _ in _lib.SuperposeObjective._fields_] == ["kind", "param"] and ctypes.sizeof(_lib.SuperposeObjective) == 8
-
-
-def test_a_library_with_another_superpose_api_is_refused(lib, monkeypatch):
-    from protstruc_amd import _lib
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "EXPECTED_SUPERPOSE_API", _lib.EXPECTED_SUPERPOSE_API + 1)
-    with pytest.raises(_lib.HipLibraryError, match="superposition API"):
-        _lib.load()
 
 
 # ---- the seed table --------------------------------------------------------------------------------------------------------------

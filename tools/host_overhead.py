@@ -32,6 +32,11 @@ junction[:, -1] = False
 sphere = geometry.sphere_points(32).cuda()
 g_rot, g_trans = torch.ones_like(rot), torch.ones_like(trans)
 
+# operands of the graph, contact, pair-head, superposition and ensemble wrappers (K24 - K46), the same 64 residues / points
+logits = torch.randn(B, N, N, 64, generator=g).cuda()
+bins = torch.randint(0, 64, (B, N, N), generator=g).to(torch.uint8).cuda()
+D = torch.cdist(pts, pts)
+
 
 def per_call(fn, n=2000):
     for _ in range(50):
@@ -61,6 +66,12 @@ rows = [
     ("ops.peptide_bond", lambda: ops.peptide_bond(xg, junction)),
     ("ops.backbone_hbonds", lambda: ops.backbone_hbonds(xg, pmask, junction)),
     ("ops.solvent_accessibility", lambda: ops.solvent_accessibility(pts, radius, pmask, sphere=sphere)),
+    ("ops.nearest_neighbors (k = 16)", lambda: ops.nearest_neighbors(pts, 16, pmask)),
+    ("ops.closest_atoms", lambda: ops.closest_atoms(xg, mg)),
+    ("ops.binned_cross_entropy (64 bins)", lambda: ops.binned_cross_entropy(logits, bins)),
+    ("ops.superpose", lambda: ops.superpose(pts, tgt, None, pmask)),
+    ("ops.rmsd_matrix", lambda: ops.rmsd_matrix(pts, tgt, pmask, pmask)),
+    ("ops.cluster", lambda: ops.cluster(D, 8.0, pmask)),
     ("torch.empty + torch.add (reference point)", lambda: torch.add(xg, 1.0)),
     # config 5's eager step: diffuse_xyz + backbone_orientations
     ("config-5 eager step (diffuse_xyz + backbone_orientations)", lambda: (sb.diffuse_xyz(beta), sb.backbone_orientations())),

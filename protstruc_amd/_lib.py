@@ -9,149 +9,44 @@ import os
 import threading
 from typing import NamedTuple
 
+from ._headers import HipLibraryError, prototypes, struct_fields  # noqa: F401 -- HipLibraryError is this module's error too
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PROTSTRUC_AMD_LIB selects another build of the library: the same-process A/B of two builds (tools/k1_ab_libs.py)
 LIB_PATH = os.environ.get("PROTSTRUC_AMD_LIB") or os.path.join(_HERE, "lib", "libprotstruc_hip.so")
 EXPECTED_ABI = 16  # PS_ABI_VERSION of include/protstruc_hip.h; bumped together with any signature change
 
 
+# the structs that cross the boundary: their layouts are the typedefs of the headers, read from them
 class K1Config(ctypes.Structure):
-    """``ps_k1_config`` of include/protstruc_hip.h, field for field."""
-    _fields_ = [(name, ctypes.c_int) for name in (
-        "struct_size", "exact_sqrt", "variant", "flat", "rows_per_block", "lds_pad_kb", "flat_cpw",
-        "flat_lds_pad_kb", "jt", "xcd_remap", "store_nt", "flat_fl_log2", "rowphase", "experiment")]
+    _fields_ = struct_fields("protstruc_hip.h", "ps_k1_config")
 
 
 class K1Plan(ctypes.Structure):
-    """``ps_k1_plan`` of include/protstruc_hip.h, field for field."""
-    _fields_ = [("struct_size", ctypes.c_int), ("n_launches", ctypes.c_int), ("family", ctypes.c_char * 48),
-                ("kernel", ctypes.c_char * 96), ("n_workgroups", ctypes.c_uint), ("lds_bytes", ctypes.c_uint),
-                ("threads_per_workgroup", ctypes.c_int), ("n_workgroups_2", ctypes.c_uint), ("lds_bytes_2", ctypes.c_uint)]
+    _fields_ = struct_fields("protstruc_hip.h", "ps_k1_plan")
 
 
 class K3Plan(ctypes.Structure):
-    """``ps_k3_plan`` of include/protstruc_hip.h, field for field."""
-    _fields_ = [("struct_size", ctypes.c_int), ("n_launches", ctypes.c_int), ("family", ctypes.c_char * 32),
-                ("kernel", ctypes.c_char * 96)] + \
-               [(name, ctypes.c_int) for name in ("columns_per_lane", "vector_stores", "skips_dead_groups", "mask_store_mode",
-                                                  "write_through", "faithful", "rows_per_task", "workgroups_per_cu",
-                                                  "structures_per_segment")] + \
-               [("n_workgroups", ctypes.c_uint), ("threads_per_workgroup", ctypes.c_int), ("lds_bytes", ctypes.c_uint),
-                ("n_tasks", ctypes.c_uint), ("tasks_per_workgroup", ctypes.c_uint)]
+    _fields_ = struct_fields("protstruc_hip.h", "ps_k3_plan")
 
 
-_c_f32p = ctypes.c_void_p
-_c_u8p = ctypes.c_void_p
-_c_int = ctypes.c_int
-_c_stream = ctypes.c_void_p
+class SuperposeObjective(ctypes.Structure):
+    _fields_ = struct_fields("protstruc_superpose.h", "ps_superpose_objective")
 
-# name -> (restype, argtypes); mirrors include/protstruc_hip.h one to one
-SIGNATURES = {
-    "ps_abi_version": (_c_int, []),
-    "ps_error_string": (ctypes.c_char_p, [_c_int]),
-    "ps_has_experiments": (_c_int, []),
-    "ps_k1_config_default": (None, [ctypes.POINTER(K1Config)]),
-    "ps_pairwise_distance_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                          _c_int, _c_int, _c_stream]),
-    "ps_pairwise_distance_cfg_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                              _c_int, _c_int, ctypes.POINTER(K1Config), _c_stream]),
-    "ps_k1_plan_f32": (_c_int, [_c_int] * 10 + [ctypes.POINTER(K1Config), ctypes.POINTER(K1Plan)]),
-    "ps_backbone_dihedrals_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_u8p, _c_u8p, _c_int, _c_int,
-                                           _c_int, _c_stream]),
-    "ps_pairwise_angles_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_int),
-                                        ctypes.POINTER(_c_int), _c_int, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_k3_plan_f32": (_c_int, [_c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)] + [_c_int] * 7 +
-                       [ctypes.POINTER(K3Plan)]),
-    "ps_featuriser_plan_f32": (_c_int, [_c_int] * 8 + [ctypes.POINTER(K3Plan)]),
-    "ps_frames_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                               _c_stream]),
-    "ps_frames_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                        _c_int, _c_int, _c_stream]),
-    "ps_pointwise_f32": (_c_int, [_c_int, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_longlong, _c_stream]),
-    "ps_diffuse_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, ctypes.c_void_p, _c_f32p, _c_stream]),
-    "ps_diffuse_frames_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_f32p, _c_f32p, _c_f32p,
-                                       _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_diffusion_trajectory_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_f32p,
-                                             _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_inter_residue_geometry_f32": (_c_int, [_c_f32p, _c_u8p] + [_c_f32p] * 6 + [_c_u8p] * 3 + [_c_int, _c_int, _c_int,
-                                                                                                  _c_int, _c_int, _c_stream]),
-    "ps_inter_residue_geometry_backward_f32": (_c_int, [_c_f32p, _c_u8p] + [_c_f32p] * 6 + [_c_f32p, _c_int, _c_int, _c_int,
-                                                                                              _c_stream]),
-    "ps_fape_f32": (_c_int, [_c_f32p] * 6 + [_c_u8p, _c_u8p, _c_f32p, ctypes.c_float, ctypes.c_float, _c_f32p, _c_f32p,
-                             _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_fape_backward_f32": (_c_int, [_c_f32p] * 6 + [_c_u8p, _c_u8p, _c_f32p, ctypes.c_float, ctypes.c_float, _c_f32p,
-                                      _c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    # thresholds is a HOST array of floats (a ctypes array, or its address)
-    "ps_lddt_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, _c_int, _c_int,
-                             ctypes.c_float, _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
-    "ps_lddt_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, _c_int,
-                                      ctypes.c_float, _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
-    "ps_clash_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
-                              _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
-    "ps_clash_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                       ctypes.c_float, _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
-    # constants is a HOST array of 12 floats (a ctypes array, or its address)
-    "ps_peptide_bond_f32": (_c_int, [_c_f32p, _c_u8p, _c_u8p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_f32p, _c_int,
-                                     _c_int, _c_int, _c_stream]),
-    "ps_peptide_bond_backward_f32": (_c_int, [_c_f32p, _c_u8p, _c_u8p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_f32p,
-                                              _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_backbone_hbonds_f32": (_c_int, [_c_f32p, _c_u8p, _c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, ctypes.c_void_p,
-                                        _c_f32p, ctypes.c_void_p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_dssp_assign": (_c_int, [_c_f32p, _c_u8p, _c_u8p, ctypes.c_void_p, _c_int, ctypes.c_void_p, _c_int, _c_int, _c_int,
-                                _c_stream]),
-    "ps_solvent_accessibility_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, _c_f32p, ctypes.c_float,
-                                              ctypes.c_void_p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_nearest_neighbors_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int,
-                                          ctypes.c_float, _c_int, ctypes.c_void_p, _c_f32p, ctypes.c_void_p, _c_int, _c_int,
-                                          _c_int, _c_stream]),
-    "ps_edge_rbf_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), _c_int,
-                                 ctypes.POINTER(ctypes.c_float), _c_int, ctypes.c_float, _c_f32p, _c_f32p, _c_int, _c_int,
-                                 _c_int, _c_int, _c_stream]),
-    "ps_edge_frames_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, ctypes.c_void_p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int,
-                                    _c_stream]),
-    # chi_atoms (T,4,4) and chi_last (T,4) are HOST arrays of ints (ctypes arrays, or their addresses)
-    "ps_chi_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_u8p, _c_int, _c_int,
-                            _c_int, _c_stream]),
-    "ps_chi_backward_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p, _c_f32p, _c_int,
-                                     _c_int, _c_int, _c_stream]),
-    "ps_chi_set_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_int, _c_f32p,
-                                _c_u8p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_chi_set_backward_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_int,
-                                         _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_rigid_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_center_of_mass_f32": (_c_int, [_c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_frames_to_backbone_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_backbone_from_dihedrals_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int,
-                                                _c_int, _c_int, _c_stream]),
-    "ps_backbone_from_dihedrals_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_f32p, _c_int,
-                                                         _c_int, _c_int, _c_int, _c_stream]),
-    "ps_backbone_distmat_init_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_u8p, _c_u8p, ctypes.c_void_p, _c_f32p,
-                                              _c_int, _c_int, _c_stream]),
-    "ps_floyd_warshall_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
-    "ps_floyd_warshall_f32": (_c_int, [_c_f32p, _c_int, _c_int, _c_int, ctypes.c_void_p, ctypes.c_longlong, _c_stream]),
-    "ps_backbone_distmat_finish_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, _c_int, _c_int, _c_stream]),
-    "ps_smacof_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int, _c_int]),
-    "ps_smacof_f32": (_c_int, [_c_f32p, _c_int, _c_int, _c_int, ctypes.c_void_p, _c_f32p, _c_int, _c_int, ctypes.c_double,
-                               _c_f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, _c_stream]),
-    "ps_mds_backbone_finish_f32": (_c_int, [_c_f32p, ctypes.c_void_p, _c_int, _c_int, _c_int, _c_int, _c_f32p, _c_stream]),
-    "ps_kabsch_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_min_dist_to_points_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_standardize_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_standardize_variant_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_affine_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_stream]),
-}
+
+# name -> (restype, argtypes) of every entry point include/protstruc_hip.h declares; a pointer of any kind is a c_void_p
+SIGNATURES = prototypes("protstruc_hip.h")
 
 # ---- the side headers: one family of entry points each ------------------------------------------------------------------
 # A family is declared in a header of its own with a version of its own (``PS_<FAMILY>_API``, returned by
-# ``ps_<family>_api()``), so that adding it changes neither PS_ABI_VERSION nor any earlier declaration.  Here it is a
-# signature table, an expected version and one line of FAMILIES; ``load()`` and ``build._deps()`` take the rest from there.
-_c_i16p = ctypes.c_void_p
-_c_i32p = ctypes.c_void_p
+# ``ps_<family>_api()``), so that adding it changes neither PS_ABI_VERSION nor any earlier declaration.  Here it is its
+# header, one line of FAMILIES and an expected version; the table is read from the header, and ``load()`` and
+# ``build._deps()`` take the rest from FAMILIES.
 
 
 class Family(NamedTuple):
     header: str        # file name under include/
-    signatures: str    # module attribute: name -> (restype, argtypes), mirrors the header one to one
+    signatures: str    # module attribute: name -> (restype, argtypes), what the header declares
     version_fn: str    # the entry point that returns the library's version of the header
     expected: str      # module attribute: the version this package binds
     word: str          # what ``load()`` calls the family when it refuses a library
@@ -167,71 +62,14 @@ FAMILIES = (   # in load order
 )
 
 EXPECTED_CONTACTS_API = 1  # PS_CONTACTS_API: the closest-atom entry points (K31 / K32)
-
-CONTACT_SIGNATURES = {
-    "ps_contacts_api": (_c_int, []),
-    "ps_closest_atoms_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_i16p, _c_int, _c_int, _c_int, ctypes.c_float, _c_stream]),
-    "ps_closest_atoms_backward_f32": (_c_int, [_c_f32p, _c_i16p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-}
-
 EXPECTED_PAIRHEAD_API = 1  # PS_PAIRHEAD_API: the pair-head entry points (K33 - K36)
-
-# breaks is a HOST array of floats
-PAIRHEAD_SIGNATURES = {
-    "ps_pairhead_api": (_c_int, []),
-    "ps_pair_bins_f32": (_c_int, [_c_int] + [_c_f32p] * 6 + [_c_u8p, _c_u8p, ctypes.c_void_p, _c_int, _c_u8p, _c_f32p, _c_int,
-                                  _c_int, _c_stream]),
-    "ps_binned_cross_entropy_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, ctypes.c_void_p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_binned_cross_entropy_backward_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_binned_expectation_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_int, _c_int, _c_int, _c_int, _c_stream]),
-}
-
 EXPECTED_SUPERPOSE_API = 1  # PS_SUPERPOSE_API: the superposition entry points (K37 - K40)
-
-
-class SuperposeObjective(ctypes.Structure):
-    """``ps_superpose_objective`` of include/protstruc_superpose.h, field for field."""
-    _fields_ = [("kind", ctypes.c_int), ("param", ctypes.c_float)]
-
-
-# objectives is a HOST array of SuperposeObjective (a ctypes array, or its address)
-SUPERPOSE_SIGNATURES = {
-    "ps_superpose_api": (_c_int, []),
-    "ps_superpose_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p] + [_c_f32p] * 4 + [_c_int, _c_int, _c_int, _c_stream]),
-    "ps_superpose_backward_f32": (_c_int, [_c_f32p, _c_f32p, _c_f32p, _c_u8p] + [_c_f32p] * 7 + [_c_int, _c_int, _c_int, _c_stream]),
-    "ps_superpose_search_f32": (_c_int, [_c_f32p, _c_f32p, _c_u8p, _c_f32p, ctypes.c_void_p, _c_int] + [_c_f32p] * 4 +
-                                [_c_int, _c_int, _c_stream]),
-    "ps_superpose_seed_count": (_c_int, [_c_int]),
-    "ps_superpose_seed": (_c_int, [_c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
-    "ps_superpose_workspace_floats": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
-}
-
 EXPECTED_STRUCTALIGN_API = 1  # PS_STRUCTALIGN_API: the structure-alignment entry points (K41 - K44)
-
-STRUCTALIGN_SIGNATURES = {
-    "ps_structalign_api": (_c_int, []),
-    "ps_structalign_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
-    "ps_nw_align_f32": (_c_int, [_c_f32p, _c_u8p, _c_u8p, ctypes.c_float, ctypes.c_void_p, _c_i32p, _c_i32p, _c_f32p, _c_int, _c_int,
-                                 _c_int, _c_stream]),
-    "ps_ca_secondary_structure_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_void_p, _c_int, _c_int, _c_stream]),
-    "ps_structure_align_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_f32p, _c_int, ctypes.c_void_p, _c_i32p, _c_i32p,
-                                        _c_f32p, _c_f32p, _c_f32p, _c_i32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
-}
-
 EXPECTED_ENSEMBLE_API = 1  # PS_ENSEMBLE_API: the ensemble entry points (K45, K46)
-
-ENSEMBLE_SIGNATURES = {
-    "ps_ensemble_api": (_c_int, []),
-    "ps_rmsd_matrix_f32": (_c_int, [_c_f32p, _c_u8p, _c_f32p, _c_u8p, _c_f32p, _c_i32p, _c_int, _c_int, _c_int, _c_stream]),
-    "ps_cluster_f32": (_c_int, [_c_f32p, _c_u8p, ctypes.c_float, ctypes.c_void_p] + [_c_i32p] * 4 + [_c_int, _c_int, _c_stream]),
-    "ps_cluster_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
-}
+# CONTACT_SIGNATURES ... ENSEMBLE_SIGNATURES, the attributes FAMILIES names: what each family's header declares
+globals().update({family.signatures: prototypes(family.header) for family in FAMILIES})
 
 _lib = None
-
-
-class HipLibraryError(RuntimeError):
-    pass
 
 
 def _try_build_in_tree():
@@ -276,7 +114,7 @@ def load():
             "run `python -m protstruc_amd.build --force` where hipcc is available.")
     lib = ctypes.CDLL(LIB_PATH)
     try:
-        lib.ps_abi_version.restype = _c_int
+        lib.ps_abi_version.restype = ctypes.c_int
         abi = lib.ps_abi_version()
     except AttributeError as exc:
         raise HipLibraryError(f"{LIB_PATH} does not export ps_abi_version: not a protstruc_amd library") from exc

@@ -7,7 +7,7 @@ process holds one copy.
 import ctypes
 import os
 
-from ._lib import HipLibraryError
+from ._headers import HipLibraryError, prototypes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libprotstruc_rccl.so")
@@ -15,19 +15,7 @@ EXPECTED_ABI = 2
 COMM_ID_BYTES = 128
 GATHER_FORCE_BROADCAST = 1   # PS_GATHER_FORCE_BROADCAST
 
-_vp, _int = ctypes.c_void_p, ctypes.c_int
-SIGNATURES = {
-    "ps_rccl_abi_version": (_int, []),
-    "ps_rccl_version": (_int, [ctypes.POINTER(_int)]),
-    "ps_comm_unique_id": (_int, [_vp]),
-    "ps_comm_create": (_int, [ctypes.POINTER(_vp), _vp, _int, _int]),
-    "ps_comm_destroy": (_int, [_vp]),
-    "ps_comm_rank": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "ps_shard_rows": (_int, [_int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "ps_allgather_rows": (_int, [_vp, _vp, _int, _int, ctypes.c_longlong, _vp]),
-    "ps_allgather_rows_ex": (_int, [_vp, _vp, _int, _int, ctypes.c_longlong, _int, _vp]),
-    "ps_comm_error_string": (ctypes.c_char_p, [_int]),
-}
+SIGNATURES = prototypes("protstruc_rccl.h")   # name -> (restype, argtypes); a pointer of any kind is a c_void_p
 
 _lib = None
 
@@ -65,6 +53,6 @@ def check(code, what):
 
 
 def rccl_version():
-    v = _int(0)
+    v = ctypes.c_int(0)
     check(load().ps_rccl_version(ctypes.byref(v)), "ps_rccl_version")
     return v.value

@@ -11,6 +11,7 @@ import hashlib
 import os
 import subprocess
 import sys
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -36,96 +37,91 @@ def _deps():
         [os.path.join(HERE, "..", "include", name) for name in ["protstruc_hip.h"] + [family.header for family in FAMILIES]]
 
 
+class _Target(NamedTuple):
+    """One native product with the digest of what it was built from recorded beside it (``out`` + ".srchash"): built only
+    when that digest is not the tree's, aside under a pid-suffixed name and renamed into place, so that concurrent builders
+    (one per rank) cannot corrupt it."""
+    out: str          # the file that is built
+    seed: bytes       # what the digest starts from
+    inputs: list      # the files the digest covers, in this order, each by base name and contents
+    command: object   # path to write -> the compiler's command line
+
+    def digest(self):
+        h = hashlib.sha256(self.seed)
+        for d in self.inputs:
+            h.update(os.path.basename(d).encode())
+            with open(d, "rb") as f:
+                h.update(f.read())
+        return h.hexdigest()
+
+    def is_stale(self):
+        """True when ``out`` is missing or was built from other inputs than the ones in the tree now.  Compared by
+        content digest, not by mtime: a snapshot copied to another machine keeps its contents but not necessarily its
+        timestamps."""
+        if not os.path.exists(self.out):
+            return True
+        try:
+            with open(self.out + ".srchash") as f:
+                return f.read().strip() != self.digest()
+        except OSError:
+            return True
+
+    def build(self, force, verbose):
+        if not force and not self.is_stale():
+            return self.out
+        os.makedirs(os.path.dirname(self.out), exist_ok=True)
+        tmp = f"{self.out}.{os.getpid()}.tmp"
+        cmd = self.command(tmp)
+        if verbose:
+            print("[protstruc_amd.build]", " ".join(cmd), flush=True)
+        try:
+            digest = self.digest()
+            subprocess.run(cmd, check=True)
+            os.replace(tmp, self.out)
+            with open(self.out + ".srchash", "w") as f:
+                f.write(digest + "\n")
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        return self.out
+
+
+def _library(out=None):
+    return _Target(out or LIB_PATH, " ".join(FLAGS).encode(), _deps(), lambda tmp: [HIPCC] + FLAGS + ["-o", tmp] + sources())
+
+
 def source_hash():
     """Digest of everything the library is compiled from (file names, contents, flags)."""
-    h = hashlib.sha256(" ".join(FLAGS).encode())
-    for d in _deps():
-        h.update(os.path.basename(d).encode())
-        with open(d, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()
+    return _library().digest()
 
 
 def is_stale(path=None):
-    """True when ``path`` is missing or was built from other sources than the ones in the tree now.  Compared by
-    content digest (recorded next to the library at build time), not by mtime: a snapshot copied to another
-    machine keeps its contents but not necessarily its timestamps."""
-    path = path or LIB_PATH
-    if not os.path.exists(path):
-        return True
-    try:
-        with open(path + ".srchash") as f:
-            recorded = f.read().strip()
-    except OSError:
-        return True
-    return recorded != source_hash()
+    """Whether the library at ``path`` (default: the tree's) has to be built: see ``_Target.is_stale``."""
+    return _library(path).is_stale()
 
 
 def build(force=False, verbose=True):
-    out = LIB_PATH
-    if not force and not is_stale(out):
-        return out
-    os.makedirs(LIB_DIR, exist_ok=True)
-    tmp = f"{out}.{os.getpid()}.tmp"  # build aside and rename: concurrent builders (one per rank) cannot corrupt the .so
-    cmd = [HIPCC] + FLAGS + ["-o", tmp] + sources()
-    if verbose:
-        print("[protstruc_amd.build]", " ".join(cmd), flush=True)
-    try:
-        digest = source_hash()
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, out)
-        with open(out + ".srchash", "w") as f:
-            f.write(digest + "\n")
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return out
+    return _library().build(force, verbose)
 
 
 def rccl_sources():
     return sorted(glob.glob(os.path.join(RCCL_SRC_DIR, "*.cpp")))
 
 
-def _rccl_hash():
-    h = hashlib.sha256(b"rccl-lib-v1")
-    for d in rccl_sources() + [os.path.join(HERE, "..", "include", "protstruc_rccl.h")]:
-        h.update(os.path.basename(d).encode())
-        with open(d, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()
+def _rccl_library():
+    return _Target(RCCL_LIB_PATH, b"rccl-lib-v1", rccl_sources() + [os.path.join(HERE, "..", "include", "protstruc_rccl.h")],
+                   lambda tmp: [HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp] + rccl_sources() +
+                   ["-L" + ROCM_LIB, "-lrccl", "-Wl,-rpath," + ROCM_LIB])
 
 
 def rccl_is_stale():
-    if not os.path.exists(RCCL_LIB_PATH):
-        return True
-    try:
-        with open(RCCL_LIB_PATH + ".srchash") as f:
-            return f.read().strip() != _rccl_hash()
-    except OSError:
-        return True
+    return _rccl_library().is_stale()
 
 
 def build_rccl(force=False, verbose=True):
     """libprotstruc_rccl.so: host-only C++ over RCCL (ps_allgather_rows, include/protstruc_rccl.h).  Linked against
     librccl.so.1 by SONAME: inside a PyTorch process that is the RCCL PyTorch already loaded, so one copy serves both."""
-    if not force and not rccl_is_stale():
-        return RCCL_LIB_PATH
-    os.makedirs(LIB_DIR, exist_ok=True)
-    tmp = f"{RCCL_LIB_PATH}.{os.getpid()}.tmp"
-    cmd = [HIPCC, "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp] + rccl_sources() + \
-        ["-L" + ROCM_LIB, "-lrccl", "-Wl,-rpath," + ROCM_LIB]
-    if verbose:
-        print("[protstruc_amd.build]", " ".join(cmd), flush=True)
-    try:
-        digest = _rccl_hash()
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, RCCL_LIB_PATH)
-        with open(RCCL_LIB_PATH + ".srchash", "w") as f:
-            f.write(digest + "\n")
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return RCCL_LIB_PATH
+    return _rccl_library().build(force, verbose)
 
 
 EXAMPLE_SRC = os.path.join(HERE, "..", "examples", "c_abi_demo.c")
@@ -151,46 +147,20 @@ PROBE_SRC = os.path.join(HERE, "..", "tests", "native", "arith_probe.hip")
 PROBE_LIB_PATH = os.path.join(HERE, "..", "build", "libps_arith_probe.so")
 
 
-def _probe_hash():
-    h = hashlib.sha256(" ".join(FLAGS).encode())
-    for d in [PROBE_SRC] + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))):
-        h.update(os.path.basename(d).encode())
-        with open(d, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()
+def _arith_probe():
+    return _Target(PROBE_LIB_PATH, " ".join(FLAGS).encode(), [PROBE_SRC] + sorted(glob.glob(os.path.join(CSRC, "*.hpp"))),
+                   lambda tmp: [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp, PROBE_SRC])
 
 
 def arith_probe_is_stale():
-    if not os.path.exists(PROBE_LIB_PATH):
-        return True
-    try:
-        with open(PROBE_LIB_PATH + ".srchash") as f:
-            return f.read().strip() != _probe_hash()
-    except OSError:
-        return True
+    return _arith_probe().is_stale()
 
 
 def build_arith_probe(force=False, verbose=True):
     """build/libps_arith_probe.so: tests/native/arith_probe.hip, the test-only entry point that evaluates one arithmetic
     primitive of csrc/*.hpp elementwise (tests/test_gpu_arith.py).  Compiled with exactly FLAGS -- the primitives must be
     probed in the arithmetic the library runs them in -- and kept out of libprotstruc_hip.so: the product ABI has no probe."""
-    if not force and not arith_probe_is_stale():
-        return PROBE_LIB_PATH
-    os.makedirs(os.path.dirname(PROBE_LIB_PATH), exist_ok=True)
-    tmp = f"{PROBE_LIB_PATH}.{os.getpid()}.tmp"
-    cmd = [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp, PROBE_SRC]
-    if verbose:
-        print("[protstruc_amd.build]", " ".join(cmd), flush=True)
-    try:
-        digest = _probe_hash()
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, PROBE_LIB_PATH)
-        with open(PROBE_LIB_PATH + ".srchash", "w") as f:
-            f.write(digest + "\n")
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return PROBE_LIB_PATH
+    return _arith_probe().build(force, verbose)
 
 
 if __name__ == "__main__":

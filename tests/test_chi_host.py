@@ -5,16 +5,15 @@ differentiable ``xyz``, what ``StructureBatch`` hands to the geometry layer, and
 No GPU needed."""
 import ctypes
 import inspect
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import chi_ref as R
-from tests.test_capi_symbols import HEADER, declared_symbols
+from tests.c_headers import parameters
 
-SYMBOLS = {"ps_chi_f32": 11, "ps_chi_backward_f32": 11, "ps_chi_set_f32": 14, "ps_chi_set_backward_f32": 13}
+SYMBOLS = ("ps_chi_f32", "ps_chi_backward_f32", "ps_chi_set_f32", "ps_chi_set_backward_f32")
 PDB_COUNTS = {"1REX": (105, 77, 30, 19), "4EOT": (146, 88, 44, 22), "5cjx_HL": (342, 197, 50, 17),
               "15c8_HL": (190, 121, 41, 16), "6dc4": (370, 227, 78, 37), "4uuj": (443, 274, 86, 41)}
 ONE_ANGLE = np.array([[[0, 1, 2, 3], [-1] * 4, [-1] * 4, [-1] * 4]])          # one residue type whose chi1 is slots 0 1 2 3
@@ -193,26 +192,12 @@ def test_analytic_gradients_match_autograd(pdb_cases, which):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------
-def test_symbols_are_declared_exported_and_bound():
-    from protstruc_amd import _lib, build, ops
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for symbol, n_args in SYMBOLS.items():
-        assert symbol in declared_symbols()
-        assert hasattr(lib, symbol)
-        restype, argtypes = _lib.SIGNATURES[symbol]
-        assert restype is ctypes.c_int
-        decl = re.search(r"\b" + symbol + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-        assert len(argtypes) == len(decl.split(",")) == n_args               # one ctypes entry per declared parameter
-    names = lambda symbol: [p.split()[-1].lstrip("*") for p in re.search(                      # noqa: E731
-        r"\b" + symbol + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1).split(",")]
+def test_parameter_names_of_the_entry_points():
+    """(declared, exported, bound, and the parameter counts: tests/test_capi_symbols.py)"""
+    names = lambda symbol: [p.split()[-1].lstrip("*") for p in parameters("protstruc_hip.h", symbol)]       # noqa: E731
     assert names("ps_chi_f32") == ["xyz", "atom_mask", "residue_type", "chi_atoms", "T", "chi", "chi_mask", "B", "N", "A", "stream"]
     assert names("ps_chi_set_f32") == ["xyz", "atom_mask", "residue_type", "chi_atoms", "chi_last", "T", "chi", "chi_select",
                                        "relative", "out", "B", "N", "A", "stream"]
-    assert ops.CHI_MAX_TYPES == int(re.search(r"#define PS_CHI_MAX_TYPES (\d+)", header).group(1)) == 32
-    # new symbols change no signature: the ABI number stays
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) == 16
-    assert _lib.EXPECTED_ABI == 16 and lib.ps_abi_version() == 16
 
 
 def ints(values):

@@ -4,7 +4,6 @@ SHEET records of four PDB files, the C ABI's surface, the argument validation of
 import ctypes
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,9 +11,7 @@ import torch
 
 from tests import dssp_ref as R
 from tests.conftest import GOLDEN_DIR
-from tests.test_capi_symbols import HEADER, declared_symbols
 
-SYMBOLS = ("ps_backbone_hbonds_f32", "ps_dssp_assign")
 PDB_FILES = ("1REX", "4EOT", "1ad0_DC", "5cjx_HL")
 
 
@@ -144,20 +141,9 @@ def test_the_records_of_1rex_are_found(pdb_labels):
     assert [k for k in sheet if labels[k] != "E"] == []
 
 
-def test_symbols_are_declared_exported_and_bound():
-    from protstruc_amd import _lib, build, geometry, ops
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in SYMBOLS:
-        assert name in declared_symbols()
-        assert hasattr(lib, name)
-        restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is ctypes.c_int
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-        assert len(argtypes) == len(decl.split(",")), name          # one ctypes entry per declared parameter
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) >= 14
-    assert _lib.EXPECTED_ABI >= 14
-    assert ops.DSSP_MAX_RESIDUES == int(re.search(r"#define PS_DSSP_MAX_RESIDUES (\d+)", header).group(1))
+def test_codes_are_the_yardsticks():
+    """(declared, exported, bound: tests/test_capi_symbols.py)"""
+    from protstruc_amd import geometry
     assert geometry.DSSP_CODES == R.CODES == "-HBEGITS"
 
 

@@ -6,7 +6,6 @@ import ctypes
 import inspect
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,9 +13,6 @@ import torch
 
 from tests import edge_ref as E
 from tests.conftest import GOLDEN_DIR
-from tests.test_capi_symbols import HEADER, declared_symbols
-
-RBF, FRAMES = "ps_edge_rbf_f32", "ps_edge_frames_f32"
 
 
 def f32(*rows):
@@ -113,25 +109,6 @@ def test_residue_case():
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------
-def test_symbols_are_declared_exported_and_bound():
-    from protstruc_amd import _lib, build, ops
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for symbol, n_args in ((RBF, 16), (FRAMES, 10)):
-        assert symbol in declared_symbols()
-        assert hasattr(lib, symbol)
-        restype, argtypes = _lib.SIGNATURES[symbol]
-        assert restype is ctypes.c_int
-        decl = re.search(r"\b" + symbol + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-        assert len(argtypes) == len(decl.split(",")) == n_args               # one ctypes entry per declared parameter
-    assert _lib.SIGNATURES[RBF][1][8] is ctypes.c_float                      # sigma travels by value
-    assert ops.EDGE_MAX_PAIRS == int(re.search(r"#define PS_EDGE_MAX_PAIRS (\d+)", header).group(1)) == 64
-    assert ops.EDGE_MAX_RBF == int(re.search(r"#define PS_EDGE_MAX_RBF (\d+)", header).group(1)) == 64
-    # new symbols change no signature: the ABI number stays
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) == 16
-    assert _lib.EXPECTED_ABI == 16 and lib.ps_abi_version() == 16
-
-
 def test_rbf_entry_refuses_bad_arguments_before_any_launch():
     """hipErrorInvalidValue (1) without touching a device; B = 0 and N = 0 launch nothing.  The pair tables and the
     centres are host arrays and are read in every call."""

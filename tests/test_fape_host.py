@@ -1,7 +1,6 @@
 """Host-side checks of the frame-aligned point error: the yardstick itself (tests/fape_ref.py), the C ABI's surface and the
 argument validation of ``ops.fape`` / ``ops.fape_backward`` / ``ops.frames_backward``.  No GPU needed."""
 import ctypes
-import re
 
 import pytest
 import torch
@@ -9,9 +8,6 @@ import torch
 from oracle import protstruc_oracle as O
 from tests import fape_ref as R
 from tests.conftest import load_golden
-from tests.test_capi_symbols import HEADER, declared_symbols
-
-SYMBOLS = ("ps_fape_f32", "ps_fape_backward_f32", "ps_frames_backward_f32")
 
 
 @pytest.mark.parametrize("regime", ["clamped", "unclamped", "frames_from_xyz"])
@@ -92,23 +88,6 @@ def test_case_generator_covers_both_sides_of_the_clamp():
     below = (d < case.clamp.double()[:, None, None]).double().mean()
     assert 0.3 < float(below) < 0.6
     assert ((case.clamp > 8) & (case.clamp < 12)).all()
-
-
-def test_symbols_are_declared_exported_and_bound():
-    from protstruc_amd import _lib, build
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in SYMBOLS:
-        assert name in declared_symbols()
-        assert hasattr(lib, name)
-        restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is ctypes.c_int
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-        assert len(argtypes) == len(decl.split(",")), name          # one ctypes entry per declared parameter
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) >= 11
-    assert _lib.EXPECTED_ABI >= 11
-    from protstruc_amd import ops
-    assert ops.FAPE_FRAME_TILE == int(re.search(r"#define PS_FAPE_FRAME_TILE (\d+)", header).group(1))
 
 
 def test_c_entries_refuse_bad_arguments_before_any_launch():

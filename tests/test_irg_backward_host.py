@@ -1,7 +1,6 @@
 """Host-side checks of the featuriser's backward pass: the yardstick itself (tests/irg_grad_ref.py), the C ABI's surface and
 the argument validation of ``ops.inter_residue_geometry_backward``.  No GPU needed."""
 import ctypes
-import re
 
 import pytest
 import torch
@@ -9,7 +8,6 @@ import torch
 from oracle import protstruc_oracle as O
 from tests import irg_grad_ref as R
 from tests.conftest import load_golden
-from tests.test_capi_symbols import HEADER, declared_symbols
 
 SYMBOL = "ps_inter_residue_geometry_backward_f32"
 
@@ -84,18 +82,6 @@ def test_float32_autograd_of_the_restatement_is_close_to_float64():
     E = R.worst_error(got, want)
     print(f"E_f32 = {E:.3e}")
     assert E < 1e-3
-
-
-def test_symbol_is_declared_exported_and_bound():
-    from protstruc_amd import _lib, build
-    assert SYMBOL in declared_symbols()
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    assert hasattr(lib, SYMBOL)
-    restype, argtypes = _lib.SIGNATURES[SYMBOL]
-    assert restype is ctypes.c_int and len(argtypes) == 13
-    header = open(HEADER).read()
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) >= 9
-    assert _lib.EXPECTED_ABI >= 9
 
 
 def test_c_entry_refuses_bad_arguments_before_any_launch():

@@ -6,7 +6,6 @@ import ctypes
 import inspect
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,9 +13,7 @@ import torch
 
 from tests import knn_ref as R
 from tests.conftest import GOLDEN_DIR
-from tests.test_capi_symbols import HEADER, declared_symbols
 
-SYMBOL = "ps_nearest_neighbors_f32"
 INF = np.float32(np.inf)
 
 
@@ -103,22 +100,6 @@ def test_chain_case():
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------
-def test_symbol_is_declared_exported_and_bound():
-    from protstruc_amd import _lib, build, ops
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert SYMBOL in declared_symbols()
-    assert hasattr(lib, SYMBOL)
-    restype, argtypes = _lib.SIGNATURES[SYMBOL]
-    assert restype is ctypes.c_int
-    decl = re.search(r"\b" + SYMBOL + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-    assert len(argtypes) == len(decl.split(",")) == 16                   # one ctypes entry per declared parameter
-    assert argtypes[7] is ctypes.c_float                                 # cutoff travels by value
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) == 16
-    assert _lib.EXPECTED_ABI == 16 and lib.ps_abi_version() == 16
-    assert ops.KNN_MAX_K == int(re.search(r"#define PS_KNN_MAX_K (\d+)", header).group(1)) == 64
-
-
 def test_c_entry_refuses_bad_arguments_before_any_launch():
     """hipErrorInvalidValue (1) without touching a device; B = 0 and Q = 0 launch nothing."""
     from protstruc_amd import _lib

@@ -2,15 +2,11 @@
 ``ops.lddt`` / ``ops.lddt_backward`` and the signatures of the layers above.  No GPU needed."""
 import ctypes
 import inspect
-import re
 
 import pytest
 import torch
 
 from tests import lddt_ref as R
-from tests.test_capi_symbols import HEADER, declared_symbols
-
-SYMBOLS = ("ps_lddt_f32", "ps_lddt_backward_f32")
 
 
 def test_yardstick_on_a_hand_computed_example():
@@ -64,23 +60,6 @@ def test_case_generator_and_brackets():
     assert (S[-1] == 0).all() and (n[-1] == 0).all()
     for name, kw in R.accuracy_cases().items():
         assert kw["B"] == 3, name
-
-
-def test_symbols_are_declared_exported_and_bound():
-    from protstruc_amd import _lib, build, ops
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name in SYMBOLS:
-        assert name in declared_symbols()
-        assert hasattr(lib, name)
-        restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is ctypes.c_int
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-        assert len(argtypes) == len(decl.split(",")), name          # one ctypes entry per declared parameter
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) >= 12
-    assert _lib.EXPECTED_ABI >= 12
-    assert ops.LDDT_MAX_THRESHOLDS == int(re.search(r"#define PS_LDDT_MAX_THRESHOLDS (\d+)", header).group(1))
-    assert ops.LDDT_MAX_THRESHOLD == float(re.search(r"#define PS_LDDT_MAX_THRESHOLD ([\d.]+)f", header).group(1))
 
 
 def test_c_entries_refuse_bad_arguments_before_any_launch():

@@ -2,7 +2,6 @@
 the kernel evaluates, the C ABI's surface and the argument validation of ``ops.backbone_from_dihedrals_backward``.  No GPU
 needed."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -10,7 +9,6 @@ import torch
 
 from tests import nerf_grad_ref as R
 from tests import nerf_ref
-from tests.test_capi_symbols import HEADER, declared_symbols
 
 SYMBOL = "ps_backbone_from_dihedrals_backward_f32"
 # every option of the GPU test's accuracy cases, at the two lengths where the float64 walk costs a second
@@ -105,18 +103,6 @@ def test_accuracy_cases_cover_what_they_must():
         end = np.flatnonzero(np.diff(chain[b]))[0]
         assert end in gone                                  # the last residue of the first chain
         assert gone[3] == gone[2] + 1                       # two adjacent
-
-
-def test_symbol_is_declared_exported_and_bound():
-    from protstruc_amd import _lib, build
-    assert SYMBOL in declared_symbols()
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    assert hasattr(lib, SYMBOL)
-    restype, argtypes = _lib.SIGNATURES[SYMBOL]
-    assert restype is ctypes.c_int and len(argtypes) == 12
-    header = open(HEADER).read()
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) >= 10
-    assert _lib.EXPECTED_ABI >= 10
 
 
 def test_c_entry_refuses_bad_arguments_before_any_launch():

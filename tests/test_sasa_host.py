@@ -6,7 +6,6 @@ import ctypes
 import inspect
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,9 +13,7 @@ import torch
 
 from tests import sasa_ref as R
 from tests.conftest import GOLDEN_DIR
-from tests.test_capi_symbols import HEADER, declared_symbols
 
-SYMBOL = "ps_solvent_accessibility_f32"
 MAX_ACCESSIBILITY = dict(A=129, R=274, N=195, D=193, C=167, E=223, Q=225, G=104, H=224, I=197,
                          L=201, K=236, M=224, F=240, P=159, S=155, T=172, W=285, Y=263, V=174)
 
@@ -127,23 +124,6 @@ def test_lysozyme_through_the_reader(monkeypatch):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------
-def test_symbol_is_declared_exported_and_bound():
-    from protstruc_amd import _lib, build, ops
-    lib = ctypes.CDLL(build.build(force=False, verbose=False))
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert SYMBOL in declared_symbols()
-    assert hasattr(lib, SYMBOL)
-    restype, argtypes = _lib.SIGNATURES[SYMBOL]
-    assert restype is ctypes.c_int
-    decl = re.search(r"\b" + SYMBOL + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
-    assert len(argtypes) == len(decl.split(",")) == 12                   # one ctypes entry per declared parameter
-    assert argtypes[5] is ctypes.c_float                                 # probe travels by value
-    assert int(re.search(r"#define PS_ABI_VERSION (\d+)", header).group(1)) >= 15
-    assert _lib.EXPECTED_ABI >= 15
-    assert ops.SASA_MAX_SPHERE_POINTS == int(re.search(r"#define PS_SASA_MAX_SPHERE_POINTS (\d+)", header).group(1)) == 256
-    assert int(re.search(r"#define PS_SASA_POINT_TILE (\d+)", header).group(1)) == 64
-
-
 def test_c_entry_refuses_bad_arguments_before_any_launch():
     """hipErrorInvalidValue (1) without touching a device; B = 0 and M = 0 launch nothing."""
     from protstruc_amd import _lib

@@ -54,6 +54,7 @@ def test_the_entry_points_and_constants_of_the_header():
 # ---- the seed table --------------------------------------------------------------------------------------------------------------
 def test_seed_table_of_the_library_is_the_restatement(lib):
     start, length = ctypes.c_int(), ctypes.c_int()
+    at, ln = ctypes.byref(start), ctypes.byref(length)      # every pointer parameter is bound as c_void_p: by reference, spelled out
     most = 0
     for n in range(R.MAX_POINTS + 1):
         want = R.seed_table(n)
@@ -63,8 +64,8 @@ def test_seed_table_of_the_library_is_the_restatement(lib):
             assert want[0] == (0, n) and want[-1][0] + want[-1][1] == n, f"n = {n}: the first fragment is everything, the last ends at n"
             assert all(0 <= s and s + L <= n and L >= min(n, 4) for s, L in want) and len(set(want)) == len(want), n
         for s, frag in enumerate(want):
-            assert lib.ps_superpose_seed(n, s, start, length) == 0 and (start.value, length.value) == frag, (n, s)
-        assert lib.ps_superpose_seed(n, len(want), start, length) == 1 and lib.ps_superpose_seed(n, -1, start, length) == 1, n
+            assert lib.ps_superpose_seed(n, s, at, ln) == 0 and (start.value, length.value) == frag, (n, s)
+        assert lib.ps_superpose_seed(n, len(want), at, ln) == 1 and lib.ps_superpose_seed(n, -1, at, ln) == 1, n
         assert lib.ps_superpose_workspace_floats(3, max(n, 1), 2) == 3 * 2 * 16 * most or n == 0, n
     assert lib.ps_superpose_seed_count(-1) == 0 and lib.ps_superpose_seed_count(R.MAX_POINTS + 1) == 0
     assert R.seed_table(5) == [(0, 5), (0, 4), (1, 4)] and R.seed_table(3) == [(0, 3)] and R.seed_table(0) == []

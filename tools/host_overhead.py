@@ -36,6 +36,8 @@ g_rot, g_trans = torch.ones_like(rot), torch.ones_like(trans)
 logits = torch.randn(B, N, N, 64, generator=g).cuda()
 bins = torch.randint(0, 64, (B, N, N), generator=g).to(torch.uint8).cuda()
 D = torch.cdist(pts, pts)
+nbr = ops.nearest_neighbors(pts, 16, pmask)[0]
+centers = [2.0 + 1.25 * c for c in range(16)]
 
 
 def per_call(fn, n=2000):
@@ -67,6 +69,7 @@ rows = [
     ("ops.backbone_hbonds", lambda: ops.backbone_hbonds(xg, pmask, junction)),
     ("ops.solvent_accessibility", lambda: ops.solvent_accessibility(pts, radius, pmask, sphere=sphere)),
     ("ops.nearest_neighbors (k = 16)", lambda: ops.nearest_neighbors(pts, 16, pmask)),
+    ("ops.edge_rbf (k = 16, 2 pairs, 16 centres)", lambda: ops.edge_rbf(xg, nbr, mg, pair_i=[1, 0], pair_j=[1, 3], centers=centers, sigma=1.25)),
     ("ops.closest_atoms", lambda: ops.closest_atoms(xg, mg)),
     ("ops.binned_cross_entropy (64 bins)", lambda: ops.binned_cross_entropy(logits, bins)),
     ("ops.superpose", lambda: ops.superpose(pts, tgt, None, pmask)),

@@ -15,7 +15,8 @@ hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward
 ``backbone_hbonds`` and ``dssp`` are the DSSP hydrogen bonds and secondary-structure labels (``ops.backbone_hbonds`` /
 ``ops.dssp_assign``); ``solvent_accessibility`` is Shrake and Rupley's surface area (``ops.solvent_accessibility``);
 ``nearest_neighbors`` is the k-nearest-neighbour graph (``ops.nearest_neighbors``) and ``gather_neighbors`` the gather
-that turns its indices into edge features; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
+that turns its indices into edge features; ``radius_graph`` is every neighbour within a cutoff as CSR lists
+(``ops.radius_graph``) and ``radius_graph_edges`` their (batch, row, col) triples; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
 features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``); ``side_chain_torsions``
 measures chi1 .. chi4, differentiably in the coordinates, and ``set_side_chain_torsions`` turns the side chains to given
 angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards); ``superposition_rmsd`` is the
@@ -620,6 +621,71 @@ def gather_neighbors(values, idx, fill=0):
     at = idx.clamp(min=0).long().reshape(B, Q * k, *([1] * (values.ndim - 2))).expand(B, Q * k, *values.shape[2:])
     out = torch.gather(values, 1, at).reshape(B, Q, k, *values.shape[2:])
     return torch.where(real.reshape(B, Q, k, *([1] * (values.ndim - 2))), out, torch.full_like(out, fill))
+
+
+class RadiusGraph(NamedTuple):
+    """Every neighbour of every query within a cutoff (``radius_graph``), in CSR form: row ``r = b * Q + q`` is
+    ``col[row_ptr[r]:row_ptr[r + 1]]``."""
+    row_ptr: torch.Tensor   # (B*Q+1,) int64: the exclusive prefix sum of count; row_ptr[-1] is the number of edges E
+    col: torch.Tensor       # (E,) int32: the neighbours' indices into the M axis of their own structure, ascending in a row
+    dist: torch.Tensor      # (E,) fp32: the distances
+    count: torch.Tensor     # (B,Q) int32: the number of neighbours of each query
+
+
+def radius_graph(points, cutoff, point_mask=None, *, queries=None, query_mask=None, exclude=None, query_exclude=None,
+                 include_self=False, max_edges=None) -> RadiusGraph:
+    """Every one of the ``points`` (B,M,3) within ``cutoff`` of every query: ``RadiusGraph(row_ptr, col, dist, count)``, lists
+    of any length in CSR form.  The arguments are those of ``nearest_neighbors`` -- ``queries`` (B,Q,3) or, None, the points
+    themselves (a point is not its own neighbour unless ``include_self``); masks; the integer keys ``exclude`` /
+    ``query_exclude`` that skip a candidate with the query's key -- and so is the predicate: distances compared in double
+    on the float32 coordinates, ``<=`` at the cutoff, so the result is defined bit for bit and, in the self graph without
+    keys, symmetric.  There is no ``k`` and no cap.  The rows are the B*Q queries in (b, q) order; within a row ``col`` is
+    ascending.  ``cutoff`` is positive and finite.  HIP kernels (``ops.radius_graph``): blocks of 64 consecutive points
+    whose bounding box is further than the cutoff from the box of 64 consecutive queries are never looked at, which is
+    what chain-ordered input gives; shuffled input gives the same answer, slower.  No (B,Q,M) tensor is built.
+
+    With ``max_edges=None`` the number of edges is read from the device once (not capturable by ``torch.cuda.graph``);
+    with ``max_edges=n`` nothing is read: ``col`` and ``dist`` have n entries, edges from position n on are not written
+    while ``row_ptr`` and ``count`` stay exact -- test ``row_ptr[-1] <= n`` --, and entries past ``row_ptr[-1]`` are -1 /
+    +inf.  numpy in -> numpy out; tensors come back on the device of ``points``, CPU tensors included.
+
+    Unlike ``torch_cluster.radius_graph``: no ``max_num_neighbors`` (nothing is ever cut silently); ``col`` indexes each
+    structure's own M axis and comes with ``row_ptr``, not as a flat ``edge_index`` over a concatenated batch
+    (``radius_graph_edges`` gives the triples); rows are ascending in j; a pair exactly at the cutoff IS an edge.
+
+    Not differentiable -- the list is discrete -- and the outputs carry no graph; ``radius_graph_edges`` is the route to
+    distances that are differentiable with respect to the coordinates."""
+    given = [(name, t) for name, t in (("points", points), ("point_mask", point_mask), ("queries", queries),
+                                       ("query_mask", query_mask), ("exclude", exclude), ("query_exclude", query_exclude))
+             if t is not None]
+    for name, t in given:
+        if not isinstance(t, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{name} must be a tensor or an ndarray")
+    home = points.device if isinstance(points, torch.Tensor) else None
+    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
+    args = dict(zip((name for name, _ in given), prepped))
+    out = ops.radius_graph(args.pop("points"), cutoff, args.pop("point_mask", None), include_self=include_self,
+                           max_edges=max_edges, **args)
+    return RadiusGraph(*(_finish(t if home is None else t.to(home), ft) for t in out))
+
+
+def radius_graph_edges(graph):
+    """``(batch, row, col)``, each (E,) int64, one entry per edge of a ``RadiusGraph`` of tensors: the structure, the query
+    and the neighbour -- the form ``index_add`` / scatter layers take.  Plain torch (``repeat_interleave`` over
+    ``count``), on the graph's device.  It is also the differentiable route to the distances, which the list is not::
+
+        g = radius_graph(x, 10.0, mask)
+        b, i, j = radius_graph_edges(g)
+        edge = (x[b, i] - x[b, j]).norm(dim=-1)      # (E,), equal to g.dist up to float32 rounding; grads reach x
+
+    For a graph made with ``max_edges`` below ``row_ptr[-1]`` the triples past the buffers have no ``col``: refused."""
+    row_ptr, col, count = graph.row_ptr, graph.col, graph.count
+    B, Q = count.shape
+    edges = int(row_ptr[-1])
+    if edges > col.shape[0]:
+        raise ValueError(f"the graph has {edges} edges but col holds {col.shape[0]}: max_edges was too small")
+    row = torch.repeat_interleave(torch.arange(B * Q, device=count.device), count.reshape(-1).long(), output_size=edges)
+    return row // max(Q, 1), row % max(Q, 1), col[:edges].long()
 
 
 BACKBONE_PAIRS = tuple((a, b) for a in range(5) for b in range(5))   # all ordered pairs of N, CA, C, O, CB: ProteinMPNN's 25

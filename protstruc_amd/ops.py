@@ -1621,7 +1621,108 @@ def nearest_neighbors(points: torch.Tensor, k: int, point_mask: Optional[torch.T
     return idx, dist, count
 
 
-CLOSEST_MAX_ATOMS = 64          # PS_CLOSEST_MAX_ATOMS of include/protstruc_contacts.h: a residue's presence word is 64 bits
+RADIUS_TILE = 64  # PS_RADIUS_TILE of include/protstruc_graph.h
+RADIUS_BOX_FLOATS = 40   # PS_RADIUS_BOX_FLOATS: five boxes of eight floats per block of candidates
+RADIUS_STATS = 6   # PS_RADIUS_STATS: counters per wave of 64 queries
+
+
+def _launch_graph(name: str, *args) -> None:
+    """Call entry point ``name`` of libprotstruc_graph.so; HipLibraryError if it does not return hipSuccess."""
+    from . import _graph
+    rc = getattr(_graph.load(), name)(*args)
+    if rc:
+        _graph.check(rc, name)
+
+
+def check_radius_graph_shapes(points, cutoff, point_mask=None, queries=None, query_mask=None, exclude=None,
+                              query_exclude=None, include_self=False, max_edges=None) -> Tuple[int, int, int]:
+    """Shape rules of ``radius_graph``, on shapes, dtypes, devices and the scalars only (no launch): ValueError; returns
+    (B, M, Q).  K24's rules (``check_knn_shapes``) without a ``k``, except that ``cutoff`` is positive AND finite, and
+    ``max_edges`` is None or a non-negative integer."""
+    B, M = _points_dims(points, 2 ** 24)
+    _check_scalar(cutoff, "cutoff", "positive")
+    if max_edges is not None:
+        if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or max_edges < 0:
+            raise ValueError(f"max_edges must be None or a non-negative integer, got {max_edges!r}")
+    _check_optional(point_mask, (B, M), "point_mask", "points", (B, M, 3))
+    _check_optional(exclude, (B, M), "exclude", "points", (B, M, 3), integer=True)
+    Q = M
+    if queries is None:
+        for name, t in (("query_mask", query_mask), ("query_exclude", query_exclude)):
+            if t is not None:
+                raise ValueError(f"{name} needs queries: in the self graph the points' own mask and keys are used")
+    else:
+        shape = tuple(queries.shape)
+        if len(shape) != 3 or shape[2] != 3 or shape[0] != B:
+            raise ValueError(f"queries must have shape ({B}, queries, 3) to match points {(B, M, 3)}, got {shape}")
+        if not queries.dtype.is_floating_point:
+            raise ValueError(f"queries must be a floating-point tensor, got {queries.dtype}")
+        Q = shape[1]
+        _check_count(Q, 0, 2 ** 24, "queries per structure")
+        _check_optional(query_mask, (B, Q), "query_mask", "queries", shape)
+        _check_optional(query_exclude, (B, Q), "query_exclude", "queries", shape, integer=True)
+        if (exclude is None) != (query_exclude is None):
+            raise ValueError("exclude and query_exclude come together: a candidate is skipped where the two keys are equal")
+        if include_self:
+            raise ValueError("include_self applies to the self graph only (queries=None)")
+    _same_device(points, point_mask=point_mask, queries=queries, query_mask=query_mask, exclude=exclude,
+                 query_exclude=query_exclude)
+    return B, M, Q
+
+
+def radius_graph(points: torch.Tensor, cutoff: float, point_mask: Optional[torch.Tensor] = None, *,
+                 queries: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None,
+                 exclude: Optional[torch.Tensor] = None, query_exclude: Optional[torch.Tensor] = None,
+                 include_self: bool = False, max_edges: Optional[int] = None, return_stats: bool = False):
+    """K47 + K48.  Every neighbour of every query within ``cutoff``, as lists of any length in CSR form: ``(row_ptr
+    (B*Q+1,) int64, col (E,) int32, dist (E,) fp32, count (B,Q) int32)``.  The arguments and the predicate are those of
+    ``nearest_neighbors`` -- masks, keys, the self graph without ``queries``, ``d2`` in double on the float32 inputs,
+    ``d2 <= cutoff^2`` inclusive -- with no ``k`` and no cap: row ``b * Q + q`` is ``col[row_ptr[r]:row_ptr[r + 1]]``, the
+    neighbours' indices into the M axis of structure b, ASCENDING, and ``dist = sqrt(d2)`` rounded to float32 once.
+    A masked query or one with a non-finite coordinate has an empty row.
+
+    ``max_edges=None`` reads ``row_ptr[-1]`` from the device once, to size ``col`` and ``dist``: a host read, so not
+    capturable.  ``max_edges=n`` makes none: ``col`` and ``dist`` have n entries, an edge whose position is >= n is not
+    written, ``row_ptr`` and ``count`` stay exact (test ``row_ptr[-1] <= n``), and the entries past ``row_ptr[-1]`` are
+    -1 / +inf; this form runs inside a captured graph.  Three launches (boxes, count, fill) and a ``torch.cumsum``;
+    nothing of size Q*M is built; no atomics, deterministic (include/protstruc_graph.h).  ``return_stats`` appends the
+    counting sweep's (B, ceil(Q/64), RADIUS_STATS) int32 counters."""
+    B, M, Q = check_radius_graph_shapes(points, cutoff, point_mask, queries, query_mask, exclude, query_exclude, include_self,
+                                        max_edges)
+    x, pm, key = _f32c(points, "points"), _u8c(point_mask, "point_mask"), _i32c(exclude, "exclude")
+    y, qm, qkey = _f32c_opt(queries, "queries"), _u8c(query_mask, "query_mask"), _i32c(query_exclude, "query_exclude")
+    rows, waves = B * Q, (Q + 63) // 64
+    with _on(x.device):
+        row_ptr = torch.zeros(rows + 1, dtype=torch.int64, device=x.device)
+        stats = torch.zeros(B, waves, RADIUS_STATS, dtype=torch.int32, device=x.device) if return_stats else None
+        if not (B and M and Q):   # empty input: nothing to launch (an empty tensor has no device pointer)
+            n = 0 if max_edges is None else int(max_edges)
+            out = (row_ptr, torch.full((n,), -1, dtype=torch.int32, device=x.device),
+                   torch.full((n,), _INF, dtype=torch.float32, device=x.device),
+                   torch.zeros(B, Q, dtype=torch.int32, device=x.device))
+            return out + (stats,) if return_stats else out
+        boxes = torch.empty(B, (M + RADIUS_TILE - 1) // RADIUS_TILE, RADIUS_BOX_FLOATS, dtype=torch.float32, device=x.device)
+        count = torch.empty(B, Q, dtype=torch.int32, device=x.device)   # the kernel writes every element
+        stream = _stream(x)
+        inputs = (_ptr(x), _ptr(pm), _ptr(y), _ptr(qm), _ptr(key), _ptr(qkey), float(cutoff), int(bool(include_self)), _ptr(boxes))
+        _launch_graph("ps_radius_tile_boxes_f32", _ptr(x), _ptr(pm), _ptr(boxes), B, M, stream)
+        _launch_graph("ps_radius_count_f32", *inputs, _ptr(count), _ptr(stats), B, M, Q, stream)
+        torch.cumsum(count.reshape(-1), 0, dtype=torch.int64, out=row_ptr[1:])
+        if max_edges is None:
+            n = int(row_ptr[-1].item())   # the documented host read
+            col = torch.empty(n, dtype=torch.int32, device=x.device)   # the kernel writes every element
+            dist = torch.empty(n, dtype=torch.float32, device=x.device)
+        else:
+            n = int(max_edges)
+            col = torch.full((n,), -1, dtype=torch.int32, device=x.device)
+            dist = torch.full((n,), _INF, dtype=torch.float32, device=x.device)
+        if n:
+            _launch_graph("ps_radius_fill_f32", *inputs, _ptr(row_ptr), n, _ptr(col), _ptr(dist), B, M, Q, stream)
+    out = (row_ptr, col, dist, count)
+    return out + (stats,) if return_stats else out
+
+
+CLOSEST_MAX_ATOMS = 64         # PS_CLOSEST_MAX_ATOMS of include/protstruc_contacts.h: a residue's presence word is 64 bits
 CLOSEST_MAX_RESIDUES = 2 ** 20  # PS_CLOSEST_MAX_RESIDUES
 
 

@@ -648,6 +648,41 @@ class StructureBatch:
         return geometry.nearest_neighbors(self.xyz.reshape(B, N * A, 3), k, takes_part, exclude=residue,
                                           cutoff=float("inf") if cutoff is None else cutoff)
 
+    def radius_graph(self, cutoff: float = 10.0, atom: str = "CA", include_self: bool = False,
+                     other_chains_only: bool = False, max_edges: Optional[int] = None):
+        """Every residue within ``cutoff`` (A, inclusive) of every residue by the distance between their ``atom`` (default
+        CA): ``geometry.RadiusGraph(row_ptr, col, dist, count)`` -- row ``b * N + i`` is ``col[row_ptr[r]:row_ptr[r + 1]]``,
+        the neighbours of residue i of structure b, ascending, with no cap on their number; ``count`` is (B,N).  Who takes
+        part, ``include_self`` and ``other_chains_only`` are as in :meth:`knn_graph`; ``max_edges`` as in
+        ``geometry.radius_graph`` (None reads the number of edges from the device; an integer makes no host read and
+        cuts the list there).  ``geometry.radius_graph_edges`` gives (batch, row, col) triples; not differentiable."""
+        from . import geometry
+
+        if not ATOM.is_valid(atom):
+            raise ValueError(f"Atom {atom} is not valid.")
+        (slot,) = self._atom_slots((atom,))
+        exclude = self._chain_keys() if other_chains_only else None
+        return geometry.radius_graph(self.xyz[:, :, slot], cutoff, self._present_atoms()[:, :, slot], exclude=exclude,
+                                     include_self=include_self, max_edges=max_edges)
+
+    def atom_radius_graph(self, cutoff: float = 5.0, atoms="all", exclude_same_residue: bool = True,
+                          max_edges: Optional[int] = None):
+        """Every atom within ``cutoff`` (A, inclusive) of every atom, over the (B, N*A, 3) view of the coordinates -- no
+        gather: ``geometry.RadiusGraph(row_ptr, col, dist, count)`` with ``count`` (B, N*A); ``col`` indexes the flattened
+        atom axis (``col // A`` is the neighbour's residue, ``col % A`` its atom slot).  Who takes part, ``atoms`` and
+        ``exclude_same_residue`` are as in :meth:`atom_knn_graph`; ``max_edges`` as in ``geometry.radius_graph``.  An
+        atom has hundreds of neighbours at 8 - 12 A: nothing is cut.  Not differentiable."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+        chosen[self._atom_slots(atoms)] = True
+        takes_part = (self._present_atoms() & chosen).reshape(B, N * A)
+        residue = None
+        if exclude_same_residue:
+            residue = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
+        return geometry.radius_graph(self.xyz.reshape(B, N * A, 3), cutoff, takes_part, exclude=residue, max_edges=max_edges)
+
     # ------------------------------------------------------------------ residue contacts
     def closest_atom_distances(self, atoms="all", cutoff: Optional[float] = None):
         """How close every pair of residues comes (``geometry.closest_atom_distances``): ``geometry.ClosestAtoms(dist,

@@ -1,9 +1,10 @@
 /*
- * protstruc_graph.h -- C ABI of libprotstruc_graph.so: the radius graph (K47, K48), every neighbour of every query within a
- * cutoff as a variable-length list in CSR form.
+ * protstruc_graph.h -- C ABI of the radius-graph kernels (K47, K48) of libprotstruc_hip.so: every neighbour of every query
+ * within a cutoff as a variable-length list in CSR form.
  *
- * A library of its own, beside libprotstruc_hip.so (protstruc_hip.h and its side headers) and libprotstruc_rccl.so
- * (protstruc_rccl.h), with a version of its own: adding it changed no declaration and no export of the other two.
+ * These entry points are compiled into the same shared library as those of protstruc_hip.h; they are declared in a header
+ * of their own, with a version number of their own, so that adding them left PS_ABI_VERSION and every declaration of the
+ * other headers as they were.
  *
  * Conventions (all entry points), those of protstruc_hip.h:
  *   - every pointer is a DEVICE pointer owned by the caller; the library never allocates, frees or retains memory;
@@ -48,7 +49,7 @@
  * lane takes part in is skipped.  What is left is decided in double, by the definition.  Both sweeps evaluate the same
  * predicate on the same inputs, so they agree; the writing sweep takes every row's position from row_ptr.
  *
- * THE BOX TEST (csrc_graph/radius_box.hpp holds the code and the full argument).  For the box A of some queries and the box
+ * THE BOX TEST (csrc/radius_box.hpp holds the code and the full argument).  For the box A of some queries and the box
  * B of some candidates -- lo and hi of their finite, unmasked points, exact in float32 --
  *     gap_a = max(0, A.lo[a] - B.hi[a], B.lo[a] - A.hi[a])          G = (gap_x*gap_x + gap_y*gap_y) + gap_z*gap_z      in float32
  *     B is dropped  iff  B holds no point  or  G > fl32(C2) * (1 + 2^-20) + 2^-126

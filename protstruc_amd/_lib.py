@@ -59,6 +59,7 @@ FAMILIES = (   # in load order
     Family("protstruc_structalign.h", "STRUCTALIGN_SIGNATURES", "ps_structalign_api", "EXPECTED_STRUCTALIGN_API",
            "structure-alignment"),
     Family("protstruc_ensemble.h", "ENSEMBLE_SIGNATURES", "ps_ensemble_api", "EXPECTED_ENSEMBLE_API", "ensemble"),
+    Family("protstruc_graph.h", "GRAPH_SIGNATURES", "ps_graph_api", "EXPECTED_GRAPH_API", "radius-graph"),
 )
 
 EXPECTED_CONTACTS_API = 1  # PS_CONTACTS_API: the closest-atom entry points (K31 / K32)
@@ -66,7 +67,8 @@ EXPECTED_PAIRHEAD_API = 1  # PS_PAIRHEAD_API: the pair-head entry points (K33 - 
 EXPECTED_SUPERPOSE_API = 1  # PS_SUPERPOSE_API: the superposition entry points (K37 - K40)
 EXPECTED_STRUCTALIGN_API = 1  # PS_STRUCTALIGN_API: the structure-alignment entry points (K41 - K44)
 EXPECTED_ENSEMBLE_API = 1  # PS_ENSEMBLE_API: the ensemble entry points (K45, K46)
-# CONTACT_SIGNATURES ... ENSEMBLE_SIGNATURES, the attributes FAMILIES names: what each family's header declares
+EXPECTED_GRAPH_API = 1  # PS_GRAPH_API: the radius-graph entry points (K47, K48)
+# CONTACT_SIGNATURES ... GRAPH_SIGNATURES, the attributes FAMILIES names: what each family's header declares
 globals().update({family.signatures: prototypes(family.header) for family in FAMILIES})
 
 _lib = None

@@ -20,9 +20,6 @@ LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_hip.so")
 # the multi-GPU exchange step lives in its own library so that libprotstruc_hip.so has no RCCL dependency
 RCCL_SRC_DIR = os.path.join(HERE, "csrc_rccl")
 RCCL_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_rccl.so")
-# the radius graph (K47, K48) is a third library, with a header and a version of its own: include/protstruc_graph.h
-GRAPH_SRC_DIR = os.path.join(HERE, "csrc_graph")
-GRAPH_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_graph.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ROCM_LIB = os.environ.get("ROCM_LIB", "/opt/rocm/lib")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"]
@@ -107,6 +104,9 @@ def build(force=False, verbose=True):
     return _library().build(force, verbose)
 
 
+build_graph = build   # transitional, see _graph.py: the radius graph's former build step; unused, deleted with that module
+
+
 def rccl_sources():
     return sorted(glob.glob(os.path.join(RCCL_SRC_DIR, "*.cpp")))
 
@@ -125,28 +125,6 @@ def build_rccl(force=False, verbose=True):
     """libprotstruc_rccl.so: host-only C++ over RCCL (ps_allgather_rows, include/protstruc_rccl.h).  Linked against
     librccl.so.1 by SONAME: inside a PyTorch process that is the RCCL PyTorch already loaded, so one copy serves both."""
     return _rccl_library().build(force, verbose)
-
-
-def graph_sources():
-    return sorted(glob.glob(os.path.join(GRAPH_SRC_DIR, "*.hip")))
-
-
-def _graph_library(out=None):
-    inputs = graph_sources() + sorted(glob.glob(os.path.join(GRAPH_SRC_DIR, "*.hpp"))) + \
-        sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "protstruc_graph.h")]
-    return _Target(out or GRAPH_LIB_PATH, b"graph-lib " + " ".join(FLAGS).encode(), inputs,
-                   lambda tmp: [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp] + graph_sources())
-
-
-def graph_is_stale(path=None):
-    return _graph_library(path).is_stale()
-
-
-def build_graph(force=False, verbose=True):
-    """libprotstruc_graph.so: csrc_graph/*.hip, the radius graph (include/protstruc_graph.h).  Compiled with exactly FLAGS
-    and -I csrc: the kernels share ps_common.hpp and owner_sweep.hpp with libprotstruc_hip.so and its arithmetic contract
-    (-ffp-contract=off), and add no export to it."""
-    return _graph_library().build(force, verbose)
 
 
 EXAMPLE_SRC = os.path.join(HERE, "..", "examples", "c_abi_demo.c")
@@ -192,6 +170,5 @@ if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build(force=force))
     print(build_rccl(force=force))
-    print(build_graph(force=force))
     print(build_c_example())
     print(build_arith_probe(force=force))

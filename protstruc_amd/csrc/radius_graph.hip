@@ -20,7 +20,7 @@
 // The sinks: COUNT adds one; FILL writes (j, (float)sqrt(d2)) at the lane's running position, which starts at
 // row_ptr[row], and only below max_edges; STATS is COUNT plus six counters per wave.  Each lane writes along its own row
 // (DESIGN.md section 4 says why not transposed).  The same source, so the same predicate: count and fill agree.
-#include "ps_common.hpp"     // PS_WAVE, f3, load3, ps_launch: shared with libprotstruc_hip.so (-I csrc), not copied
+#include "ps_common.hpp"     // PS_WAVE, f3, load3, ps_launch
 #include "radius_box.hpp"
 
 #include <math.h>

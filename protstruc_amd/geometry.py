@@ -565,6 +565,23 @@ def solvent_accessibility(points, radius, point_mask=None, isolate=None, probe=1
                                                            probe=float(probe)))
 
 
+def _marshal(named):
+    """What the functions over neighbour lists share: numpy or tensors in (``named``: (name, value) pairs, None left out,
+    the first one deciding the device the results come back on) -> ``(prepared, finish)``, the dict of prepared tensors
+    by name and the function that takes a tuple of result tensors (or None) back out the same way.  The edge functions
+    pass the dict on as ``**prepared``, so their names are the parameter names of ``ops.edge_rbf`` / ``ops.edge_frames``."""
+    given = [(name, t) for name, t in named if t is not None]
+    for name, t in given:
+        if not isinstance(t, (torch.Tensor, np.ndarray)):
+            raise TypeError(f"{name} must be a tensor or an ndarray")
+    home = named[0][1].device if isinstance(named[0][1], torch.Tensor) else None
+    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
+
+    def finish(out):
+        return tuple(None if t is None else _finish(t if home is None else t.to(home), ft) for t in out)
+    return dict(zip((name for name, _ in given), prepped)), finish
+
+
 class Neighbors(NamedTuple):
     """The k nearest neighbours of every query (``nearest_neighbors``), nearest first."""
     idx: torch.Tensor     # (B,Q,k) int32: indices into the points' M axis; -1 where a query has fewer than k neighbours
@@ -594,18 +611,11 @@ def nearest_neighbors(points, k, point_mask=None, *, queries=None, query_mask=No
         edge = (xj - x[:, :, None]).norm(dim=-1)                # (B,M,k), equal to nb.dist up to float32 rounding
         edge = edge.masked_fill(nb.idx < 0, 0.0)                # the padding takes no gradient
     """
-    given = [(name, t) for name, t in (("points", points), ("point_mask", point_mask), ("queries", queries),
-                                       ("query_mask", query_mask), ("exclude", exclude), ("query_exclude", query_exclude))
-             if t is not None]
-    for name, t in given:
-        if not isinstance(t, (torch.Tensor, np.ndarray)):
-            raise TypeError(f"{name} must be a tensor or an ndarray")
-    home = points.device if isinstance(points, torch.Tensor) else None
-    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
-    args = dict(zip((name for name, _ in given), prepped))
+    args, finish = _marshal((("points", points), ("point_mask", point_mask), ("queries", queries), ("query_mask", query_mask),
+                             ("exclude", exclude), ("query_exclude", query_exclude)))
     out = ops.nearest_neighbors(args.pop("points"), k, args.pop("point_mask", None), cutoff=cutoff, include_self=include_self,
                                 **args)
-    return Neighbors(*(_finish(t if home is None else t.to(home), ft) for t in out))
+    return Neighbors(*finish(out))
 
 
 def gather_neighbors(values, idx, fill=0):
@@ -655,18 +665,11 @@ def radius_graph(points, cutoff, point_mask=None, *, queries=None, query_mask=No
 
     Not differentiable -- the list is discrete -- and the outputs carry no graph; ``radius_graph_edges`` is the route to
     distances that are differentiable with respect to the coordinates."""
-    given = [(name, t) for name, t in (("points", points), ("point_mask", point_mask), ("queries", queries),
-                                       ("query_mask", query_mask), ("exclude", exclude), ("query_exclude", query_exclude))
-             if t is not None]
-    for name, t in given:
-        if not isinstance(t, (torch.Tensor, np.ndarray)):
-            raise TypeError(f"{name} must be a tensor or an ndarray")
-    home = points.device if isinstance(points, torch.Tensor) else None
-    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
-    args = dict(zip((name for name, _ in given), prepped))
+    args, finish = _marshal((("points", points), ("point_mask", point_mask), ("queries", queries), ("query_mask", query_mask),
+                             ("exclude", exclude), ("query_exclude", query_exclude)))
     out = ops.radius_graph(args.pop("points"), cutoff, args.pop("point_mask", None), include_self=include_self,
                            max_edges=max_edges, **args)
-    return RadiusGraph(*(_finish(t if home is None else t.to(home), ft) for t in out))
+    return RadiusGraph(*finish(out))
 
 
 def radius_graph_edges(graph):
@@ -704,19 +707,6 @@ def rbf_centers(n_rbf: int = 16, d_min: float = 2.0, d_max: float = 22.0):
     return centers, (float(d_max) - float(d_min)) / int(n_rbf)
 
 
-def _edge_call(named, run):
-    """What the two edge-feature functions share: numpy or tensors in (``named``: (name, value) pairs, the first one
-    deciding the device the results come back on), ``run(**prepared)`` -> a tuple of tensors or None, the same out."""
-    given = [(name, t) for name, t in named if t is not None]
-    for name, t in given:
-        if not isinstance(t, (torch.Tensor, np.ndarray)):
-            raise TypeError(f"{name} must be a tensor or an ndarray")
-    home = given[0][1].device if isinstance(given[0][1], torch.Tensor) else None
-    prepped, ft = _prep([t.detach() if isinstance(t, torch.Tensor) else t for _, t in given])
-    out = run(**dict(zip((name for name, _ in given), prepped)))
-    return tuple(None if t is None else _finish(t if home is None else t.to(home), ft) for t in out)
-
-
 def edge_distance_features(xyz, idx, atom_mask=None, pairs=BACKBONE_PAIRS, centers=None, sigma=None, return_dist=False):
     """Radial basis functions of the atom-pair distances along the edges of a neighbour graph: ``rbf`` (B,N,k,P*R) fp32
     or, with ``return_dist``, ``(rbf, dist)`` with ``dist`` (B,N,k,P).  ``xyz`` is (B,N,A,3); ``idx`` (B,N,k) are the
@@ -739,10 +729,9 @@ def edge_distance_features(xyz, idx, atom_mask=None, pairs=BACKBONE_PAIRS, cente
     pairs = [tuple(p) for p in pairs]
     if any(len(p) != 2 for p in pairs):
         raise ValueError("pairs must be (slot on the source residue, slot on the neighbour) pairs")
-    dist, rbf = _edge_call((("xyz", xyz), ("idx", idx), ("atom_mask", atom_mask)),
-                           lambda xyz, idx, atom_mask=None: ops.edge_rbf(
-                               xyz, idx, atom_mask, pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs],
-                               centers=centers, sigma=sigma, want_dist=bool(return_dist)))
+    args, finish = _marshal((("xyz", xyz), ("idx", idx), ("atom_mask", atom_mask)))
+    dist, rbf = finish(ops.edge_rbf(**args, pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers,
+                                    sigma=sigma, want_dist=bool(return_dist)))
     return (rbf, dist) if return_dist else rbf
 
 
@@ -762,7 +751,8 @@ def edge_frame_features(rot, trans, idx, frame_mask=None) -> EdgeFrames:
     numpy in -> numpy out; tensors come back on the device of ``rot``, CPU tensors included.
 
     Not differentiable: the outputs carry no graph.  The differentiable route stays ``gather_neighbors`` and plain torch."""
-    return EdgeFrames(*_edge_call((("rot", rot), ("trans", trans), ("idx", idx), ("frame_mask", frame_mask)), ops.edge_frames))
+    args, finish = _marshal((("rot", rot), ("trans", trans), ("idx", idx), ("frame_mask", frame_mask)))
+    return EdgeFrames(*finish(ops.edge_frames(**args)))
 
 
 class SideChainTorsions(NamedTuple):

@@ -1553,19 +1553,12 @@ def solvent_accessibility(points: torch.Tensor, radius: torch.Tensor, point_mask
 KNN_MAX_K = 64   # PS_KNN_MAX_K of include/protstruc_hip.h: an owner's list of k lives in LDS
 
 
-def check_knn_shapes(points, k, point_mask=None, queries=None, query_mask=None, exclude=None, query_exclude=None,
-                     cutoff=_INF, include_self=False) -> None:
-    """Shape rules of ``nearest_neighbors``, on shapes, dtypes, devices and the scalars only (no launch): ValueError.
-    ``1 <= k <= KNN_MAX_K``; ``cutoff`` positive, +inf allowed; ``exclude`` / ``query_exclude`` integer tensors.  Without
-    ``queries`` (the self graph) ``query_mask`` and ``query_exclude`` are not given -- they are ``point_mask`` and
-    ``exclude``; with ``queries``, ``exclude`` and ``query_exclude`` come together and ``include_self`` means nothing."""
-    B, M = _points_dims(points, 2 ** 24)
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KNN_MAX_K:
-        raise ValueError(f"k must be an integer in 1 .. {KNN_MAX_K}, got {k!r}")
-    if float(cutoff) != _INF:
-        _check_scalar(cutoff, "cutoff", "positive")
+def _check_neighbor_operands(points, B, M, point_mask, queries, query_mask, exclude, query_exclude, include_self) -> int:
+    """The masks, keys and queries of a neighbour list over ``points`` (B,M,3), as ``check_knn_shapes`` states them:
+    ValueError; returns Q, the queries per structure (M in the self graph)."""
     _check_optional(point_mask, (B, M), "point_mask", "points", (B, M, 3))
     _check_optional(exclude, (B, M), "exclude", "points", (B, M, 3), integer=True)
+    Q = M
     if queries is None:
         for name, t in (("query_mask", query_mask), ("query_exclude", query_exclude)):
             if t is not None:
@@ -1586,6 +1579,21 @@ def check_knn_shapes(points, k, point_mask=None, queries=None, query_mask=None, 
             raise ValueError("include_self applies to the self graph only (queries=None)")
     _same_device(points, point_mask=point_mask, queries=queries, query_mask=query_mask, exclude=exclude,
                  query_exclude=query_exclude)
+    return Q
+
+
+def check_knn_shapes(points, k, point_mask=None, queries=None, query_mask=None, exclude=None, query_exclude=None,
+                     cutoff=_INF, include_self=False) -> None:
+    """Shape rules of ``nearest_neighbors``, on shapes, dtypes, devices and the scalars only (no launch): ValueError.
+    ``1 <= k <= KNN_MAX_K``; ``cutoff`` positive, +inf allowed; ``exclude`` / ``query_exclude`` integer tensors.  Without
+    ``queries`` (the self graph) ``query_mask`` and ``query_exclude`` are not given -- they are ``point_mask`` and
+    ``exclude``; with ``queries``, ``exclude`` and ``query_exclude`` come together and ``include_self`` means nothing."""
+    B, M = _points_dims(points, 2 ** 24)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must be an integer in 1 .. {KNN_MAX_K}, got {k!r}")
+    if float(cutoff) != _INF:
+        _check_scalar(cutoff, "cutoff", "positive")
+    _check_neighbor_operands(points, B, M, point_mask, queries, query_mask, exclude, query_exclude, include_self)
 
 
 def nearest_neighbors(points: torch.Tensor, k: int, point_mask: Optional[torch.Tensor] = None, *,
@@ -1626,14 +1634,6 @@ RADIUS_BOX_FLOATS = 40   # PS_RADIUS_BOX_FLOATS: five boxes of eight floats per 
 RADIUS_STATS = 6   # PS_RADIUS_STATS: counters per wave of 64 queries
 
 
-def _launch_graph(name: str, *args) -> None:
-    """Call entry point ``name`` of libprotstruc_graph.so; HipLibraryError if it does not return hipSuccess."""
-    from . import _graph
-    rc = getattr(_graph.load(), name)(*args)
-    if rc:
-        _graph.check(rc, name)
-
-
 def check_radius_graph_shapes(points, cutoff, point_mask=None, queries=None, query_mask=None, exclude=None,
                               query_exclude=None, include_self=False, max_edges=None) -> Tuple[int, int, int]:
     """Shape rules of ``radius_graph``, on shapes, dtypes, devices and the scalars only (no launch): ValueError; returns
@@ -1644,29 +1644,7 @@ def check_radius_graph_shapes(points, cutoff, point_mask=None, queries=None, que
     if max_edges is not None:
         if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or max_edges < 0:
             raise ValueError(f"max_edges must be None or a non-negative integer, got {max_edges!r}")
-    _check_optional(point_mask, (B, M), "point_mask", "points", (B, M, 3))
-    _check_optional(exclude, (B, M), "exclude", "points", (B, M, 3), integer=True)
-    Q = M
-    if queries is None:
-        for name, t in (("query_mask", query_mask), ("query_exclude", query_exclude)):
-            if t is not None:
-                raise ValueError(f"{name} needs queries: in the self graph the points' own mask and keys are used")
-    else:
-        shape = tuple(queries.shape)
-        if len(shape) != 3 or shape[2] != 3 or shape[0] != B:
-            raise ValueError(f"queries must have shape ({B}, queries, 3) to match points {(B, M, 3)}, got {shape}")
-        if not queries.dtype.is_floating_point:
-            raise ValueError(f"queries must be a floating-point tensor, got {queries.dtype}")
-        Q = shape[1]
-        _check_count(Q, 0, 2 ** 24, "queries per structure")
-        _check_optional(query_mask, (B, Q), "query_mask", "queries", shape)
-        _check_optional(query_exclude, (B, Q), "query_exclude", "queries", shape, integer=True)
-        if (exclude is None) != (query_exclude is None):
-            raise ValueError("exclude and query_exclude come together: a candidate is skipped where the two keys are equal")
-        if include_self:
-            raise ValueError("include_self applies to the self graph only (queries=None)")
-    _same_device(points, point_mask=point_mask, queries=queries, query_mask=query_mask, exclude=exclude,
-                 query_exclude=query_exclude)
+    Q = _check_neighbor_operands(points, B, M, point_mask, queries, query_mask, exclude, query_exclude, include_self)
     return B, M, Q
 
 
@@ -1705,8 +1683,8 @@ def radius_graph(points: torch.Tensor, cutoff: float, point_mask: Optional[torch
         count = torch.empty(B, Q, dtype=torch.int32, device=x.device)   # the kernel writes every element
         stream = _stream(x)
         inputs = (_ptr(x), _ptr(pm), _ptr(y), _ptr(qm), _ptr(key), _ptr(qkey), float(cutoff), int(bool(include_self)), _ptr(boxes))
-        _launch_graph("ps_radius_tile_boxes_f32", _ptr(x), _ptr(pm), _ptr(boxes), B, M, stream)
-        _launch_graph("ps_radius_count_f32", *inputs, _ptr(count), _ptr(stats), B, M, Q, stream)
+        _launch("ps_radius_tile_boxes_f32", _ptr(x), _ptr(pm), _ptr(boxes), B, M, stream)
+        _launch("ps_radius_count_f32", *inputs, _ptr(count), _ptr(stats), B, M, Q, stream)
         torch.cumsum(count.reshape(-1), 0, dtype=torch.int64, out=row_ptr[1:])
         if max_edges is None:
             n = int(row_ptr[-1].item())   # the documented host read
@@ -1717,7 +1695,7 @@ def radius_graph(points: torch.Tensor, cutoff: float, point_mask: Optional[torch
             col = torch.full((n,), -1, dtype=torch.int32, device=x.device)
             dist = torch.full((n,), _INF, dtype=torch.float32, device=x.device)
         if n:
-            _launch_graph("ps_radius_fill_f32", *inputs, _ptr(row_ptr), n, _ptr(col), _ptr(dist), B, M, Q, stream)
+            _launch("ps_radius_fill_f32", *inputs, _ptr(row_ptr), n, _ptr(col), _ptr(dist), B, M, Q, stream)
     out = (row_ptr, col, dist, count)
     return out + (stats,) if return_stats else out
 

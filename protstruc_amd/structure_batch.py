@@ -608,6 +608,28 @@ class StructureBatch:
         """(B,N) int32 chain index; the padding's NaN becomes -1 (padded residues are outside every mask anyway)."""
         return torch.nan_to_num(self.chain_idx.to(torch.float32), nan=-1.0).to(torch.int32)
 
+    def _residue_points(self, atom, other_chains_only):
+        """What the residue graphs take (:meth:`knn_graph`, :meth:`radius_graph`): the residues' ``atom`` (B,N,3), where it
+        is present (B,N), and the chain keys (B,N) that leave only the other chains, or None."""
+        if not ATOM.is_valid(atom):
+            raise ValueError(f"Atom {atom} is not valid.")
+        (slot,) = self._atom_slots((atom,))
+        exclude = self._chain_keys() if other_chains_only else None
+        return self.xyz[:, :, slot], self._present_atoms()[:, :, slot], exclude
+
+    def _flat_atom_points(self, atoms, exclude_same_residue):
+        """What the atom graphs take (:meth:`atom_knn_graph`, :meth:`atom_radius_graph`): the (B, N*A, 3) view of the
+        coordinates -- no gather --, the point mask (B, N*A) with the selection ``atoms`` folded in, and the residue keys
+        (B, N*A) that leave out an atom's own residue, or None."""
+        B, N, A = self.xyz.shape[:3]
+        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
+        chosen[self._atom_slots(atoms)] = True
+        takes_part = (self._present_atoms() & chosen).reshape(B, N * A)
+        residue = None
+        if exclude_same_residue:
+            residue = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
+        return self.xyz.reshape(B, N * A, 3), takes_part, residue
+
     def knn_graph(self, k: int = 30, atom: str = "CA", cutoff: Optional[float] = None, include_self: bool = False,
                   other_chains_only: bool = False):
         """The ``k`` nearest residues of every residue by the distance between their ``atom`` (default CA):
@@ -620,11 +642,8 @@ class StructureBatch:
         no (B,N,N) tensor is built; not differentiable -- ``geometry.gather_neighbors`` rebuilds differentiable edges."""
         from . import geometry
 
-        if not ATOM.is_valid(atom):
-            raise ValueError(f"Atom {atom} is not valid.")
-        (slot,) = self._atom_slots((atom,))
-        exclude = self._chain_keys() if other_chains_only else None
-        return geometry.nearest_neighbors(self.xyz[:, :, slot], k, self._present_atoms()[:, :, slot], exclude=exclude,
+        points, present, exclude = self._residue_points(atom, other_chains_only)
+        return geometry.nearest_neighbors(points, k, present, exclude=exclude,
                                           cutoff=float("inf") if cutoff is None else cutoff, include_self=include_self)
 
     def atom_knn_graph(self, k: int = 32, atoms="all", cutoff: Optional[float] = None, exclude_same_residue: bool = True):
@@ -638,14 +657,8 @@ class StructureBatch:
         Needs neither a sequence nor radii.  One HIP kernel; no (B, N*A, N*A) tensor is built; not differentiable."""
         from . import geometry
 
-        B, N, A = self.xyz.shape[:3]
-        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
-        chosen[self._atom_slots(atoms)] = True
-        takes_part = (self._present_atoms() & chosen).reshape(B, N * A)
-        residue = None
-        if exclude_same_residue:
-            residue = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
-        return geometry.nearest_neighbors(self.xyz.reshape(B, N * A, 3), k, takes_part, exclude=residue,
+        points, takes_part, residue = self._flat_atom_points(atoms, exclude_same_residue)
+        return geometry.nearest_neighbors(points, k, takes_part, exclude=residue,
                                           cutoff=float("inf") if cutoff is None else cutoff)
 
     def radius_graph(self, cutoff: float = 10.0, atom: str = "CA", include_self: bool = False,
@@ -658,11 +671,8 @@ class StructureBatch:
         cuts the list there).  ``geometry.radius_graph_edges`` gives (batch, row, col) triples; not differentiable."""
         from . import geometry
 
-        if not ATOM.is_valid(atom):
-            raise ValueError(f"Atom {atom} is not valid.")
-        (slot,) = self._atom_slots((atom,))
-        exclude = self._chain_keys() if other_chains_only else None
-        return geometry.radius_graph(self.xyz[:, :, slot], cutoff, self._present_atoms()[:, :, slot], exclude=exclude,
+        points, present, exclude = self._residue_points(atom, other_chains_only)
+        return geometry.radius_graph(points, cutoff, present, exclude=exclude,
                                      include_self=include_self, max_edges=max_edges)
 
     def atom_radius_graph(self, cutoff: float = 5.0, atoms="all", exclude_same_residue: bool = True,
@@ -674,14 +684,8 @@ class StructureBatch:
         atom has hundreds of neighbours at 8 - 12 A: nothing is cut.  Not differentiable."""
         from . import geometry
 
-        B, N, A = self.xyz.shape[:3]
-        chosen = torch.zeros(A, dtype=torch.bool, device=self.device)
-        chosen[self._atom_slots(atoms)] = True
-        takes_part = (self._present_atoms() & chosen).reshape(B, N * A)
-        residue = None
-        if exclude_same_residue:
-            residue = torch.arange(N, dtype=torch.int32, device=self.device).repeat_interleave(A).expand(B, N * A)
-        return geometry.radius_graph(self.xyz.reshape(B, N * A, 3), cutoff, takes_part, exclude=residue, max_edges=max_edges)
+        points, takes_part, residue = self._flat_atom_points(atoms, exclude_same_residue)
+        return geometry.radius_graph(points, cutoff, takes_part, exclude=residue, max_edges=max_edges)
 
     # ------------------------------------------------------------------ residue contacts
     def closest_atom_distances(self, atoms="all", cutoff: Optional[float] = None):

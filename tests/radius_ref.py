@@ -8,7 +8,7 @@ on the same float32 inputs the kernels get -- brute force over all pairs.
 
 Every numpy operation rounds on its own, as the kernel's do under -ffp-contract=off, and a double square root and its
 conversion to float32 are correctly rounded on both sides: the tests demand EQUAL count, row_ptr and col and bitwise equal
-dist.  Also here: a float32 restatement of the box test (csrc_graph/radius_box.hpp), the case families of
+dist.  Also here: a float32 restatement of the box test (csrc/radius_box.hpp), the case families of
 tests/test_gpu_radius.py, and the conditions that keep those cases from passing vacuously (``assert_family``).
 """
 import functools

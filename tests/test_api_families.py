@@ -23,9 +23,9 @@ def lib():
     return _lib.load()
 
 
-def test_the_registry_is_the_five_families_in_load_order():
+def test_the_registry_is_the_six_families_in_load_order():
     assert [family.word for family in _lib.FAMILIES] == ["contacts", "pair-head", "superposition", "structure-alignment",
-                                                         "ensemble"]
+                                                         "ensemble", "radius-graph"]
     for family in _lib.FAMILIES:
         stem = re.fullmatch(r"ps_([a-z]+)_api", family.version_fn).group(1)
         assert family.header == f"protstruc_{stem}.h" and family.expected == f"EXPECTED_{stem.upper()}_API"
@@ -99,7 +99,8 @@ def test_the_table_of_mirrored_constants_is_complete():
             "DSSP_MAX_RESIDUES", "SASA_MAX_SPHERE_POINTS", "KNN_MAX_K", "EDGE_MAX_PAIRS", "EDGE_MAX_RBF", "CHI_MAX_TYPES",
             "CLOSEST_MAX_ATOMS", "CLOSEST_MAX_RESIDUES", "PAIRHEAD_MAX_RESIDUES", "PAIRHEAD_MAX_BREAKS", "PAIRHEAD_MAX_BINS",
             "PAIRHEAD_MAX_TABLES", "PAIRHEAD_NO_TARGET", "SUPERPOSE_MAX_POINTS", "SUPERPOSE_MAX_OBJECTIVES", "SUPERPOSE_TM",
-            "SUPERPOSE_COUNT", "STRUCTALIGN_MAX_POINTS", "CLUSTER_MAX_ITEMS", "RMSD_MATRIX_MAX_POINTS"} <= names
+            "SUPERPOSE_COUNT", "STRUCTALIGN_MAX_POINTS", "CLUSTER_MAX_ITEMS", "RMSD_MATRIX_MAX_POINTS",
+            "RADIUS_TILE", "RADIUS_BOX_FLOATS", "RADIUS_STATS"} <= names
     assert all(macro == "PS_" + name for name, macro, _ in MIRRORED), "a constant is called what its macro is called"
 
 

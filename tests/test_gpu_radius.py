@@ -32,10 +32,9 @@ PDB_FILES = ("1REX", "4EOT", "1ad0_DC", "5cjx_HL")
 def pkg():
     assert torch.cuda.is_available(), "-m gpu tests need a GPU"
     import protstruc_amd
-    from protstruc_amd import _graph, _lib, build, geometry, ops  # noqa: F401 -- the submodules the tests reach through the package
-    build.build_graph(force=False)
+    from protstruc_amd import _lib, build, geometry, ops  # noqa: F401 -- the submodules the tests reach through the package
+    build.build(force=False)
     _lib.load()
-    _graph.load()
     return protstruc_amd
 
 
@@ -48,7 +47,7 @@ def in_sentinels(pkg, x, cutoff, mask=None, queries=None, query_mask=None, exclu
     """The three launches through the C ABI, with col and dist carved out of buffers of sentinels 4 to 12 bytes past a
     16-byte boundary: (row_ptr, col, dist, count), after checking that nothing around them was written.  ``capacity`` None:
     exactly the number of edges; otherwise entries past the edges keep the sentinel."""
-    lib = pkg._graph.load()
+    lib = pkg._lib.load()
     B, M = x.shape[:2]
     Q = M if queries is None else queries.shape[1]
     u8 = lambda t: None if t is None else t.to(torch.uint8).contiguous()       # noqa: E731
@@ -325,7 +324,7 @@ def test_ops_with_nothing_to_do_launch_nothing(pkg, monkeypatch):
     def no_launch(*args):
         raise AssertionError("an empty call launched a kernel")
 
-    monkeypatch.setattr(ops, "_launch_graph", no_launch)
+    monkeypatch.setattr(ops, "_launch", no_launch)
     for B, M, Q in ((0, 5, None), (2, 0, None), (2, 0, 5), (2, 5, 0), (0, 0, 0)):
         x = torch.zeros(B, M, 3, device="cuda")
         queries = None if Q is None else torch.zeros(B, Q, 3, device="cuda")
@@ -403,8 +402,7 @@ def assert_variants_differ(name):
 
 
 def test_contract_cases_cover_the_header_and_meet_the_yardstick(pkg):
-    from protstruc_amd import _graph
-    assert sorted({s for case in CONTRACT for s in case.symbols}) == sorted(set(_graph.SIGNATURES) - {"ps_graph_api"})
+    assert sorted({s for case in CONTRACT for s in case.symbols}) == sorted(set(pkg._lib.GRAPH_SIGNATURES) - {"ps_graph_api"})
     for name in NAMES:
         assert_variants_differ(name)
     for v in "AB":

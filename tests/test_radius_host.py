@@ -1,7 +1,8 @@
 """The radius graph without a GPU: the yardstick (tests/radius_ref.py) held to K24's, the box test the kernels run
-(csrc_graph/radius_box.hpp, compiled for the host) held to "never drops a block that holds a neighbour pair" on adversarial
+(csrc/radius_box.hpp, compiled for the host) held to "never drops a block that holds a neighbour pair" on adversarial
 blocks, the conditions that keep the GPU cases of tests/test_gpu_radius.py from passing vacuously, every refusal of
-``ops.check_radius_graph_shapes`` with its message, and the header, the binding and the cross-compiled library."""
+``ops.check_radius_graph_shapes`` with its message, and the radius graph's own entry points, arguments and sources (what
+every family shares is in tests/test_api_families.py)."""
 import ctypes
 import os
 import re
@@ -12,9 +13,9 @@ import numpy as np
 import pytest
 import torch
 
-from protstruc_amd import _graph, _lib, build, ops
+from protstruc_amd import _lib, build, ops
 from tests import knn_ref, radius_ref as R
-from tests.c_headers import INCLUDE, declared_symbols, macros
+from tests.c_headers import macros
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = "protstruc_graph.h"
@@ -54,7 +55,7 @@ def box_program(tmp_path_factory):
     compiler = next((c for c in ("g++", "c++", "clang++") if shutil.which(c)), None)
     assert compiler is not None, "no host C++ compiler"
     exe = str(tmp_path_factory.mktemp("radius_box") / "radius_box_host")
-    subprocess.run([compiler, "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "protstruc_amd", "csrc_graph"),
+    subprocess.run([compiler, "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "protstruc_amd", "csrc"),
                     os.path.join(ROOT, "tools", "radius_box_host.cpp"), "-o", exe], check=True)
     return exe
 
@@ -272,68 +273,22 @@ def test_the_public_functions_have_the_signatures_of_the_issue():
     assert ops.RADIUS_TILE == macros(HEADER)["PS_RADIUS_TILE"] == R.TILE == 64
 
 
-# ---- the header and the library ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    build.build_graph(force=False, verbose=False)      # hipcc cross-compiles gfx950 without a GPU
-    return _graph.load()
-
-
-def exported(path):
-    nm = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return set(re.findall(r"\b(ps_[a-z0-9_]+)$", nm, flags=re.M))
-
-
-def test_header_is_c99():
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", os.path.join(INCLUDE, HEADER)], check=True)
-
-
-def test_header_binding_and_library_agree(lib):
-    declared = declared_symbols(HEADER)
-    assert declared == sorted(_graph.SIGNATURES) == ["ps_graph_api", "ps_radius_count_f32", "ps_radius_fill_f32",
-                                                     "ps_radius_tile_boxes_f32"]
-    assert sorted(exported(build.GRAPH_LIB_PATH)) == declared
-    assert lib.ps_graph_api() == macros(HEADER)["PS_GRAPH_API"] == _graph.EXPECTED_API
+# ---- the radius graph's own entry points and sources (what every family shares: tests/test_api_families.py) -------------------------
+def test_the_entry_points_and_their_arguments():
+    assert sorted(_lib.GRAPH_SIGNATURES) == ["ps_graph_api", "ps_radius_count_f32", "ps_radius_fill_f32",
+                                             "ps_radius_tile_boxes_f32"]
     for name in ("ps_radius_tile_boxes_f32", "ps_radius_count_f32", "ps_radius_fill_f32"):
-        restype, argtypes = _graph.SIGNATURES[name]
+        restype, argtypes = _lib.GRAPH_SIGNATURES[name]
         assert restype is ctypes.c_int and argtypes[-1] is ctypes.c_void_p                # the HIP error; the stream last
-    assert _graph.SIGNATURES["ps_radius_fill_f32"][1][9:11] == [ctypes.c_void_p, ctypes.c_longlong]   # row_ptr, max_edges
-    assert _graph.SIGNATURES["ps_radius_count_f32"][1][6] is ctypes.c_float
+    assert _lib.GRAPH_SIGNATURES["ps_radius_fill_f32"][1][9:11] == [ctypes.c_void_p, ctypes.c_longlong]   # row_ptr, max_edges
+    assert _lib.GRAPH_SIGNATURES["ps_radius_count_f32"][1][6] is ctypes.c_float
 
 
-def test_the_first_library_exports_what_it_did():
-    build.build(force=False, verbose=False)
+def test_the_library_exports_every_table_and_is_built_from_the_radius_sources():
+    build.build(force=False, verbose=False)      # hipcc cross-compiles gfx950 without a GPU
     tables = ["SIGNATURES"] + [family.signatures for family in _lib.FAMILIES]
-    bound = set().union(*(getattr(_lib, t) for t in tables))
-    names = exported(build.LIB_PATH)
-    assert names == bound and not names & set(_graph.SIGNATURES)
-    assert not [n for n in names if "radius" in n or "graph_api" in n]
-    assert not any("csrc_graph" in d or d.endswith(HEADER) for d in build._deps())
+    nm = subprocess.run(["nm", "-D", "--defined-only", build.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    assert set(re.findall(r"\b(ps_[a-z0-9_]+)$", nm, flags=re.M)) == set().union(*(getattr(_lib, t) for t in tables))
     assert all(os.path.dirname(s) == build.CSRC for s in build.sources())
-
-
-def test_the_graph_library_is_built_from_its_own_sources_and_the_shared_headers():
-    target = build._graph_library()
-    names = {os.path.basename(d) for d in target.inputs}
+    names = {os.path.basename(d) for d in build._deps()}
     assert {"radius_graph.hip", "radius_box.hpp", "ps_common.hpp", "owner_sweep.hpp", HEADER} <= names
-    cmd = target.command("out.so")
-    assert cmd[1:1 + len(build.FLAGS)] == build.FLAGS and "-I" + build.CSRC in cmd
-    assert [c for c in cmd if c.endswith(".hip")] == build.graph_sources()
-
-
-def test_a_library_with_another_version_is_refused(lib, monkeypatch):
-    monkeypatch.setattr(_graph, "_lib", None)
-    monkeypatch.setattr(_graph, "EXPECTED_API", _graph.EXPECTED_API + 1)
-    with pytest.raises(_lib.HipLibraryError) as info:
-        _graph.load()
-    assert str(info.value) == (f"{_graph.LIB_PATH} has radius-graph API version 1, this package binds version 2: "
-                               "rebuild with `python -m protstruc_amd.build --force`")
-
-
-def test_a_missing_library_is_refused(lib, monkeypatch, tmp_path):
-    monkeypatch.setattr(_graph, "_lib", None)
-    monkeypatch.setattr(_graph, "LIB_PATH", str(tmp_path / "libprotstruc_graph.so"))
-    with pytest.raises(_lib.HipLibraryError) as info:
-        _graph.load()
-    assert str(info.value) == (f"{tmp_path / 'libprotstruc_graph.so'} is missing: build it with `python -m protstruc_amd.build` "
-                               "(hipcc --offload-arch=gfx950). protstruc_amd has no CPU fallback.")

@@ -69,6 +69,7 @@ rows = [
     ("ops.backbone_hbonds", lambda: ops.backbone_hbonds(xg, pmask, junction)),
     ("ops.solvent_accessibility", lambda: ops.solvent_accessibility(pts, radius, pmask, sphere=sphere)),
     ("ops.nearest_neighbors (k = 16)", lambda: ops.nearest_neighbors(pts, 16, pmask)),
+    ("ops.radius_graph (10 A, max_edges given)", lambda: ops.radius_graph(pts, 10.0, pmask, max_edges=N * N)),
     ("ops.edge_rbf (k = 16, 2 pairs, 16 centres)", lambda: ops.edge_rbf(xg, nbr, mg, pair_i=[1, 0], pair_j=[1, 3], centers=centers, sigma=1.25)),
     ("ops.closest_atoms", lambda: ops.closest_atoms(xg, mg)),
     ("ops.binned_cross_entropy (64 bins)", lambda: ops.binned_cross_entropy(logits, bins)),

@@ -1,7 +1,7 @@
-// The box test of the radius graph on the host: protstruc_amd/csrc_graph/radius_box.hpp, the code the kernels run,
+// The box test of the radius graph on the host: protstruc_amd/csrc/radius_box.hpp, the code the kernels run,
 // compiled with a plain C++ compiler (tests/test_radius_host.py).
 //
-//   c++ -std=c++17 -O2 -ffp-contract=off -I protstruc_amd/csrc_graph tools/radius_box_host.cpp -o radius_box_host
+//   c++ -std=c++17 -O2 -ffp-contract=off -I protstruc_amd/csrc tools/radius_box_host.cpp -o radius_box_host
 //
 // stdin, one case per line, every float32 as the decimal of its bit pattern:
 //   cutoff nA nB   then 3 * nA coordinates of the queries, then 3 * nB coordinates of the candidates

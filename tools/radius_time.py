@@ -55,8 +55,8 @@ def launches(x, mask, key, cutoff):
     """The call of ops.radius_graph taken apart, on buffers made once: {name: a function that enqueues that part}, the
     number of edges, and the summed counters"""
     import torch
-    from protstruc_amd import _graph, ops
-    lib = _graph.load()
+    from protstruc_amd import _lib, ops
+    lib = _lib.load()
     batch, M = x.shape[:2]
     ptr = lambda t: None if t is None else t.data_ptr()                         # noqa: E731
     stream = torch.cuda.current_stream().cuda_stream

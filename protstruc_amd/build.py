@@ -1,4 +1,4 @@
-"""Build libprotstruc_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
+"""Build libprotstruc_hip.so (and the libraries beside it) for gfx950 with hipcc (cross-compiles without a GPU).
 
     python -m protstruc_amd.build [--force]
 
@@ -20,6 +20,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_hip.so")
 # the multi-GPU exchange step lives in its own library so that libprotstruc_hip.so has no RCCL dependency
 RCCL_SRC_DIR = os.path.join(HERE, "csrc_rccl")
 RCCL_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_rccl.so")
+# the edge features on CSR graphs (K49 - K51) are a library of their own, with a header and a version of their own:
+# include/protstruc_csredge.h
+CSREDGE_SRC_DIR = os.path.join(HERE, "csrc_csredge")
+CSREDGE_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_csredge.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ROCM_LIB = os.environ.get("ROCM_LIB", "/opt/rocm/lib")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"]
@@ -127,6 +131,28 @@ def build_rccl(force=False, verbose=True):
     return _rccl_library().build(force, verbose)
 
 
+def csredge_sources():
+    return sorted(glob.glob(os.path.join(CSREDGE_SRC_DIR, "*.hip")))
+
+
+def _csredge_library(out=None):
+    inputs = csredge_sources() + sorted(glob.glob(os.path.join(CSREDGE_SRC_DIR, "*.hpp"))) + \
+        sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "protstruc_csredge.h")]
+    return _Target(out or CSREDGE_LIB_PATH, b"csredge-lib " + " ".join(FLAGS).encode(), inputs,
+                   lambda tmp: [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp] + csredge_sources())
+
+
+def csredge_is_stale(path=None):
+    return _csredge_library(path).is_stale()
+
+
+def build_csredge(force=False, verbose=True):
+    """libprotstruc_csredge.so: csrc_csredge/*.hip, the edge features on CSR graphs (include/protstruc_csredge.h).  Compiled
+    with exactly FLAGS and -I csrc: the kernels share ps_common.hpp with libprotstruc_hip.so and its arithmetic contract
+    (-ffp-contract=off), and add no export to it."""
+    return _csredge_library().build(force, verbose)
+
+
 EXAMPLE_SRC = os.path.join(HERE, "..", "examples", "c_abi_demo.c")
 EXAMPLE_BIN = os.path.join(HERE, "..", "build", "c_abi_demo")
 
@@ -170,5 +196,6 @@ if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build(force=force))
     print(build_rccl(force=force))
+    print(build_csredge(force=force))
     print(build_c_example())
     print(build_arith_probe(force=force))

@@ -681,7 +681,9 @@ def radius_graph_edges(graph):
         b, i, j = radius_graph_edges(g)
         edge = (x[b, i] - x[b, j]).norm(dim=-1)      # (E,), equal to g.dist up to float32 rounding; grads reach x
 
-    For a graph made with ``max_edges`` below ``row_ptr[-1]`` the triples past the buffers have no ``col``: refused."""
+    For a graph made with ``max_edges`` below ``row_ptr[-1]`` the triples past the buffers have no ``col``: refused.
+    This function reads ``row_ptr[-1]`` on the host; ``radius_edge_rows`` gives ``batch`` and ``row`` for every position
+    of ``col`` without a host read and is the route that runs inside a captured graph."""
     row_ptr, col, count = graph.row_ptr, graph.col, graph.count
     B, Q = count.shape
     edges = int(row_ptr[-1])
@@ -753,6 +755,105 @@ def edge_frame_features(rot, trans, idx, frame_mask=None) -> EdgeFrames:
     Not differentiable: the outputs carry no graph.  The differentiable route stays ``gather_neighbors`` and plain torch."""
     args, finish = _marshal((("rot", rot), ("trans", trans), ("idx", idx), ("frame_mask", frame_mask)))
     return EdgeFrames(*finish(ops.edge_frames(**args)))
+
+
+# ---- the same edge features on the CSR lists of radius_graph -----------------------------------------------------------------
+def _graph_queries(graph) -> int:
+    """Q of a ``RadiusGraph``: the queries per structure, from ``count`` (B,Q)"""
+    if not isinstance(graph, RadiusGraph):
+        raise TypeError("graph must be a geometry.RadiusGraph (radius_graph, neighbors_to_radius_graph)")
+    if graph.count.ndim != 2:
+        raise ValueError(f"graph.count must have shape (batch, queries), got {tuple(graph.count.shape)}")
+    return int(graph.count.shape[1])
+
+
+def radius_edge_rows(graph):
+    """``(batch, row)``, each (E,) int32, of every edge position of a ``RadiusGraph``, E being ``graph.col.shape[0]``: the
+    structure and the query the entry ``col[p]`` belongs to, both -1 from position ``row_ptr[-1]`` on (the tail that
+    ``max_edges`` leaves).  With ``col`` these are the triples of ``radius_graph_edges``, found on the device (one HIP
+    kernel, ``ops.csr_edge_rows``) with no host read, so this runs inside ``torch.cuda.graph`` behind
+    ``radius_graph(..., max_edges=n)``.  numpy in -> numpy out; tensors come back on the device of ``graph.row_ptr``.
+
+    Not differentiable (indices)."""
+    Q = _graph_queries(graph)
+    args, finish = _marshal((("row_ptr", graph.row_ptr), ("col", graph.col)))
+    return finish(ops.csr_edge_rows(args["row_ptr"], Q, int(args["col"].shape[0])))
+
+
+def radius_edge_distance_features(xyz, graph, atom_mask=None, pairs=BACKBONE_PAIRS, centers=None, sigma=None, return_dist=False,
+                                  source_xyz=None, source_mask=None):
+    """``edge_distance_features`` along the edges of a ``RadiusGraph``: ``rbf`` (E, P*R) fp32 or, with ``return_dist``,
+    ``(rbf, dist)`` with ``dist`` (E, P), one row per entry of ``graph.col`` -- flat over the batch, lists of any length, no
+    padding to a ``k``.  ``xyz`` (B,M,A,3) are the residues ``col`` indexes (``atom_mask`` (B,M,A)); the sources, the rows
+    of the graph, are ``source_xyz`` (B,Q,As,3) with ``source_mask`` (B,Q,As) where the graph was made with ``queries``, and
+    the same residues otherwise.  ``pairs`` are (slot on the source, slot on the neighbour); ``centers`` / ``sigma`` default
+    to ``rbf_centers()``.  The values are ``edge_distance_features``' on the same edges, bit for bit; exactly 0 where
+    either atom is outside its mask and on every position that is no edge -- from ``row_ptr[-1]`` on, and wherever ``col``
+    is outside [0, M) -- and NaN there never reaches the result.  One HIP kernel (``ops.csr_edge_rbf``) that cuts its work
+    by edge position, so load balance does not depend on row lengths; nothing gathered or broadcast is built; no host
+    read.  For an atom graph pass the zero-copy view ``xyz.reshape(B, N*A, 1, 3)`` with ``pairs=((0, 0),)``.
+    numpy in -> numpy out; tensors come back on the device of ``xyz``, CPU tensors included.
+
+    Not differentiable: the outputs carry no graph.  ``radius_graph_edges`` and plain torch stay the differentiable route."""
+    if (centers is None) != (sigma is None):
+        raise ValueError("centers and sigma come together (rbf_centers() returns both)")
+    if centers is None:
+        centers, sigma = rbf_centers()
+    pairs = [tuple(p) for p in pairs]
+    if any(len(p) != 2 for p in pairs):
+        raise ValueError("pairs must be (slot on the source residue, slot on the neighbour) pairs")
+    _graph_queries(graph)
+    args, finish = _marshal((("xyz", xyz), ("row_ptr", graph.row_ptr), ("col", graph.col), ("atom_mask", atom_mask),
+                             ("src_xyz", source_xyz), ("src_mask", source_mask)))
+    dist, rbf = finish(ops.csr_edge_rbf(**args, pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers,
+                                        sigma=sigma, want_dist=bool(return_dist)))
+    return (rbf, dist) if return_dist else rbf
+
+
+def radius_edge_frame_features(rot, trans, graph, frame_mask=None, source_rot=None, source_trans=None,
+                               source_mask=None) -> EdgeFrames:
+    """``edge_frame_features`` along the edges of a ``RadiusGraph``: ``EdgeFrames(local_pos (E,3) = R_i^T (t_j - t_i), rel_rot
+    (E,3,3) = R_i^T R_j)``, one row per entry of ``graph.col``; i is the edge's source -- a frame of ``source_rot`` (B,Q,3,3),
+    ``source_trans`` (B,Q,3), ``source_mask`` (B,Q) where given, else of ``rot`` / ``trans`` / ``frame_mask`` like the
+    neighbour j.  ``edge_frame_features``' values on the same edges, bit for bit; exactly 0 where either frame is outside
+    its mask and on every position that is no edge.  One HIP kernel (``ops.csr_edge_frames``); no host read.
+    numpy in -> numpy out; tensors come back on the device of ``rot``, CPU tensors included.
+
+    Not differentiable: the outputs carry no graph."""
+    _graph_queries(graph)
+    args, finish = _marshal((("rot", rot), ("trans", trans), ("row_ptr", graph.row_ptr), ("col", graph.col),
+                             ("frame_mask", frame_mask), ("src_rot", source_rot), ("src_trans", source_trans),
+                             ("src_mask", source_mask)))
+    return EdgeFrames(*finish(ops.csr_edge_frames(**args)))
+
+
+def neighbors_to_radius_graph(neighbors_or_idx) -> RadiusGraph:
+    """A padded neighbour list -- ``Neighbors`` or its ``idx`` (B,Q,k) -- as CSR lists with the padding dropped:
+    ``RadiusGraph(row_ptr (B*Q+1,) int64, col (E,) int32, dist (E,) or None, count (B,Q) int32)``.  Every negative entry is
+    padding; the others keep their order within the row (nearest first for ``nearest_neighbors``, not ascending in j).
+    ``dist`` is ``Neighbors.dist`` at the entries kept, or None for a bare index tensor.  Gives a kNN graph the flat edge
+    list the ``radius_edge_*`` functions take.  Plain torch on the list's own device (mask, ``cumsum``,
+    ``masked_select``: the number of edges is read from the device); numpy in -> numpy out.  Not differentiable."""
+    idx, dist = (neighbors_or_idx.idx, neighbors_or_idx.dist) if isinstance(neighbors_or_idx, Neighbors) else (neighbors_or_idx, None)
+    arrays = isinstance(idx, np.ndarray)
+    idx = torch.from_numpy(np.ascontiguousarray(idx)) if arrays else idx
+    if not isinstance(idx, torch.Tensor):
+        raise TypeError("idx must be a tensor or an ndarray")
+    if idx.ndim != 3 or idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool:
+        raise ValueError(f"idx must be an integer tensor of shape (B, Q, k), got {idx.dtype} {tuple(idx.shape)}")
+    B, Q, _ = idx.shape
+    real = idx >= 0
+    count = real.sum(-1, dtype=torch.int32)
+    row_ptr = torch.zeros(B * Q + 1, dtype=torch.int64, device=idx.device)
+    torch.cumsum(count.reshape(-1), 0, dtype=torch.int64, out=row_ptr[1:])
+    col = torch.masked_select(idx, real).to(torch.int32)
+    if dist is not None:
+        dist = torch.from_numpy(np.ascontiguousarray(dist)) if isinstance(dist, np.ndarray) else dist
+        if tuple(dist.shape) != tuple(idx.shape):
+            raise ValueError(f"dist must have shape {tuple(idx.shape)} to match idx, got {tuple(dist.shape)}")
+        dist = torch.masked_select(dist.detach().to(idx.device), real)
+    out = (row_ptr, col, dist, count)
+    return RadiusGraph(*(t if t is None or not arrays else t.numpy() for t in out))
 
 
 class SideChainTorsions(NamedTuple):

@@ -16,7 +16,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _csredge, _lib
 
 
 RNG_STATE_WORDS = 528  # PS_RNG_STATE_WORDS of include/protstruc_hip.h
@@ -2381,7 +2381,218 @@ def edge_frames(rot: torch.Tensor, trans: torch.Tensor, idx: torch.Tensor, frame
     return pos, rel
 
 
-CHI_MAX_TYPES = 32   # PS_CHI_MAX_TYPES of include/protstruc_hip.h: the tables travel in the kernel's arguments
+CSREDGE_CHUNK = 64   # PS_CSREDGE_CHUNK of include/protstruc_csredge.h
+CSREDGE_MAX_PAIRS = 64   # PS_CSREDGE_MAX_PAIRS: a chunk's 64 * P distances live in LDS
+CSREDGE_MAX_RBF = 64   # PS_CSREDGE_MAX_RBF: the centres travel in the kernel's arguments
+
+
+def _launch_csredge(name: str, *args) -> None:
+    """Call entry point ``name`` of libprotstruc_csredge.so; HipLibraryError if it does not return hipSuccess."""
+    rc = getattr(_csredge.load(), name)(*args)
+    if rc:
+        _csredge.check(rc, name)
+
+
+def _check_csr_graph(row_ptr, col, B: int, Q: int, like: str) -> int:
+    """E, the length of the edge buffers of the CSR lists ``row_ptr`` (B*Q+1,), ``col`` (E,) over the B x Q sources of
+    ``like``; ValueError otherwise."""
+    if tuple(row_ptr.shape) != (B * Q + 1,):
+        raise ValueError(f"row_ptr must have shape ({B * Q + 1},) to match the {B} x {Q} sources of {like}, "
+                         f"got {tuple(row_ptr.shape)}")
+    if not _is_integer_tensor(row_ptr):
+        raise ValueError(f"row_ptr must be an integer tensor, got {row_ptr.dtype}")
+    if col.ndim != 1:
+        raise ValueError(f"col must have shape (edges,), got {tuple(col.shape)}")
+    if not _is_integer_tensor(col):
+        raise ValueError(f"col must be an integer tensor, got {col.dtype}")
+    return col.shape[0]
+
+
+def _row_ptr64(row_ptr: torch.Tensor) -> torch.Tensor:
+    _require_device(row_ptr, "row_ptr")
+    return (row_ptr if row_ptr.dtype == torch.int64 else row_ptr.to(torch.int64)).contiguous()
+
+
+def _col32(col: torch.Tensor, M: int) -> torch.Tensor:
+    """``col`` as contiguous int32 for the CSR edge kernels, to which every value outside [0, M) is padding: wider integers
+    are clamped to [-1, M] first, so that none wraps into the range."""
+    _require_device(col, "col")
+    if col.dtype != torch.int32:
+        col = col.clamp(-1, M).to(torch.int32)
+    return col.contiguous()
+
+
+def check_csr_edge_rows_shapes(row_ptr, Q, E) -> int:
+    """Shape rules of ``csr_edge_rows`` (no launch): ValueError; returns B.  ``row_ptr`` (B*Q+1,) integers; ``Q`` an integer
+    in 0 .. 2^24 that divides the number of rows; ``E`` a non-negative integer."""
+    for name, value in (("Q", Q), ("E", E)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
+    _check_count(int(Q), 0, 2 ** 24, "queries per structure")
+    if row_ptr.ndim != 1 or row_ptr.shape[0] < 1:
+        raise ValueError(f"row_ptr must have shape (rows + 1,), got {tuple(row_ptr.shape)}")
+    if not _is_integer_tensor(row_ptr):
+        raise ValueError(f"row_ptr must be an integer tensor, got {row_ptr.dtype}")
+    rows = row_ptr.shape[0] - 1
+    if rows % Q if Q else rows:
+        raise ValueError(f"row_ptr holds {rows} rows, no multiple of Q = {Q}")
+    B = rows // Q if Q else 0
+    _check_batch(B)
+    return B
+
+
+def csr_edge_rows(row_ptr: torch.Tensor, Q: int, E: int):
+    """K49.  ``(batch (E,) int32, row (E,) int32)``: the structure and the query of every edge position of CSR lists
+    ``row_ptr`` (B*Q+1,) whose edge buffers hold ``E`` entries -- ``col.shape[0]``, not ``row_ptr[-1]`` --, both -1 at the
+    positions from ``row_ptr[-1]`` on.  Position p belongs to the row r with ``row_ptr[r] <= p < row_ptr[r + 1]``, found on
+    the device by bisection: the triples of ``geometry.radius_graph_edges`` without its host read, so it runs inside a
+    captured graph (include/protstruc_csredge.h)."""
+    check_csr_edge_rows_shapes(row_ptr, Q, E)
+    rp = _row_ptr64(row_ptr)
+    Q, E = int(Q), int(E)
+    with _on(rp.device):
+        if not E:   # nothing to launch (an empty tensor has no device pointer)
+            return (torch.empty(0, dtype=torch.int32, device=rp.device), torch.empty(0, dtype=torch.int32, device=rp.device))
+        batch = torch.empty(E, dtype=torch.int32, device=rp.device)   # the kernel writes every element
+        row = torch.empty(E, dtype=torch.int32, device=rp.device)
+        _launch_csredge("ps_csr_edge_rows_i32", _ptr(rp), rp.shape[0] - 1, Q, E, _ptr(batch), _ptr(row), _stream(rp))
+    return batch, row
+
+
+def check_csr_edge_rbf_shapes(xyz, row_ptr, col, atom_mask=None, pair_i=(), pair_j=(), centers=(), sigma=1.0, src_xyz=None,
+                              src_mask=None, want_dist=True, want_rbf=True) -> Tuple[int, int, int, int, int, int]:
+    """Shape rules of ``csr_edge_rbf``, on shapes, dtypes, devices, the host tables and the scalar only (no launch):
+    ValueError; returns (B, M, A, Q, As, E).  ``xyz`` (B,M,A,3) the targets; ``src_xyz`` (B,Q,As,3) the sources or None,
+    the targets, which takes no ``src_mask``; ``row_ptr`` (B*Q+1,) and ``col`` (E,) integers; ``pair_i`` slots in [0, As),
+    ``pair_j`` in [0, A), equally long, 1 .. ``CSREDGE_MAX_PAIRS``; 1 .. ``CSREDGE_MAX_RBF`` ``centers``; ``sigma`` positive
+    and finite; one of the two outputs wanted."""
+    B, M, A = _xyz_dims(xyz)
+    _check_batch(B)
+    _check_count(M, 0, 2 ** 24, "residues per structure")
+    _check_optional(atom_mask, (B, M, A), "atom_mask", "xyz", (B, M, A, 3))
+    Q, As = M, A
+    if src_xyz is None:
+        if src_mask is not None:
+            raise ValueError("src_mask needs src_xyz: where the sources are the targets, atom_mask is used")
+    else:
+        shape = tuple(src_xyz.shape)
+        if len(shape) != 4 or shape[3] != 3 or shape[0] != B:
+            raise ValueError(f"src_xyz must have shape ({B}, queries, atoms, 3) to match xyz {(B, M, A, 3)}, got {shape}")
+        if not src_xyz.dtype.is_floating_point:
+            raise ValueError(f"src_xyz must be a floating-point tensor, got {src_xyz.dtype}")
+        Q, As = shape[1:3]
+        _check_count(Q, 0, 2 ** 24, "queries per structure")
+        _check_optional(src_mask, (B, Q, As), "src_mask", "src_xyz", shape)
+    E = _check_csr_graph(row_ptr, col, B, Q, f"xyz {(B, M, A, 3)}" if src_xyz is None else f"src_xyz {tuple(src_xyz.shape)}")
+    try:
+        slots_i, slots_j = [int(s) for s in pair_i], [int(s) for s in pair_j]
+    except (TypeError, ValueError):
+        raise ValueError("pair_i and pair_j must be sequences of atom slots") from None
+    if len(slots_i) != len(slots_j) or not 1 <= len(slots_i) <= CSREDGE_MAX_PAIRS:
+        raise ValueError(f"pair_i and pair_j must be equally long, 1 .. {CSREDGE_MAX_PAIRS} atom slots each, got "
+                         f"{len(slots_i)} and {len(slots_j)}")
+    _check_atom_slots(As, *slots_i)
+    _check_atom_slots(A, *slots_j)
+    R = _host_f32(centers, "centers").shape[0]
+    if not 1 <= R <= CSREDGE_MAX_RBF:
+        raise ValueError(f"centers must hold 1 .. {CSREDGE_MAX_RBF} values, got {R}")
+    _check_scalar(sigma, "sigma", "positive")
+    if not (want_dist or want_rbf):
+        raise ValueError("nothing to compute: want_dist and want_rbf are both False")
+    _same_device(xyz, row_ptr=row_ptr, col=col, atom_mask=atom_mask, src_xyz=src_xyz, src_mask=src_mask)
+    return B, M, A, Q, As, E
+
+
+def csr_edge_rbf(xyz: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor, atom_mask: Optional[torch.Tensor] = None, *,
+                 pair_i: Sequence[int], pair_j: Sequence[int], centers, sigma: float, src_xyz: Optional[torch.Tensor] = None,
+                 src_mask: Optional[torch.Tensor] = None, want_dist: bool = True, want_rbf: bool = True):
+    """K50.  ``edge_rbf`` on CSR lists of any length: ``(dist (E,P) fp32, rbf (E,P*R) fp32)``, None for an output not wanted,
+    one row per edge position.  ``xyz`` (B,M,A,3) are the targets, what ``col`` (E,) indexes; ``src_xyz`` (B,Q,As,3) the
+    sources, the rows of ``row_ptr`` (B*Q+1,) -- None: the targets themselves (Q = M), with ``atom_mask`` for both.  Pair p is
+    slot ``pair_i[p]`` of the source against slot ``pair_j[p]`` of the target.  The arithmetic is ``edge_rbf``'s, and on
+    the same edge so are the bits.  A position is padding from ``row_ptr[-1]`` on and where ``col`` is outside [0, M):
+    exactly 0, like a pair with an atom outside its mask, and nothing is read there.  E is ``col.shape[0]``; lists cut by
+    ``max_edges`` are served for the positions that exist.  No host read, so capturable; every element is written;
+    deterministic (include/protstruc_csredge.h)."""
+    B, M, A, Q, As, E = check_csr_edge_rbf_shapes(xyz, row_ptr, col, atom_mask, pair_i, pair_j, centers, sigma, src_xyz, src_mask,
+                                                  want_dist, want_rbf)
+    x, am = _f32c(xyz, "xyz"), _u8c(atom_mask, "atom_mask")
+    sx, sm = _f32c_opt(src_xyz, "src_xyz"), _u8c(src_mask, "src_mask")
+    rp, cl = _row_ptr64(row_ptr), _col32(col, M)
+    cen = _host_f32(centers, "centers")
+    P, R = len(pair_i), cen.shape[0]
+    ints = ctypes.c_int * P
+    with _on(x.device):
+        if not (B and E and M and Q):   # nothing to launch (an empty tensor has no device pointer): all padding
+            return (torch.zeros(E, P, dtype=torch.float32, device=x.device) if want_dist else None,
+                    torch.zeros(E, P * R, dtype=torch.float32, device=x.device) if want_rbf else None)
+        dist = torch.empty(E, P, dtype=torch.float32, device=x.device) if want_dist else None   # every element is written
+        rbf = torch.empty(E, P * R, dtype=torch.float32, device=x.device) if want_rbf else None
+        _launch_csredge("ps_csr_edge_rbf_f32", _ptr(x), _ptr(am), _ptr(sx), _ptr(sm), _ptr(rp), _ptr(cl), E,
+                        ints(*(int(s) for s in pair_i)), ints(*(int(s) for s in pair_j)), P, (ctypes.c_float * R)(*cen.tolist()),
+                        R, float(sigma), _ptr(dist), _ptr(rbf), B, M, A, Q, As, _stream(x))
+    return dist, rbf
+
+
+def check_csr_edge_frames_shapes(rot, trans, row_ptr, col, frame_mask=None, src_rot=None, src_trans=None, src_mask=None,
+                                 want_pos=True, want_rot=True) -> Tuple[int, int, int, int]:
+    """Shape rules of ``csr_edge_frames``, on shapes, dtypes and devices only (no launch): ValueError; returns (B, M, Q, E)."""
+    shape = _float_dims(rot, "rot", "batch, frames, 3, 3", tail=(3, 3))
+    B, M = shape[:2]
+    _check_batch(B)
+    _check_count(M, 0, 2 ** 24, "frames per structure")
+    _check_float_tensor(trans, (B, M, 3), "trans", f"rot {shape}")
+    _check_optional(frame_mask, (B, M), "frame_mask", "rot", shape)
+    Q = M
+    if (src_rot is None) != (src_trans is None):
+        raise ValueError("src_rot and src_trans come together: the sources' frames")
+    if src_rot is None:
+        if src_mask is not None:
+            raise ValueError("src_mask needs src_rot and src_trans: where the sources are the targets, frame_mask is used")
+    else:
+        src_shape = tuple(src_rot.shape)
+        if len(src_shape) != 4 or src_shape[2:] != (3, 3) or src_shape[0] != B:
+            raise ValueError(f"src_rot must have shape ({B}, queries, 3, 3) to match rot {shape}, got {src_shape}")
+        if not src_rot.dtype.is_floating_point:
+            raise ValueError(f"src_rot must be a floating-point tensor, got {src_rot.dtype}")
+        Q = src_shape[1]
+        _check_count(Q, 0, 2 ** 24, "queries per structure")
+        _check_float_tensor(src_trans, (B, Q, 3), "src_trans", f"src_rot {src_shape}")
+        _check_optional(src_mask, (B, Q), "src_mask", "src_rot", src_shape)
+    E = _check_csr_graph(row_ptr, col, B, Q, f"rot {shape}" if src_rot is None else f"src_rot {tuple(src_rot.shape)}")
+    if not (want_pos or want_rot):
+        raise ValueError("nothing to compute: want_pos and want_rot are both False")
+    _same_device(rot, trans=trans, row_ptr=row_ptr, col=col, frame_mask=frame_mask, src_rot=src_rot, src_trans=src_trans,
+                 src_mask=src_mask)
+    return B, M, Q, E
+
+
+def csr_edge_frames(rot: torch.Tensor, trans: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor,
+                    frame_mask: Optional[torch.Tensor] = None, *, src_rot: Optional[torch.Tensor] = None,
+                    src_trans: Optional[torch.Tensor] = None, src_mask: Optional[torch.Tensor] = None, want_pos: bool = True,
+                    want_rot: bool = True):
+    """K51.  ``edge_frames`` on CSR lists of any length: ``(local_pos (E,3), rel_rot (E,3,3))`` fp32, None for an output not
+    wanted.  ``rot`` (B,M,3,3), ``trans`` (B,M,3) and ``frame_mask`` (B,M) are the targets' frames, what ``col`` indexes;
+    ``src_rot`` (B,Q,3,3), ``src_trans`` (B,Q,3), ``src_mask`` (B,Q) the sources', the rows of ``row_ptr`` -- None: the
+    targets themselves.  ``edge_frames``' formulas and, on the same edge, its bits; exactly 0 at the padding (from
+    ``row_ptr[-1]`` on, and where ``col`` is outside [0, M)) and where either frame is outside its mask.  No host read;
+    every element is written; deterministic (include/protstruc_csredge.h)."""
+    B, M, Q, E = check_csr_edge_frames_shapes(rot, trans, row_ptr, col, frame_mask, src_rot, src_trans, src_mask, want_pos, want_rot)
+    r, t, fm = _f32c(rot, "rot"), _f32c(trans, "trans"), _u8c(frame_mask, "frame_mask")
+    sr, st, sm = _f32c_opt(src_rot, "src_rot"), _f32c_opt(src_trans, "src_trans"), _u8c(src_mask, "src_mask")
+    rp, cl = _row_ptr64(row_ptr), _col32(col, M)
+    with _on(r.device):
+        if not (B and E and M and Q):   # nothing to launch: all padding
+            return (torch.zeros(E, 3, dtype=torch.float32, device=r.device) if want_pos else None,
+                    torch.zeros(E, 3, 3, dtype=torch.float32, device=r.device) if want_rot else None)
+        pos = torch.empty(E, 3, dtype=torch.float32, device=r.device) if want_pos else None
+        rel = torch.empty(E, 3, 3, dtype=torch.float32, device=r.device) if want_rot else None
+        _launch_csredge("ps_csr_edge_frames_f32", _ptr(r), _ptr(t), _ptr(fm), _ptr(sr), _ptr(st), _ptr(sm), _ptr(rp), _ptr(cl), E,
+                        _ptr(pos), _ptr(rel), B, M, Q, _stream(r))
+    return pos, rel
+
+
+CHI_MAX_TYPES = 32  # PS_CHI_MAX_TYPES of include/protstruc_hip.h: the tables travel in the kernel's arguments
 
 
 def _host_i32_table(values, shape_tail, name: str) -> np.ndarray:

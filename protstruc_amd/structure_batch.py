@@ -47,6 +47,28 @@ class EdgeFeatures(NamedTuple):
     rel_rot: Optional[torch.Tensor]     # (B,N,k,3,3) fp32: the neighbour's frame in the source residue's frame, or None
 
 
+class RadiusEdgeFeatures(NamedTuple):
+    """The edge features of a radius graph (``StructureBatch.edge_features(graph=radius_graph(...))``), flat over the E
+    entries of the graph's ``col``."""
+    batch: torch.Tensor                 # (E,) int32: the structure of every edge; -1 past the last edge
+    row: torch.Tensor                   # (E,) int32: its source residue; -1 past the last edge
+    col: torch.Tensor                   # (E,) int32: its neighbour, an index into the N axis of structure ``batch``
+    mask: torch.Tensor                  # (E,) bool: batch >= 0
+    rbf: torch.Tensor                   # (E,P*n_rbf) fp32: radial basis functions of the atom-pair distances
+    offset: torch.Tensor                # (E,) int64: the class of the sequence offset
+    local_pos: Optional[torch.Tensor]   # (E,3) fp32: the neighbour's CA in the source residue's frame, or None
+    rel_rot: Optional[torch.Tensor]     # (E,3,3) fp32: the neighbour's frame in the source residue's frame, or None
+
+
+class AtomEdgeFeatures(NamedTuple):
+    """The edge features of an atom radius graph (``StructureBatch.atom_edge_features``), flat over the E entries of ``col``."""
+    batch: torch.Tensor   # (E,) int32: the structure of every edge; -1 past the last edge
+    atom: torch.Tensor    # (E,) int32: its source atom, an index into the flattened N*A atom axis; -1 past the last edge
+    col: torch.Tensor     # (E,) int32: its neighbour, likewise
+    mask: torch.Tensor    # (E,) bool: batch >= 0
+    rbf: torch.Tensor     # (E,n_rbf) fp32: radial basis functions of the distance
+
+
 class StructuralAlignment(NamedTuple):
     """``geometry.StructureAlignment`` with the sequence identity of the aligned pairs (``StructureBatch.structural_alignment``)."""
     map: torch.Tensor            # (B,N) int32: the residue of the target aligned to a residue of this batch, or -1
@@ -983,8 +1005,73 @@ class StructureBatch:
         offset = torch.where(within, offset, torch.full_like(offset, 2 * max_offset + 1))
         return offset.masked_fill(idx < 0, 0)
 
+    def _flat_edge_offsets(self, batch: torch.Tensor, row: torch.Tensor, col: torch.Tensor, max_offset: int) -> torch.Tensor:
+        """(E,) int64: the classes of :meth:`_edge_offsets` for the flat edges (batch, row, col) of a radius graph, 0 where
+        ``batch`` is negative or ``col`` outside [0, N).  Plain torch, no host read."""
+        B, N = self.xyz.shape[:2]
+        if not (B and N and batch.shape[0]):
+            return torch.zeros(batch.shape[0], dtype=torch.int64, device=batch.device)
+        if self.residue_idx is None:
+            r = torch.arange(N, device=self.device).expand(B, N)
+        else:   # the padding's NaN becomes 0; padded residues are nobody's neighbour
+            r = torch.nan_to_num(_always_tensor(self.residue_idx).to(self.device, torch.float64), nan=0.0).long()
+        chain = self._chain_keys()
+        real = (batch >= 0) & (col >= 0) & (col < N)
+        b, i, j = batch.clamp(min=0).long(), row.clamp(min=0).long(), col.clamp(0, N - 1).long()
+        offset = (r[b, i] - r[b, j] + max_offset).clamp(0, 2 * max_offset)
+        offset = torch.where(chain[b, i] == chain[b, j], offset, torch.full_like(offset, 2 * max_offset + 1))
+        return offset.masked_fill(~real, 0)
+
+    def _radius_edge_features(self, graph, slots, n_rbf, d_min, d_max, frames, max_offset) -> RadiusEdgeFeatures:
+        """:meth:`edge_features` on a ``geometry.RadiusGraph`` over the residues: K49 - K51 and the offsets, no host read."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        if tuple(graph.count.shape) != (B, N):
+            raise ValueError(f"graph.count must have shape {(B, N)}, the residues of this batch, got {tuple(graph.count.shape)}")
+        graph = geometry.RadiusGraph(*(None if t is None else _always_tensor(t).to(self.device) for t in graph))
+        centers, sigma = geometry.rbf_centers(n_rbf, d_min, d_max)
+        present = self._present_atoms()
+        with torch.no_grad():
+            batch, row = geometry.radius_edge_rows(graph)
+            rbf = geometry.radius_edge_distance_features(self.xyz, graph, present, pairs=[(a, b) for a in slots for b in slots],
+                                                         centers=centers, sigma=sigma)
+            local_pos = rel_rot = None
+            if frames:
+                if A < 3:
+                    raise ValueError(f"frames need the N, CA and C slots; this batch has {A} atom slots")
+                rot, trans = self.backbone_orientations_and_translations()
+                local_pos, rel_rot = geometry.radius_edge_frame_features(rot, trans, graph, present[:, :, :3].all(dim=-1))
+            col = graph.col if graph.col.dtype == torch.int32 else graph.col.clamp(-1, N).to(torch.int32)
+            offset = self._flat_edge_offsets(batch, row, col, int(max_offset))
+        return RadiusEdgeFeatures(batch, row, col, batch >= 0, rbf, offset, local_pos, rel_rot)
+
+    def atom_edge_features(self, graph, n_rbf: int = 16, d_min: float = 0.0, d_max: float = 8.0) -> AtomEdgeFeatures:
+        """The edge features of an atom graph of :meth:`atom_radius_graph`: ``AtomEdgeFeatures(batch, atom, col, mask, rbf)``,
+        flat over the E entries of ``graph.col``.  ``batch`` and ``atom`` (E,) int32 are the structure and the source atom
+        of every edge -- ``atom`` and ``col`` index the flattened N*A atom axis, ``// A`` the residue and ``% A`` the slot
+        --, -1 from position ``row_ptr[-1]`` on; ``mask`` is ``batch >= 0``.  ``rbf`` (E, n_rbf): ``n_rbf`` Gaussians
+        (``geometry.rbf_centers(n_rbf, d_min, d_max)``) of the distance between the two atoms, exactly 0 where ``mask`` is
+        False.  Two HIP kernels over the zero-copy (B, N*A, 1, 3) view of the coordinates
+        (``geometry.radius_edge_rows``, ``.radius_edge_distance_features``); with a ``max_edges`` graph no host read.  Not
+        differentiable."""
+        from . import geometry
+
+        B, N, A = self.xyz.shape[:3]
+        if not isinstance(graph, geometry.RadiusGraph) or tuple(graph.count.shape) != (B, N * A):
+            raise ValueError(f"graph must be a geometry.RadiusGraph over the {(B, N * A)} atoms of this batch (atom_radius_graph)")
+        graph = geometry.RadiusGraph(*(None if t is None else _always_tensor(t).to(self.device) for t in graph))
+        centers, sigma = geometry.rbf_centers(n_rbf, d_min, d_max)
+        with torch.no_grad():
+            batch, atom = geometry.radius_edge_rows(graph)
+            rbf = geometry.radius_edge_distance_features(self.xyz.reshape(B, N * A, 1, 3), graph,
+                                                         self._present_atoms().reshape(B, N * A, 1), pairs=((0, 0),),
+                                                         centers=centers, sigma=sigma)
+        col = graph.col if graph.col.dtype == torch.int32 else graph.col.clamp(-1, N * A).to(torch.int32)
+        return AtomEdgeFeatures(batch, atom, col, batch >= 0, rbf)
+
     def edge_features(self, graph=None, k: int = 30, atoms=("N", "CA", "C", "O", "CB"), n_rbf: int = 16, d_min: float = 2.0,
-                      d_max: float = 22.0, frames: bool = True, max_offset: int = 32) -> EdgeFeatures:
+                      d_max: float = 22.0, frames: bool = True, max_offset: int = 32):
         """What a structure network computes on every edge of a neighbour graph, between :meth:`knn_graph` and its first
         linear layer (ProteinMPNN, Structured Transformer, GVP, PiFold): ``EdgeFeatures(idx, mask, rbf, offset, local_pos,
         rel_rot)``.
@@ -1001,7 +1088,17 @@ class StructureBatch:
         neighbour's CA and N-CA-C frame in the source residue's frame, ``R_i^T (t_j - t_i)`` and ``R_i^T R_j``, zero
         where either residue lacks N, CA or C; otherwise both are None.  Two HIP kernels
         (``geometry.edge_distance_features``, ``.edge_frame_features``); the offsets are plain torch.  Not differentiable
-        -- ``geometry.gather_neighbors`` is the differentiable route."""
+        -- ``geometry.gather_neighbors`` is the differentiable route.
+
+        ``graph`` may also be a ``geometry.RadiusGraph`` over the residues (:meth:`radius_graph`): lists of any length.
+        The result is then ``RadiusEdgeFeatures(batch, row, col, mask, rbf, offset, local_pos, rel_rot)``, the same
+        features flat over the E entries of ``graph.col`` -- ``rbf`` (E,P*n_rbf), ``offset`` (E,), ``local_pos`` (E,3),
+        ``rel_rot`` (E,3,3) -- with ``batch`` and ``row`` (E,) int32 the structure and the source residue of every edge and
+        ``mask = batch >= 0``; everything is 0 (``batch`` and ``row`` -1) from position ``row_ptr[-1]`` on.  ``col`` indexes
+        the N axis of the edge's own structure: with ``batch`` and ``row`` it is the edge list, not a flat
+        ``edge_index`` over a concatenated batch.  Three HIP kernels (``geometry.radius_edge_rows``,
+        ``.radius_edge_distance_features``, ``.radius_edge_frame_features``); with a graph made by
+        ``radius_graph(max_edges=n)`` the whole call makes no host read and runs inside ``torch.cuda.graph``."""
         from . import geometry
 
         if isinstance(max_offset, bool) or not isinstance(max_offset, (int, np.integer)) or max_offset < 0:
@@ -1013,6 +1110,8 @@ class StructureBatch:
         A, N = self.max_n_atoms_per_residue, self.n_residues
         if not slots or max(slots) >= A:
             raise ValueError(f"atoms {tuple(atoms)} do not fit the {A} atom slots of this batch")
+        if isinstance(graph, geometry.RadiusGraph):
+            return self._radius_edge_features(graph, slots, n_rbf, d_min, d_max, frames, max_offset)
         if graph is None:
             graph = self.knn_graph(k)
         idx = _always_tensor(graph.idx if isinstance(graph, geometry.Neighbors) else graph).to(self.device)

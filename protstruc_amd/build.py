@@ -24,6 +24,9 @@ RCCL_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_rccl.so")
 # include/protstruc_csredge.h
 CSREDGE_SRC_DIR = os.path.join(HERE, "csrc_csredge")
 CSREDGE_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_csredge.so")
+# the backward kernels of the edge features (K52 - K54), likewise: include/protstruc_edgegrad.h
+EDGEGRAD_SRC_DIR = os.path.join(HERE, "csrc_edgegrad")
+EDGEGRAD_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_edgegrad.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ROCM_LIB = os.environ.get("ROCM_LIB", "/opt/rocm/lib")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"]
@@ -153,6 +156,28 @@ def build_csredge(force=False, verbose=True):
     return _csredge_library().build(force, verbose)
 
 
+def edgegrad_sources():
+    return sorted(glob.glob(os.path.join(EDGEGRAD_SRC_DIR, "*.hip")))
+
+
+def _edgegrad_library(out=None):
+    inputs = edgegrad_sources() + sorted(glob.glob(os.path.join(EDGEGRAD_SRC_DIR, "*.hpp"))) + \
+        sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "protstruc_edgegrad.h")]
+    return _Target(out or EDGEGRAD_LIB_PATH, b"edgegrad-lib " + " ".join(FLAGS).encode(), inputs,
+                   lambda tmp: [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp] + edgegrad_sources())
+
+
+def edgegrad_is_stale(path=None):
+    return _edgegrad_library(path).is_stale()
+
+
+def build_edgegrad(force=False, verbose=True):
+    """libprotstruc_edgegrad.so: csrc_edgegrad/*.hip, the backward kernels of the edge features
+    (include/protstruc_edgegrad.h).  Compiled with exactly FLAGS and -I csrc, like libprotstruc_csredge.so, and for the same
+    reason: it shares ps_common.hpp and -ffp-contract=off with the forward kernels, and adds no export to them."""
+    return _edgegrad_library().build(force, verbose)
+
+
 EXAMPLE_SRC = os.path.join(HERE, "..", "examples", "c_abi_demo.c")
 EXAMPLE_BIN = os.path.join(HERE, "..", "build", "c_abi_demo")
 
@@ -197,5 +222,6 @@ if __name__ == "__main__":
     print(build(force=force))
     print(build_rccl(force=force))
     print(build_csredge(force=force))
+    print(build_edgegrad(force=force))
     print(build_c_example())
     print(build_arith_probe(force=force))

@@ -17,7 +17,9 @@ hard (the metric) and smooth (differentiable; ``ops.lddt`` / ``ops.lddt_backward
 ``nearest_neighbors`` is the k-nearest-neighbour graph (``ops.nearest_neighbors``) and ``gather_neighbors`` the gather
 that turns its indices into edge features; ``radius_graph`` is every neighbour within a cutoff as CSR lists
 (``ops.radius_graph``) and ``radius_graph_edges`` their (batch, row, col) triples; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
-features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``); ``side_chain_torsions``
+features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``), differentiable in the
+coordinates and the frames (``ops.csr_edge_rbf_backward``, ``.csr_edge_pair_grad_sum``, ``.csr_edge_frames_backward``), and
+``radius_graph_incoming`` groups a graph's edges by their target; ``side_chain_torsions``
 measures chi1 .. chi4, differentiably in the coordinates, and ``set_side_chain_torsions`` turns the side chains to given
 angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards); ``superposition_rmsd`` is the
 RMSD after optimal superposition, differentiable in both point sets (``ops.superpose`` / ``ops.superpose_backward``), and
@@ -709,6 +711,105 @@ def rbf_centers(n_rbf: int = 16, d_min: float = 2.0, d_max: float = 22.0):
     return centers, (float(d_max) - float(d_min)) / int(n_rbf)
 
 
+def _wants_grad(*tensors) -> bool:
+    """whether a graph is to be built: grad mode is on and one of ``tensors`` is a floating tensor that requires grad"""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.is_floating_point() and t.requires_grad
+                                           for t in tensors)
+
+
+def _attached(prepared: dict, **given) -> dict:
+    """``prepared`` (the detached tensors of ``_marshal``, on the kernels' device) with those of ``given`` that require grad
+    put back attached to their graph"""
+    for name, t in given.items():
+        if isinstance(t, torch.Tensor) and t.is_floating_point() and t.requires_grad:
+            prepared[name] = t.to(prepared[name].device)
+    return prepared
+
+
+def _csr_lists(first, col, B: int, N: int):
+    """``(row_ptr, col)`` of the edge lists a function was called with: CSR lists ``(row_ptr, col)`` as they are, a padded
+    (B,N,k) list ``(idx, None)`` as the CSR lists it is -- ``arange(B*N + 1) * k`` and the flattened indices"""
+    if col is not None:
+        return first, col
+    idx = ops._idx32(first, N)
+    return torch.arange(B * N + 1, dtype=torch.int64, device=idx.device) * idx.shape[2], idx.reshape(-1)
+
+
+def _flat_grad(g, E: int):
+    """an incoming gradient as a contiguous (E, ...) tensor; ``x.sum().backward()`` hands in one of stride 0"""
+    return None if g is None else g.contiguous().reshape(E, -1)
+
+
+class _EdgeDistanceFeatures(torch.autograd.Function):
+    """ops.edge_rbf (K25) or ops.csr_edge_rbf (K50) with K52 and K53 as their vector-Jacobian product.  The lists are
+    ``(idx, None)`` or ``(row_ptr, col)``; ``tables`` the keywords pair_i, pair_j, centers and sigma.  Lists and masks are
+    saved like the coordinates, so that changing one in place before the backward pass is noticed."""
+
+    @staticmethod
+    def forward(ctx, xyz, src_xyz, first, col, atom_mask, src_mask, tables, want_dist):
+        if col is None:
+            dist, rbf = ops.edge_rbf(xyz, first, atom_mask, want_dist=want_dist, **tables)
+        else:
+            dist, rbf = ops.csr_edge_rbf(xyz, first, col, atom_mask, src_xyz=src_xyz, src_mask=src_mask, want_dist=want_dist,
+                                         **tables)
+        ctx.tables = tables
+        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None: K52 takes a NULL for it
+        ctx.save_for_backward(xyz, src_xyz, first, col, atom_mask, src_mask)
+        return rbf, dist
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_rbf, grad_dist):
+        xyz, src_xyz, first, col, atom_mask, src_mask = ctx.saved_tensors
+        if grad_rbf is None and grad_dist is None:
+            return (None,) * 8
+        B, M, A = xyz.shape[:3]
+        row_ptr, col = _csr_lists(first, col, B, M)
+        E = col.shape[0]
+        pair_grad = ops.csr_edge_rbf_backward(xyz, row_ptr, col, atom_mask, src_xyz=src_xyz, src_mask=src_mask,
+                                              grad_dist=_flat_grad(grad_dist, E), grad_rbf=_flat_grad(grad_rbf, E), **ctx.tables)
+        Q, As = (None, None) if src_xyz is None else src_xyz.shape[1:3]
+        in_ptr, in_edge = ops.csr_incoming_edges(row_ptr, col, B, M if Q is None else Q, M)
+        out = ops.csr_edge_pair_grad_sum(pair_grad, row_ptr, in_ptr, in_edge, pair_i=ctx.tables["pair_i"],
+                                         pair_j=ctx.tables["pair_j"], B=B, M=M, A=A, Q=Q, As=As)
+        grad, grad_src = (out, None) if src_xyz is None else out
+        return (grad.to(xyz.dtype) if ctx.needs_input_grad[0] else None,
+                grad_src.to(src_xyz.dtype) if src_xyz is not None and ctx.needs_input_grad[1] else None) + (None,) * 6
+
+
+class _EdgeFrameFeatures(torch.autograd.Function):
+    """ops.edge_frames (K26) or ops.csr_edge_frames (K51) with K54 as their vector-Jacobian product; the lists as above."""
+
+    @staticmethod
+    def forward(ctx, rot, trans, src_rot, src_trans, first, col, frame_mask, src_mask):
+        if col is None:
+            pos, rel = ops.edge_frames(rot, trans, first, frame_mask)
+        else:
+            pos, rel = ops.csr_edge_frames(rot, trans, first, col, frame_mask, src_rot=src_rot, src_trans=src_trans,
+                                           src_mask=src_mask)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(rot, trans, src_rot, src_trans, first, col, frame_mask, src_mask)
+        return pos, rel
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_pos, grad_rot):
+        rot, trans, src_rot, src_trans, first, col, frame_mask, src_mask = ctx.saved_tensors
+        if grad_pos is None and grad_rot is None:
+            return (None,) * 8
+        B, M = rot.shape[:2]
+        row_ptr, col = _csr_lists(first, col, B, M)
+        E = col.shape[0]
+        in_ptr, in_edge = ops.csr_incoming_edges(row_ptr, col, B, M if src_rot is None else src_rot.shape[1], M)
+        out = ops.csr_edge_frames_backward(rot, trans, row_ptr, col, in_ptr, in_edge, frame_mask, src_rot=src_rot,
+                                           src_trans=src_trans, src_mask=src_mask, grad_pos=_flat_grad(grad_pos, E),
+                                           grad_rot=None if grad_rot is None else grad_rot.contiguous().reshape(E, 3, 3))
+        out = tuple(out) + (None, None) * (src_rot is None)
+        inputs = (rot, trans, src_rot, src_trans)
+        return tuple(g.to(x.dtype) if x is not None and ctx.needs_input_grad[n] else None
+                     for n, (g, x) in enumerate(zip(out, inputs))) + (None,) * 4
+
+
 def edge_distance_features(xyz, idx, atom_mask=None, pairs=BACKBONE_PAIRS, centers=None, sigma=None, return_dist=False):
     """Radial basis functions of the atom-pair distances along the edges of a neighbour graph: ``rbf`` (B,N,k,P*R) fp32
     or, with ``return_dist``, ``(rbf, dist)`` with ``dist`` (B,N,k,P).  ``xyz`` is (B,N,A,3); ``idx`` (B,N,k) are the
@@ -722,8 +823,13 @@ def edge_distance_features(xyz, idx, atom_mask=None, pairs=BACKBONE_PAIRS, cente
     (B,N,k,A,3) coordinates and the broadcast (B,N,k,P,R) intermediates of the composed route are never built.
     numpy in -> numpy out; tensors come back on the device of ``xyz``, CPU tensors included.
 
-    Not differentiable: the outputs carry no graph, and no backward kernel exists.  The differentiable route stays
-    ``gather_neighbors`` and plain torch on what it returns."""
+    Differentiable with respect to ``xyz``: where it is a tensor that requires grad (and grad mode is on) the outputs carry
+    a graph whose backward pass is HIP too -- ``ops.csr_edge_rbf_backward`` (K52) on the list as CSR lists, the incoming
+    lists of ``ops.csr_incoming_edges`` and ``ops.csr_edge_pair_grad_sum`` (K53): no atomics, bit-for-bit repeatable, exactly
+    0 at the padding, under the mask and on a self edge of length 0.  Not differentiable with respect to ``centers``,
+    ``sigma`` or the list, and not twice: for a second derivative the composed route -- ``gather_neighbors`` and plain torch
+    -- is still the one.  numpy inputs and inputs that do not require grad take the forward kernel alone, and their
+    outputs carry no graph."""
     if (centers is None) != (sigma is None):
         raise ValueError("centers and sigma come together (rbf_centers() returns both)")
     if centers is None:
@@ -732,8 +838,13 @@ def edge_distance_features(xyz, idx, atom_mask=None, pairs=BACKBONE_PAIRS, cente
     if any(len(p) != 2 for p in pairs):
         raise ValueError("pairs must be (slot on the source residue, slot on the neighbour) pairs")
     args, finish = _marshal((("xyz", xyz), ("idx", idx), ("atom_mask", atom_mask)))
-    dist, rbf = finish(ops.edge_rbf(**args, pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers,
-                                    sigma=sigma, want_dist=bool(return_dist)))
+    tables = dict(pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers, sigma=sigma)
+    if _wants_grad(xyz):
+        args = _attached(args, xyz=xyz)
+        rbf, dist = finish(_EdgeDistanceFeatures.apply(args["xyz"], None, args["idx"], None, args.get("atom_mask"), None, tables,
+                                                       bool(return_dist)))
+    else:
+        dist, rbf = finish(ops.edge_rbf(**args, **tables, want_dist=bool(return_dist)))
     return (rbf, dist) if return_dist else rbf
 
 
@@ -752,8 +863,17 @@ def edge_frame_features(rot, trans, idx, frame_mask=None) -> EdgeFrames:
     is outside ``frame_mask`` (B,N), and NaN there never reaches the result.  One HIP kernel (``ops.edge_frames``).
     numpy in -> numpy out; tensors come back on the device of ``rot``, CPU tensors included.
 
-    Not differentiable: the outputs carry no graph.  The differentiable route stays ``gather_neighbors`` and plain torch."""
+    Differentiable with respect to ``rot`` and ``trans``: where one of them is a tensor that requires grad (and grad mode
+    is on) the outputs carry a graph whose backward pass is one HIP kernel, ``ops.csr_edge_frames_backward`` (K54), on the
+    list as CSR lists -- ``rot`` as nine free numbers per frame, which is what the backward pass of ``backbone_frames``
+    takes; no atomics, defined bit for bit, exactly 0 at the padding and under the mask.  Not differentiable twice (for a
+    second derivative ``gather_neighbors`` and plain torch are still the route), nor with respect to the list; where
+    neither input requires grad the outputs carry no graph."""
     args, finish = _marshal((("rot", rot), ("trans", trans), ("idx", idx), ("frame_mask", frame_mask)))
+    if _wants_grad(rot, trans):
+        args = _attached(args, rot=rot, trans=trans)
+        return EdgeFrames(*finish(_EdgeFrameFeatures.apply(args["rot"], args["trans"], None, None, args["idx"], None,
+                                                           args.get("frame_mask"), None)))
     return EdgeFrames(*finish(ops.edge_frames(**args)))
 
 
@@ -794,7 +914,10 @@ def radius_edge_distance_features(xyz, graph, atom_mask=None, pairs=BACKBONE_PAI
     read.  For an atom graph pass the zero-copy view ``xyz.reshape(B, N*A, 1, 3)`` with ``pairs=((0, 0),)``.
     numpy in -> numpy out; tensors come back on the device of ``xyz``, CPU tensors included.
 
-    Not differentiable: the outputs carry no graph.  ``radius_graph_edges`` and plain torch stay the differentiable route."""
+    Differentiable with respect to ``xyz`` and ``source_xyz``, like ``edge_distance_features`` and by the same kernels (K52,
+    K53): where one of them requires grad the outputs carry a graph; the graph itself, ``centers`` and ``sigma`` take no
+    gradient.  The backward pass makes no host read either, so it runs inside ``torch.cuda.graph`` behind a ``max_edges``
+    graph.  Not differentiable with respect to anything else, and where neither requires grad the outputs carry no graph."""
     if (centers is None) != (sigma is None):
         raise ValueError("centers and sigma come together (rbf_centers() returns both)")
     if centers is None:
@@ -805,8 +928,13 @@ def radius_edge_distance_features(xyz, graph, atom_mask=None, pairs=BACKBONE_PAI
     _graph_queries(graph)
     args, finish = _marshal((("xyz", xyz), ("row_ptr", graph.row_ptr), ("col", graph.col), ("atom_mask", atom_mask),
                              ("src_xyz", source_xyz), ("src_mask", source_mask)))
-    dist, rbf = finish(ops.csr_edge_rbf(**args, pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers,
-                                        sigma=sigma, want_dist=bool(return_dist)))
+    tables = dict(pair_i=[p[0] for p in pairs], pair_j=[p[1] for p in pairs], centers=centers, sigma=sigma)
+    if _wants_grad(xyz, source_xyz):
+        args = _attached(args, xyz=xyz, src_xyz=source_xyz)
+        rbf, dist = finish(_EdgeDistanceFeatures.apply(args["xyz"], args.get("src_xyz"), args["row_ptr"], args["col"],
+                                                       args.get("atom_mask"), args.get("src_mask"), tables, bool(return_dist)))
+    else:
+        dist, rbf = finish(ops.csr_edge_rbf(**args, **tables, want_dist=bool(return_dist)))
     return (rbf, dist) if return_dist else rbf
 
 
@@ -819,12 +947,43 @@ def radius_edge_frame_features(rot, trans, graph, frame_mask=None, source_rot=No
     its mask and on every position that is no edge.  One HIP kernel (``ops.csr_edge_frames``); no host read.
     numpy in -> numpy out; tensors come back on the device of ``rot``, CPU tensors included.
 
-    Not differentiable: the outputs carry no graph."""
+    Differentiable with respect to ``rot``, ``trans``, ``source_rot`` and ``source_trans``, like ``edge_frame_features`` and by
+    the same kernel (K54), with no host read.  Not differentiable with respect to the graph, and where none of the four
+    requires grad the outputs carry no graph."""
     _graph_queries(graph)
     args, finish = _marshal((("rot", rot), ("trans", trans), ("row_ptr", graph.row_ptr), ("col", graph.col),
                              ("frame_mask", frame_mask), ("src_rot", source_rot), ("src_trans", source_trans),
                              ("src_mask", source_mask)))
+    if _wants_grad(rot, trans, source_rot, source_trans):
+        args = _attached(args, rot=rot, trans=trans, src_rot=source_rot, src_trans=source_trans)
+        return EdgeFrames(*finish(_EdgeFrameFeatures.apply(args["rot"], args["trans"], args.get("src_rot"), args.get("src_trans"),
+                                                           args["row_ptr"], args["col"], args.get("frame_mask"),
+                                                           args.get("src_mask"))))
     return EdgeFrames(*finish(ops.csr_edge_frames(**args)))
+
+
+class IncomingEdges(NamedTuple):
+    """The edges of a ``RadiusGraph`` grouped by their target (``radius_graph_incoming``): target ``o = b * n_targets + j``
+    receives the edge positions ``edge[ptr[o]:ptr[o + 1]]``."""
+    ptr: torch.Tensor    # (B*n_targets+1,) int64; ptr[-1] is the number of real edges
+    edge: torch.Tensor   # (E,) int64: positions into graph.col, ascending within a group; from ptr[-1] on, the padding
+
+
+def radius_graph_incoming(graph, n_targets) -> IncomingEdges:
+    """The edges of a ``RadiusGraph`` by the point they arrive at: ``IncomingEdges(ptr (B*n_targets+1,) int64, edge (E,)
+    int64)``, E being ``graph.col.shape[0]``.  ``edge[ptr[o]:ptr[o + 1]]`` are the positions p into ``graph.col`` with
+    ``col[p] == j`` in structure b, ``o = b * n_targets + j``, ascending.  Positions that are no edge -- from ``row_ptr[-1]``
+    on, and wherever ``col`` is outside [0, n_targets) -- are left out of every group: they fill ``edge`` from ``ptr[-1]`` on,
+    so the shapes do not depend on the data.  ``n_targets`` is M, the length of the axis ``col`` indexes.  With it a layer
+    aggregates messages at the targets in a fixed order -- ``segment_reduce`` over ``messages[edge]``, or a loop -- where
+    ``index_add`` uses atomics; it is what the backward pass of the edge features sums by.  Plain torch
+    (``ops.csr_incoming_edges``: a stable sort and two ``searchsorted``) on the graph's own device, CPU included; no host
+    read, so it runs inside ``torch.cuda.graph`` behind ``radius_graph(max_edges=n)``.  numpy in -> numpy out."""
+    Q = _graph_queries(graph)
+    arrays = isinstance(graph.row_ptr, np.ndarray)
+    row_ptr, col = (torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t for t in (graph.row_ptr, graph.col))
+    out = ops.csr_incoming_edges(row_ptr, col, int(graph.count.shape[0]), Q, n_targets)
+    return IncomingEdges(*(t.numpy() if arrays else t for t in out))
 
 
 def neighbors_to_radius_graph(neighbors_or_idx) -> RadiusGraph:

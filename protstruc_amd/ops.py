@@ -16,7 +16,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _csredge, _lib
+from . import _csredge, _edgegrad, _lib
 
 
 RNG_STATE_WORDS = 528  # PS_RNG_STATE_WORDS of include/protstruc_hip.h
@@ -2590,6 +2590,209 @@ def csr_edge_frames(rot: torch.Tensor, trans: torch.Tensor, row_ptr: torch.Tenso
         _launch_csredge("ps_csr_edge_frames_f32", _ptr(r), _ptr(t), _ptr(fm), _ptr(sr), _ptr(st), _ptr(sm), _ptr(rp), _ptr(cl), E,
                         _ptr(pos), _ptr(rel), B, M, Q, _stream(r))
     return pos, rel
+
+
+# ---- the backward kernels of the edge features (K52 - K54, include/protstruc_edgegrad.h) -------------------------------------
+def _launch_edgegrad(name: str, *args) -> None:
+    """Call entry point ``name`` of libprotstruc_edgegrad.so; HipLibraryError if it does not return hipSuccess."""
+    rc = getattr(_edgegrad.load(), name)(*args)
+    if rc:
+        _edgegrad.check(rc, name)
+
+
+def _check_sizes(**sizes) -> None:
+    """sizes that arrive as arguments, where other functions read them off a shape: non-negative integers, or ValueError"""
+    for name, value in sizes.items():
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
+
+
+def _check_incoming(in_ptr, in_edge, B: int, M: int) -> None:
+    """The incoming list of ``csr_incoming_edges`` over B x M targets: ``in_ptr`` (B*M+1,) and ``in_edge`` (n,) int64."""
+    if tuple(in_ptr.shape) != (B * M + 1,) or in_ptr.dtype != torch.int64:
+        raise ValueError(f"in_ptr must be an int64 tensor of shape ({B * M + 1},), the {B} x {M} targets and one, got "
+                         f"{in_ptr.dtype} {tuple(in_ptr.shape)}")
+    if in_edge.ndim != 1 or in_edge.dtype != torch.int64:
+        raise ValueError(f"in_edge must be an int64 tensor of shape (edges,), got {in_edge.dtype} {tuple(in_edge.shape)}")
+
+
+def csr_incoming_edges(row_ptr: torch.Tensor, col: torch.Tensor, B: int, Q: int, M: int):
+    """The transpose's index of CSR lists ``row_ptr`` (B*Q+1,), ``col`` (E,) over B x M targets: ``(ptr (B*M+1,) int64, edge
+    (E,) int64)``.  ``edge[ptr[o]:ptr[o + 1]]`` are the edge positions p whose target is ``o = batch(p) * M + col[p]``,
+    ascending; the positions that are no edge -- from ``row_ptr[-1]`` on, and wherever ``col`` is outside [0, M) -- belong to
+    no group and fill ``edge`` from ``ptr[-1]`` on.  It is what lets a target sum over its edges in a fixed order without
+    atomics (``csr_edge_pair_grad_sum``, ``csr_edge_frames_backward``).  Plain torch on the lists' own device, CPU included:
+    the row of every position by ``searchsorted``, the key ``batch * M + col`` (``B * M`` for the padding), a stable sort and
+    a second ``searchsorted``.  No host read -- no ``bincount``, whose output size is one --, so capturable."""
+    _check_sizes(B=B, Q=Q, M=M)
+    B, Q, M = int(B), int(Q), int(M)
+    _check_batch(B)
+    _check_count(Q, 0, 2 ** 24, "queries per structure")
+    _check_count(M, 0, 2 ** 24, "points per structure")
+    E = _check_csr_graph(row_ptr, col, B, Q, f"{B} structures")
+    _same_device(row_ptr, col=col)
+    dev = row_ptr.device
+    position = torch.arange(E, dtype=torch.int64, device=dev)
+    rows = torch.searchsorted(row_ptr[1:].to(torch.int64).contiguous(), position, right=True)   # r(p), B * Q in the tail
+    target = col.to(torch.int64)
+    real = (rows < B * Q) & (target >= 0) & (target < M)
+    key = torch.where(real, torch.div(rows, max(Q, 1), rounding_mode="floor") * M + target, torch.full_like(target, B * M))
+    key, edge = torch.sort(key, stable=True)
+    ptr = torch.searchsorted(key, torch.arange(B * M + 1, dtype=torch.int64, device=dev))
+    return ptr, edge
+
+
+def check_csr_edge_rbf_backward_shapes(xyz, row_ptr, col, atom_mask=None, pair_i=(), pair_j=(), centers=(), sigma=1.0,
+                                       src_xyz=None, src_mask=None, grad_dist=None, grad_rbf=None):
+    """Shape rules of ``csr_edge_rbf_backward`` (no launch): those of ``csr_edge_rbf``, and ``grad_dist`` (E,P) and
+    ``grad_rbf`` (E,P*R) floating-point, one of them given; ValueError; returns (B, M, A, Q, As, E)."""
+    dims = check_csr_edge_rbf_shapes(xyz, row_ptr, col, atom_mask, pair_i, pair_j, centers, sigma, src_xyz, src_mask)
+    E, P, R = dims[5], len(pair_i), _host_f32(centers, "centers").shape[0]
+    if grad_dist is None and grad_rbf is None:
+        raise ValueError("nothing to compute: grad_dist and grad_rbf are both None")
+    _check_optional(grad_dist, (E, P), "grad_dist", "the edges and pairs", floating=True)
+    _check_optional(grad_rbf, (E, P * R), "grad_rbf", "the edges, pairs and centers", floating=True)
+    _same_device(xyz, grad_dist=grad_dist, grad_rbf=grad_rbf)
+    return dims
+
+
+def csr_edge_rbf_backward(xyz: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor,
+                          atom_mask: Optional[torch.Tensor] = None, *, pair_i: Sequence[int], pair_j: Sequence[int], centers,
+                          sigma: float, src_xyz: Optional[torch.Tensor] = None, src_mask: Optional[torch.Tensor] = None,
+                          grad_dist: Optional[torch.Tensor] = None, grad_rbf: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K52.  The gradient of ``csr_edge_rbf`` (and of ``edge_rbf``) per edge and atom pair: ``pair_grad`` (E,P,3) fp32, the
+    derivative of the loss with respect to the TARGET's atom of pair p of every edge, given ``grad_dist`` (E,P) and / or
+    ``grad_rbf`` (E,P*R); the source's atom gets its negative (``csr_edge_pair_grad_sum`` adds both up).  The distance and
+    the Gaussians are recomputed as the forward computes them; exactly 0 at the padding, where either atom is outside its
+    mask and where the distance is 0 (a self edge: defined as 0, not NaN), and nothing -- no coordinate and no element of the
+    incoming gradients -- is read there.  The order of every sum is fixed, so the result does not depend on how ``grad_rbf``
+    is aligned, and repeats bit for bit.  No host read; every element is written (include/protstruc_edgegrad.h)."""
+    B, M, A, Q, As, E = check_csr_edge_rbf_backward_shapes(xyz, row_ptr, col, atom_mask, pair_i, pair_j, centers, sigma, src_xyz,
+                                                           src_mask, grad_dist, grad_rbf)
+    x, am = _f32c(xyz, "xyz"), _u8c(atom_mask, "atom_mask")
+    sx, sm = _f32c_opt(src_xyz, "src_xyz"), _u8c(src_mask, "src_mask")
+    gd, gr = _f32c_opt(grad_dist, "grad_dist"), _f32c_opt(grad_rbf, "grad_rbf")
+    rp, cl = _row_ptr64(row_ptr), _col32(col, M)
+    cen = _host_f32(centers, "centers")
+    P, R = len(pair_i), cen.shape[0]
+    ints = ctypes.c_int * P
+    with _on(x.device):
+        if not (B and E and M and Q):   # nothing to launch (an empty tensor has no device pointer): all padding
+            return torch.zeros(E, P, 3, dtype=torch.float32, device=x.device)
+        pair_grad = torch.empty(E, P, 3, dtype=torch.float32, device=x.device)   # every element is written
+        _launch_edgegrad("ps_csr_edge_rbf_backward_f32", _ptr(x), _ptr(am), _ptr(sx), _ptr(sm), _ptr(rp), _ptr(cl), E,
+                         ints(*(int(s) for s in pair_i)), ints(*(int(s) for s in pair_j)), P, (ctypes.c_float * R)(*cen.tolist()),
+                         R, float(sigma), _ptr(gd), _ptr(gr), _ptr(pair_grad), B, M, A, Q, As, _stream(x))
+    return pair_grad
+
+
+def check_csr_edge_pair_grad_sum_shapes(pair_grad, row_ptr, in_ptr, in_edge, pair_i=(), pair_j=(), B=0, M=0, A=1, Q=None,
+                                        As=None) -> Tuple[int, int, int]:
+    """Shape rules of ``csr_edge_pair_grad_sum`` (no launch): ValueError; returns (Q, As, E).  ``pair_grad`` (E,P,3) fp32;
+    ``row_ptr`` (B*Q+1,) integers; the incoming list of ``csr_incoming_edges``; ``Q`` and ``As`` come together (the bipartite
+    graph) or not at all."""
+    _check_sizes(B=B, M=M, A=A)
+    if (Q is None) != (As is None):
+        raise ValueError("Q and As come together: the sources of a bipartite graph")
+    if Q is not None:
+        _check_sizes(Q=Q, As=As)
+    _check_batch(B)
+    _check_count(M, 0, 2 ** 24, "residues per structure")
+    Qs, Ass = (M, A) if Q is None else (int(Q), int(As))
+    _check_count(Qs, 0, 2 ** 24, "queries per structure")
+    try:
+        slots_i, slots_j = [int(s) for s in pair_i], [int(s) for s in pair_j]
+    except (TypeError, ValueError):
+        raise ValueError("pair_i and pair_j must be sequences of atom slots") from None
+    if len(slots_i) != len(slots_j) or not 1 <= len(slots_i) <= CSREDGE_MAX_PAIRS:
+        raise ValueError(f"pair_i and pair_j must be equally long, 1 .. {CSREDGE_MAX_PAIRS} atom slots each, got "
+                         f"{len(slots_i)} and {len(slots_j)}")
+    if A < 1 or Ass < 1:
+        raise ValueError(f"at least one atom slot, got A = {A} and As = {Ass}")
+    _check_atom_slots(Ass, *slots_i)
+    _check_atom_slots(A, *slots_j)
+    P = len(slots_i)
+    if pair_grad.ndim != 3 or tuple(pair_grad.shape[1:]) != (P, 3) or not pair_grad.dtype.is_floating_point:
+        raise ValueError(f"pair_grad must be a floating-point tensor of shape (edges, {P}, 3), got {pair_grad.dtype} "
+                         f"{tuple(pair_grad.shape)}")
+    if tuple(row_ptr.shape) != (B * Qs + 1,) or not _is_integer_tensor(row_ptr):
+        raise ValueError(f"row_ptr must be an integer tensor of shape ({B * Qs + 1},), the {B} x {Qs} sources and one, got "
+                         f"{row_ptr.dtype} {tuple(row_ptr.shape)}")
+    _check_incoming(in_ptr, in_edge, B, M)
+    _same_device(pair_grad, row_ptr=row_ptr, in_ptr=in_ptr, in_edge=in_edge)
+    return Qs, Ass, pair_grad.shape[0]
+
+
+def csr_edge_pair_grad_sum(pair_grad: torch.Tensor, row_ptr: torch.Tensor, in_ptr: torch.Tensor, in_edge: torch.Tensor, *,
+                           pair_i: Sequence[int], pair_j: Sequence[int], B: int, M: int, A: int, Q: Optional[int] = None,
+                           As: Optional[int] = None):
+    """K53.  The segmented sum of ``pair_grad`` (E,P,3) of ``csr_edge_rbf_backward`` into the gradient of the coordinates:
+    ``grad`` (B,M,A,3) fp32 or, with ``Q`` and ``As`` (a bipartite graph), ``(grad, grad_src (B,Q,As,3))``.  Every atom sums,
+    in double from +0 and in a fixed order -- its residue's outgoing edge positions ascending, each SUBTRACTED at slot
+    ``pair_i[t]``, then the incoming ones of ``csr_incoming_edges`` ascending, each ADDED at slot ``pair_j[t]`` -- and rounds
+    once; in a bipartite graph ``grad_src`` takes the first loop and ``grad`` the second.  No atomics; exact +0 for a slot no
+    pair names and for a residue without edges; every element is written; no host read (include/protstruc_edgegrad.h)."""
+    Qs, Ass, E = check_csr_edge_pair_grad_sum_shapes(pair_grad, row_ptr, in_ptr, in_edge, pair_i, pair_j, B, M, A, Q, As)
+    B, M, A = int(B), int(M), int(A)
+    pg = _f32c(pair_grad, "pair_grad")
+    rp, ip, ie = _row_ptr64(row_ptr), in_ptr.contiguous(), in_edge.contiguous()
+    P = len(pair_i)
+    ints = ctypes.c_int * P
+    with _on(pg.device):
+        edges = bool(B and E and M and Qs)   # otherwise nothing is an edge, and an empty tensor has no device pointer
+        new = torch.empty if edges else torch.zeros   # the kernel writes every element
+        grad = new(B, M, A, 3, dtype=torch.float32, device=pg.device)
+        grad_src = None if Q is None else new(B, Qs, Ass, 3, dtype=torch.float32, device=pg.device)
+        if edges:
+            _launch_edgegrad("ps_csr_edge_pair_grad_sum_f32", _ptr(pg), _ptr(rp), E, _ptr(ip), _ptr(ie), ie.shape[0],
+                             ints(*(int(s) for s in pair_i)), ints(*(int(s) for s in pair_j)), P, _ptr(grad), _ptr(grad_src),
+                             B, M, A, Qs, Ass, _stream(pg))
+    return grad if Q is None else (grad, grad_src)
+
+
+def check_csr_edge_frames_backward_shapes(rot, trans, row_ptr, col, in_ptr, in_edge, frame_mask=None, src_rot=None,
+                                          src_trans=None, src_mask=None, grad_pos=None, grad_rot=None) -> Tuple[int, int, int, int]:
+    """Shape rules of ``csr_edge_frames_backward`` (no launch): those of ``csr_edge_frames``, the incoming list of
+    ``csr_incoming_edges``, and ``grad_pos`` (E,3) and ``grad_rot`` (E,3,3) floating-point, one of them given; ValueError;
+    returns (B, M, Q, E)."""
+    B, M, Q, E = check_csr_edge_frames_shapes(rot, trans, row_ptr, col, frame_mask, src_rot, src_trans, src_mask)
+    if grad_pos is None and grad_rot is None:
+        raise ValueError("nothing to compute: grad_pos and grad_rot are both None")
+    _check_optional(grad_pos, (E, 3), "grad_pos", "the edges", floating=True)
+    _check_optional(grad_rot, (E, 3, 3), "grad_rot", "the edges", floating=True)
+    _check_incoming(in_ptr, in_edge, B, M)
+    _same_device(rot, in_ptr=in_ptr, in_edge=in_edge, grad_pos=grad_pos, grad_rot=grad_rot)
+    return B, M, Q, E
+
+
+def csr_edge_frames_backward(rot: torch.Tensor, trans: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor,
+                             in_ptr: torch.Tensor, in_edge: torch.Tensor, frame_mask: Optional[torch.Tensor] = None, *,
+                             src_rot: Optional[torch.Tensor] = None, src_trans: Optional[torch.Tensor] = None,
+                             src_mask: Optional[torch.Tensor] = None, grad_pos: Optional[torch.Tensor] = None,
+                             grad_rot: Optional[torch.Tensor] = None):
+    """K54.  The gradient of ``csr_edge_frames`` (and of ``edge_frames``) with respect to the frames, given ``grad_pos`` (E,3)
+    and / or ``grad_rot`` (E,3,3): ``(d_rot (B,M,3,3), d_trans (B,M,3))`` fp32 and, where the sources' frames are given, ``(d_rot,
+    d_trans, d_src_rot (B,Q,3,3), d_src_trans (B,Q,3))``.  ``rot`` counts as nine free numbers per frame, which is what
+    ``frames_backward`` takes.  One kernel walks a frame's outgoing edge positions, ascending, then its incoming ones
+    (``csr_incoming_edges``), ascending, sums their terms in double from +0 and rounds once: defined bit for bit, no
+    atomics.  Exactly 0 at the padding and where either frame is outside its mask; nothing is read there.  No host read;
+    every element is written (include/protstruc_edgegrad.h)."""
+    B, M, Q, E = check_csr_edge_frames_backward_shapes(rot, trans, row_ptr, col, in_ptr, in_edge, frame_mask, src_rot, src_trans,
+                                                       src_mask, grad_pos, grad_rot)
+    r, t, fm = _f32c(rot, "rot"), _f32c(trans, "trans"), _u8c(frame_mask, "frame_mask")
+    sr, st, sm = _f32c_opt(src_rot, "src_rot"), _f32c_opt(src_trans, "src_trans"), _u8c(src_mask, "src_mask")
+    gp, gr = _f32c_opt(grad_pos, "grad_pos"), _f32c_opt(grad_rot, "grad_rot")
+    rp, cl, ip, ie = _row_ptr64(row_ptr), _col32(col, M), in_ptr.contiguous(), in_edge.contiguous()
+    bipartite = sr is not None
+    with _on(r.device):
+        edges = bool(B and E and M and Q)   # otherwise nothing is an edge, and an empty tensor has no device pointer
+        shapes = [(B, M, 3, 3), (B, M, 3)] + ([(B, Q, 3, 3), (B, Q, 3)] if bipartite else [])
+        out = tuple((torch.empty if edges else torch.zeros)(shape, dtype=torch.float32, device=r.device) for shape in shapes)
+        if edges:   # the kernel writes every element
+            _launch_edgegrad("ps_csr_edge_frames_backward_f32", _ptr(r), _ptr(t), _ptr(fm), _ptr(sr), _ptr(st), _ptr(sm), _ptr(rp),
+                             _ptr(cl), E, _ptr(ip), _ptr(ie), ie.shape[0], _ptr(gp), _ptr(gr), *(_ptr(o) for o in out),
+                             *(() if bipartite else (None, None)), B, M, Q, _stream(r))
+    return out
 
 
 CHI_MAX_TYPES = 32  # PS_CHI_MAX_TYPES of include/protstruc_hip.h: the tables travel in the kernel's arguments

@@ -1022,6 +1022,18 @@ class StructureBatch:
         offset = torch.where(chain[b, i] == chain[b, j], offset, torch.full_like(offset, 2 * max_offset + 1))
         return offset.masked_fill(~real, 0)
 
+    def _tracks_grad(self) -> bool:
+        """whether the float outputs of the edge features carry a graph: the coordinates require grad and grad mode is on"""
+        return torch.is_grad_enabled() and self.xyz.requires_grad
+
+    def _edge_frames(self, present: torch.Tensor):
+        """The N-CA-C frames and CA positions the edge features are taken of.  Where they carry a graph, residues that
+        lack one of the three atoms are kept out of its backward pass, so NaN coordinates there never reach a gradient."""
+        if self._tracks_grad():
+            from . import geometry
+            return geometry.backbone_frames(self.xyz, "N", "CA", "C", "CA", residue_mask=present[:, :, :3].all(dim=-1))
+        return self.backbone_orientations_and_translations()
+
     def _radius_edge_features(self, graph, slots, n_rbf, d_min, d_max, frames, max_offset) -> RadiusEdgeFeatures:
         """:meth:`edge_features` on a ``geometry.RadiusGraph`` over the residues: K49 - K51 and the offsets, no host read."""
         from . import geometry
@@ -1032,7 +1044,7 @@ class StructureBatch:
         graph = geometry.RadiusGraph(*(None if t is None else _always_tensor(t).to(self.device) for t in graph))
         centers, sigma = geometry.rbf_centers(n_rbf, d_min, d_max)
         present = self._present_atoms()
-        with torch.no_grad():
+        with torch.set_grad_enabled(self._tracks_grad()):   # the float outputs carry a graph where the coordinates require grad
             batch, row = geometry.radius_edge_rows(graph)
             rbf = geometry.radius_edge_distance_features(self.xyz, graph, present, pairs=[(a, b) for a in slots for b in slots],
                                                          centers=centers, sigma=sigma)
@@ -1040,7 +1052,7 @@ class StructureBatch:
             if frames:
                 if A < 3:
                     raise ValueError(f"frames need the N, CA and C slots; this batch has {A} atom slots")
-                rot, trans = self.backbone_orientations_and_translations()
+                rot, trans = self._edge_frames(present)
                 local_pos, rel_rot = geometry.radius_edge_frame_features(rot, trans, graph, present[:, :, :3].all(dim=-1))
             col = graph.col if graph.col.dtype == torch.int32 else graph.col.clamp(-1, N).to(torch.int32)
             offset = self._flat_edge_offsets(batch, row, col, int(max_offset))
@@ -1053,8 +1065,9 @@ class StructureBatch:
         --, -1 from position ``row_ptr[-1]`` on; ``mask`` is ``batch >= 0``.  ``rbf`` (E, n_rbf): ``n_rbf`` Gaussians
         (``geometry.rbf_centers(n_rbf, d_min, d_max)``) of the distance between the two atoms, exactly 0 where ``mask`` is
         False.  Two HIP kernels over the zero-copy (B, N*A, 1, 3) view of the coordinates
-        (``geometry.radius_edge_rows``, ``.radius_edge_distance_features``); with a ``max_edges`` graph no host read.  Not
-        differentiable."""
+        (``geometry.radius_edge_rows``, ``.radius_edge_distance_features``); with a ``max_edges`` graph no host read.
+        ``rbf`` is differentiable with respect to this batch's coordinates where they require grad (HIP kernels backwards
+        too: K52, K53); the indices and the mask carry no graph."""
         from . import geometry
 
         B, N, A = self.xyz.shape[:3]
@@ -1062,7 +1075,7 @@ class StructureBatch:
             raise ValueError(f"graph must be a geometry.RadiusGraph over the {(B, N * A)} atoms of this batch (atom_radius_graph)")
         graph = geometry.RadiusGraph(*(None if t is None else _always_tensor(t).to(self.device) for t in graph))
         centers, sigma = geometry.rbf_centers(n_rbf, d_min, d_max)
-        with torch.no_grad():
+        with torch.set_grad_enabled(self._tracks_grad()):
             batch, atom = geometry.radius_edge_rows(graph)
             rbf = geometry.radius_edge_distance_features(self.xyz.reshape(B, N * A, 1, 3), graph,
                                                          self._present_atoms().reshape(B, N * A, 1), pairs=((0, 0),),
@@ -1087,8 +1100,11 @@ class StructureBatch:
         holds none); 0 at the padding.  With ``frames``, ``local_pos`` (B,N,k,3) and ``rel_rot`` (B,N,k,3,3) are the
         neighbour's CA and N-CA-C frame in the source residue's frame, ``R_i^T (t_j - t_i)`` and ``R_i^T R_j``, zero
         where either residue lacks N, CA or C; otherwise both are None.  Two HIP kernels
-        (``geometry.edge_distance_features``, ``.edge_frame_features``); the offsets are plain torch.  Not differentiable
-        -- ``geometry.gather_neighbors`` is the differentiable route.
+        (``geometry.edge_distance_features``, ``.edge_frame_features``); the offsets are plain torch.  ``rbf``,
+        ``local_pos`` and ``rel_rot`` are differentiable with respect to this batch's coordinates where they require grad
+        and grad mode is on -- HIP kernels backwards too (K52 - K54, then the frames' own backward kernel), nothing of the
+        size of the forward's output kept alive --; ``idx``, ``mask`` and ``offset`` carry no graph, and neither does
+        anything where the coordinates do not require grad.
 
         ``graph`` may also be a ``geometry.RadiusGraph`` over the residues (:meth:`radius_graph`): lists of any length.
         The result is then ``RadiusEdgeFeatures(batch, row, col, mask, rbf, offset, local_pos, rel_rot)``, the same
@@ -1118,14 +1134,14 @@ class StructureBatch:
         idx = torch.where((idx >= 0) & (idx < N), idx, torch.full_like(idx, -1)).to(torch.int32)
         centers, sigma = geometry.rbf_centers(n_rbf, d_min, d_max)
         present = self._present_atoms()
-        with torch.no_grad():
+        with torch.set_grad_enabled(self._tracks_grad()):
             rbf = geometry.edge_distance_features(self.xyz, idx, present, pairs=[(a, b) for a in slots for b in slots],
                                                   centers=centers, sigma=sigma)
             local_pos = rel_rot = None
             if frames:
                 if A < 3:
                     raise ValueError(f"frames need the N, CA and C slots; this batch has {A} atom slots")
-                rot, trans = self.backbone_orientations_and_translations()
+                rot, trans = self._edge_frames(present)
                 local_pos, rel_rot = geometry.edge_frame_features(rot, trans, idx, present[:, :, :3].all(dim=-1))
             offset = self._edge_offsets(idx, int(max_offset))
         return EdgeFeatures(idx, idx >= 0, rbf, offset, local_pos, rel_rot)

@@ -27,6 +27,9 @@ CSREDGE_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_csredge.so")
 # the backward kernels of the edge features (K52 - K54), likewise: include/protstruc_edgegrad.h
 EDGEGRAD_SRC_DIR = os.path.join(HERE, "csrc_edgegrad")
 EDGEGRAD_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_edgegrad.so")
+# message passing on graphs (K55 - K59), likewise: include/protstruc_aggregate.h
+AGGREGATE_SRC_DIR = os.path.join(HERE, "csrc_aggregate")
+AGGREGATE_LIB_PATH = os.path.join(LIB_DIR, "libprotstruc_aggregate.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ROCM_LIB = os.environ.get("ROCM_LIB", "/opt/rocm/lib")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"]
@@ -178,6 +181,28 @@ def build_edgegrad(force=False, verbose=True):
     return _edgegrad_library().build(force, verbose)
 
 
+def aggregate_sources():
+    return sorted(glob.glob(os.path.join(AGGREGATE_SRC_DIR, "*.hip")))
+
+
+def _aggregate_library(out=None):
+    inputs = aggregate_sources() + sorted(glob.glob(os.path.join(AGGREGATE_SRC_DIR, "*.hpp"))) + \
+        sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "protstruc_aggregate.h")]
+    return _Target(out or AGGREGATE_LIB_PATH, b"aggregate-lib " + " ".join(FLAGS).encode(), inputs,
+                   lambda tmp: [HIPCC] + FLAGS + ["-I" + CSRC, "-o", tmp] + aggregate_sources())
+
+
+def aggregate_is_stale(path=None):
+    return _aggregate_library(path).is_stale()
+
+
+def build_aggregate(force=False, verbose=True):
+    """libprotstruc_aggregate.so: csrc_aggregate/*.hip, message passing on graphs -- segment reductions, gathers and the edge
+    softmax (include/protstruc_aggregate.h).  Compiled with exactly FLAGS and -I csrc, like libprotstruc_edgegrad.so, and for
+    the same reason: it shares ps_common.hpp and -ffp-contract=off with the other kernels, and adds no export to them."""
+    return _aggregate_library().build(force, verbose)
+
+
 EXAMPLE_SRC = os.path.join(HERE, "..", "examples", "c_abi_demo.c")
 EXAMPLE_BIN = os.path.join(HERE, "..", "build", "c_abi_demo")
 
@@ -223,5 +248,6 @@ if __name__ == "__main__":
     print(build_rccl(force=force))
     print(build_csredge(force=force))
     print(build_edgegrad(force=force))
+    print(build_aggregate(force=force))
     print(build_c_example())
     print(build_arith_probe(force=force))

@@ -19,7 +19,10 @@ that turns its indices into edge features; ``radius_graph`` is every neighbour w
 (``ops.radius_graph``) and ``radius_graph_edges`` their (batch, row, col) triples; ``edge_distance_features`` and ``edge_frame_features`` are the fused edge
 features of a structure network on such a graph (``ops.edge_rbf`` / ``ops.edge_frames``), differentiable in the
 coordinates and the frames (``ops.csr_edge_rbf_backward``, ``.csr_edge_pair_grad_sum``, ``.csr_edge_frames_backward``), and
-``radius_graph_incoming`` groups a graph's edges by their target; ``side_chain_torsions``
+``radius_graph_incoming`` groups a graph's edges by their target; ``edge_aggregate``, ``edge_gather``, ``edge_softmax`` and
+``edge_attention`` are message passing on such a graph -- segment sums, gathers and the softmax over every node's edges, with
+their gradients, in a fixed order and without atomics (``ops.segment_reduce``, ``.segment_gather``, ``.edge_dot``,
+``.segment_softmax``, ``.segment_softmax_backward``); ``side_chain_torsions``
 measures chi1 .. chi4, differentiably in the coordinates, and ``set_side_chain_torsions`` turns the side chains to given
 angles, differentiably in the angles (``ops.chi`` / ``ops.chi_set`` and their backwards); ``superposition_rmsd`` is the
 RMSD after optimal superposition, differentiable in both point sets (``ops.superpose`` / ``ops.superpose_backward``), and
@@ -1013,6 +1016,360 @@ def neighbors_to_radius_graph(neighbors_or_idx) -> RadiusGraph:
         dist = torch.masked_select(dist.detach().to(idx.device), real)
     out = (row_ptr, col, dist, count)
     return RadiusGraph(*(t if t is None or not arrays else t.numpy() for t in out))
+
+
+# ---- message passing on a graph: segment sums, gathers, the edge softmax (K55 - K59) --------------------------------------------
+class _EdgeLists(NamedTuple):
+    """The edge list a message-passing function was called with, on the kernels' device, as CSR lists"""
+    row_ptr: torch.Tensor   # (B*Q+1,) int64
+    col: torch.Tensor       # (E,) int32
+    B: int
+    Q: int
+    M: int
+
+    def grouping(self, at):
+        """``(ptr, perm)`` of the segments ``at`` the sources (the rows themselves) or the targets (the incoming list)"""
+        if at == "source":
+            return self.row_ptr, None
+        return ops.csr_incoming_edges(self.row_ptr, self.col, self.B, self.Q, self.M)
+
+    def index(self, at):
+        """(E,) int64: the flat node every edge position has ``at`` its source or target, -1 at the padding; no host read"""
+        E = self.col.shape[0]
+        batch, row = ops.csr_edge_rows(self.row_ptr, self.Q, E)
+        target = self.col.long()
+        real = (batch >= 0) & (target >= 0) & (target < self.M)
+        flat = batch.long() * self.M + target if at == "target" else batch.long() * self.Q + row.long()
+        return torch.where(real, flat, torch.full_like(flat, -1))
+
+    def nodes(self, at) -> int:
+        return self.M if at == "target" else self.Q
+
+
+def _message_graph(graph):
+    """``(first, col, B, Q, edge_shape)`` of a ``RadiusGraph`` -- its CSR lists, edge axis (E,) -- or of a padded list, a
+    ``Neighbors`` or a bare (B,Q,k) index tensor -- ``(idx, None)``, edge axis (B,Q,k)"""
+    if isinstance(graph, RadiusGraph):
+        Q = _graph_queries(graph)
+        if graph.col.ndim != 1:
+            raise ValueError(f"graph.col must have shape (edges,), got {tuple(graph.col.shape)}")
+        return graph.row_ptr, graph.col, int(graph.count.shape[0]), Q, (int(graph.col.shape[0]),)
+    idx = graph.idx if isinstance(graph, Neighbors) else graph
+    if not isinstance(idx, (torch.Tensor, np.ndarray)):
+        raise TypeError("graph must be a geometry.RadiusGraph, a geometry.Neighbors or a (B, Q, k) index tensor")
+    integer = np.issubdtype(idx.dtype, np.integer) if isinstance(idx, np.ndarray) else ops._is_integer_tensor(idx)
+    if idx.ndim != 3 or not integer:
+        raise ValueError(f"a padded neighbour list must be an integer tensor of shape (B, Q, k), got {idx.dtype} {tuple(idx.shape)}")
+    return idx, None, int(idx.shape[0]), int(idx.shape[1]), tuple(int(n) for n in idx.shape)
+
+
+def _check_at(at, n_targets, Q: int) -> int:
+    """M, the number of targets per structure: ``n_targets`` or, None, Q; ValueError for an ``at`` that is neither end"""
+    if at not in ("source", "target"):
+        raise ValueError(f"at must be 'source' or 'target', got {at!r}")
+    if n_targets is None:
+        return Q
+    if isinstance(n_targets, bool) or not isinstance(n_targets, (int, np.integer)) or n_targets < 0:
+        raise ValueError(f"n_targets must be a non-negative integer, got {n_targets!r}")
+    return int(n_targets)
+
+
+def _edge_tail(t, edge_shape, name: str, what: str, most: int) -> tuple:
+    """the axes of the per-edge tensor ``t`` after its edge axis ``edge_shape``: 0 .. ``most`` of them; ValueError otherwise"""
+    if not isinstance(t, (torch.Tensor, np.ndarray)):
+        raise TypeError(f"{name} must be a tensor or an ndarray")
+    shape, n = tuple(t.shape), len(edge_shape)
+    floating = np.issubdtype(t.dtype, np.floating) if isinstance(t, np.ndarray) else t.dtype.is_floating_point
+    if shape[:n] != tuple(edge_shape) or not (len(shape) - n <= most) or (most == 2 and len(shape) == n):
+        raise ValueError(f"{name} must have shape {tuple(edge_shape)} + {what} to match the graph, got {shape}")
+    if not floating:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    return shape[n:]
+
+
+def _edge_weight(weight, E: int, H: int):
+    """a weight (edges,) or (edges, H) as (E, H): one number per edge serves every head"""
+    if weight is None:
+        return None
+    weight = weight.reshape(E, H if weight.numel() == E * H else 1)   # named sizes: E may be 0
+    return weight.expand(E, H) if weight.shape[1] == 1 and H > 1 else weight
+
+
+def _edge_setup(named, floats, parsed, at, n_targets):
+    """What the four functions share: the lists of the graph ``parsed`` by ``_message_graph`` and the named operands on the
+    kernels' device (those of ``floats`` that require grad attached), ``finish`` and whether a graph is to be built.  A
+    padded (B,Q,k) list is the CSR list ``arange(B*Q + 1) * k`` -- its rows are the Q queries -- with the indices held to
+    [0, M), the targets, which a bipartite list has another number of."""
+    first, col, B, Q, edge_shape = parsed
+    M = _check_at(at, n_targets, Q)
+    args, finish = _marshal(tuple(named) + (("first", first), ("col", col)))
+    wants = _wants_grad(*floats.values())
+    if wants:
+        args = _attached(args, **floats)
+    if col is not None and tuple(first.shape) != (B * Q + 1,):
+        raise ValueError(f"graph.row_ptr must have shape ({B * Q + 1},) to match count {(B, Q)}, got {tuple(first.shape)}")
+    first, col = args.pop("first"), args.pop("col", None)
+    if col is None:
+        col = ops._idx32(first, M).reshape(-1)
+        first = torch.arange(B * Q + 1, dtype=torch.int64, device=col.device) * edge_shape[2]
+    return args, finish, _EdgeLists(first.to(torch.int64), col, B, Q, M), wants
+
+
+class _EdgeAggregate(torch.autograd.Function):
+    """ops.segment_reduce (K55) with K56 and K57 as its vector-Jacobian product (sum, mean) or a scatter to ``arg`` (max, min)"""
+
+    @staticmethod
+    def forward(ctx, messages, weight, row_ptr, col, ptr, perm, dims, at, reduce, return_arg):
+        lists = _EdgeLists(row_ptr, col, *dims)
+        extreme = reduce in ("max", "min")
+        out = ops.segment_reduce(messages, ptr, perm, B=lists.B, Q=lists.Q, M=lists.M, reduce=reduce, weight=weight,
+                                 row_ptr=row_ptr, col=col, return_arg=extreme)
+        out, arg = out if extreme else (out, None)
+        n = None
+        if reduce == "mean":   # the 1/n of the backward pass: n is the sum of ones over the same grouping, taken once, here
+            ones = torch.ones(messages.shape[0], 1, 1, dtype=torch.float32, device=messages.device)
+            n = ops.segment_reduce(ones, ptr, perm, B=lists.B, Q=lists.Q, M=lists.M, row_ptr=row_ptr, col=col).clamp_(min=1.0)
+        ctx.dims, ctx.at, ctx.reduce = dims, at, reduce
+        ctx.save_for_backward(messages, weight, row_ptr, col, arg, n)
+        if return_arg:
+            ctx.mark_non_differentiable(arg)
+            return out, arg
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_arg=None):
+        messages, weight, row_ptr, col, arg, n = ctx.saved_tensors
+        lists = _EdgeLists(row_ptr, col, *ctx.dims)
+        E, H, D = messages.shape
+        g = grad_out.contiguous().float()
+        if ctx.reduce in ("max", "min"):   # the destinations are unique: a plain scatter, deterministic
+            place = torch.arange(H * D, device=g.device).reshape(1, H, D)
+            dest = torch.where(arg >= 0, arg * (H * D) + place, torch.full_like(arg, E * H * D))
+            grad = torch.zeros(E * H * D + 1, dtype=g.dtype, device=g.device).scatter_(0, dest.reshape(-1), g.reshape(-1))
+            return (grad[:-1].reshape(E, H, D).to(messages.dtype),) + (None,) * 9
+        if ctx.reduce == "mean":
+            g = g / n
+        index = lists.index(ctx.at)
+        grad_messages = ops.segment_gather(g, index, weight).to(messages.dtype) if ctx.needs_input_grad[0] else None
+        grad_weight = None
+        if weight is not None and ctx.needs_input_grad[1]:
+            grad_weight = ops.edge_dot(g, messages, index).to(weight.dtype)
+        return (grad_messages, grad_weight) + (None,) * 8
+
+
+class _EdgeGather(torch.autograd.Function):
+    """ops.segment_gather (K56) with K55 (the sum at the same end of the edges) and K57 as its vector-Jacobian product"""
+
+    @staticmethod
+    def forward(ctx, values, weight, row_ptr, col, dims, at):
+        lists = _EdgeLists(row_ptr, col, *dims)
+        index = lists.index(at)
+        ctx.dims, ctx.at = dims, at
+        ctx.save_for_backward(values, weight, row_ptr, col, index)
+        return ops.segment_gather(values, index, weight)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        values, weight, row_ptr, col, index = ctx.saved_tensors
+        lists = _EdgeLists(row_ptr, col, *ctx.dims)
+        g = grad_out.contiguous().float()
+        grad_values = grad_weight = None
+        if ctx.needs_input_grad[0]:
+            ptr, perm = lists.grouping(ctx.at)
+            grad_values = ops.segment_reduce(g, ptr, perm, B=lists.B, Q=lists.Q, M=lists.M, weight=weight, row_ptr=row_ptr,
+                                             col=col).to(values.dtype)
+        if weight is not None and ctx.needs_input_grad[1]:
+            grad_weight = ops.edge_dot(values, g, index).to(weight.dtype)
+        return (grad_values, grad_weight) + (None,) * 4
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    """ops.segment_softmax (K58) with ops.segment_softmax_backward (K59) as its vector-Jacobian product"""
+
+    @staticmethod
+    def forward(ctx, logits, row_ptr, col, ptr, perm, dims, return_lse):
+        lists = _EdgeLists(row_ptr, col, *dims)
+        out = ops.segment_softmax(logits, ptr, perm, B=lists.B, Q=lists.Q, M=lists.M, row_ptr=row_ptr, col=col,
+                                  return_lse=return_lse)
+        w, lse = out if return_lse else (out, None)
+        ctx.dims = dims
+        ctx.save_for_backward(w, row_ptr, col, ptr, perm)
+        if return_lse:
+            ctx.mark_non_differentiable(lse)
+            return w, lse
+        return w
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_w, _grad_lse=None):
+        w, row_ptr, col, ptr, perm = ctx.saved_tensors
+        B, Q, M = ctx.dims
+        gx = ops.segment_softmax_backward(w, grad_w.contiguous(), ptr, perm, B=B, Q=Q, M=M, row_ptr=row_ptr, col=col)
+        return (gx.to(grad_w.dtype),) + (None,) * 6
+
+
+def _run_aggregate(m3, w2, lists, ptr, perm, at, reduce="sum", return_arg=False):
+    """K55 on prepared operands -- with its graph where ``m3`` (E,H,D) or ``w2`` (E,H) requires grad, alone otherwise"""
+    if _wants_grad(m3, w2):
+        return _EdgeAggregate.apply(m3, w2, lists.row_ptr, lists.col, ptr, perm, (lists.B, lists.Q, lists.M), at, reduce,
+                                    bool(return_arg))
+    return ops.segment_reduce(m3, ptr, perm, B=lists.B, Q=lists.Q, M=lists.M, reduce=reduce, weight=w2, row_ptr=lists.row_ptr,
+                              col=lists.col, return_arg=bool(return_arg))
+
+
+def _run_softmax(x2, lists, ptr, perm, return_lse=False):
+    """K58 on prepared logits (E,H) -- with its graph where they require grad, alone otherwise"""
+    if _wants_grad(x2):
+        return _EdgeSoftmax.apply(x2, lists.row_ptr, lists.col, ptr, perm, (lists.B, lists.Q, lists.M), bool(return_lse))
+    return ops.segment_softmax(x2, ptr, perm, B=lists.B, Q=lists.Q, M=lists.M, row_ptr=lists.row_ptr, col=lists.col,
+                               return_lse=bool(return_lse))
+
+
+def _weight_tail_fits(wtail, tail) -> bool:
+    return wtail in ((), (1,), (tail[0],) if len(tail) == 2 else (1,))
+
+
+def edge_aggregate(messages, graph, *, at="source", n_targets=None, reduce="sum", weight=None, return_arg=False):
+    """The sum, mean, max or min (``reduce``) of per-edge ``messages`` at every node of a graph: (B, Q, ...) at the sources of
+    the edges -- the rows of the graph -- or, with ``at="target"``, (B, n_targets, ...) at the points ``col`` names
+    (``n_targets`` defaults to Q and is required for a bipartite graph).  ``graph`` is a ``RadiusGraph``, with ``messages``
+    (E, C) or (E, H, D), one row per entry of ``graph.col``, or a padded list -- a ``Neighbors`` or its ``idx`` (B,Q,k) --,
+    with ``messages`` (B, Q, k, C) or (B, Q, k, H, D).  ``weight`` -- (E,) or (E, H); (B,Q,k) or (B,Q,k,H) -- multiplies every
+    message per head before the sum (sum and mean only; no (E,H,D) product is built).  With ``return_arg`` (max, min) the
+    result is ``(out, arg)``, ``arg`` int64 the winning edge position (flat over (B,Q,k) for a padded list), -1 at a node
+    without edges.  Nothing is read at the padding -- from ``row_ptr[-1]`` on, and wherever ``col`` is outside [0, n_targets),
+    the -1 of a padded list included --, so NaN there never reaches a result.  One HIP kernel (``ops.segment_reduce``, K55):
+    every node sums its own edges in ascending order, in double from +0, and rounds once -- no atomics, defined bit for
+    bit; the targets' lists come from ``ops.csr_incoming_edges``; a node without edges gets exactly +0.  Lists are not
+    split, so the time is that of the longest list.  No host read: it runs inside ``torch.cuda.graph`` behind
+    ``radius_graph(max_edges=n)``.  numpy in -> numpy out; tensors come back on the device of ``messages``.
+
+    Differentiable with respect to ``messages`` and ``weight`` (not twice, and not with respect to the graph): the backward
+    pass of sum and mean is ``ops.segment_gather`` (K56) and ``ops.edge_dot`` (K57); that of max and min a scatter to ``arg``,
+    whose destinations are unique.  Where neither requires grad the forward kernel runs alone."""
+    if reduce not in ops.AGGREGATE_MODES:
+        raise ValueError(f"reduce must be one of {', '.join(ops.AGGREGATE_MODES)}, got {reduce!r}")
+    if reduce in ("max", "min") and weight is not None:
+        raise ValueError(f"reduce={reduce!r} takes no weight")
+    if return_arg and reduce in ("sum", "mean"):
+        raise ValueError(f"reduce={reduce!r} has no arg: return_arg goes with max and min")
+    parsed = _message_graph(graph)
+    edge_shape = parsed[4]
+    tail = _edge_tail(messages, edge_shape, "messages", "(C,) or (H, D)", 2)
+    if weight is not None:
+        wtail = _edge_tail(weight, edge_shape, "weight", "() or (H,)", 1)
+        if not _weight_tail_fits(wtail, tail):
+            raise ValueError(f"weight must hold one number per edge or per head, got {wtail} for messages {tail}")
+    args, finish, lists, _ = _edge_setup((("messages", messages), ("weight", weight)), dict(messages=messages, weight=weight),
+                                         parsed, at, n_targets)
+    E = lists.col.shape[0]
+    H, D = tail if len(tail) == 2 else (1, tail[0])
+    m3 = args["messages"].reshape(E, H, D)
+    w2 = _edge_weight(args.get("weight"), E, H)
+    out = _run_aggregate(m3, w2, lists, *lists.grouping(at), at, reduce, return_arg)
+    shape = (lists.B, lists.nodes(at)) + tuple(tail)
+    if return_arg:
+        return finish((out[0].reshape(shape), out[1].reshape(shape)))
+    return finish((out.reshape(shape),))[0]
+
+
+def edge_gather(values, graph, *, at="target", n_targets=None, weight=None):
+    """A node's features on every edge of a graph: ``values`` (B, M, ...) of the edges' targets -- ``values[b, col[p]]`` -- or,
+    with ``at="source"``, (B, Q, ...) of their sources, as (E, ...) for a ``RadiusGraph`` and (B, Q, k, ...) for a padded list
+    (``Neighbors`` or ``idx``); ``...`` is (C,) or (H, D), and M is read off ``values`` (``n_targets`` where ``at="source"`` and
+    the graph is bipartite).  ``weight`` -- one number per edge, or per edge and head -- multiplies the row, rounded once.  The
+    result is exactly 0 at the padding, and nothing is read there.  The CSR counterpart of ``gather_neighbors``, which stays
+    as it is.  One HIP kernel (``ops.segment_gather``, K56) behind ``ops.csr_edge_rows``; no host read, so it runs inside
+    ``torch.cuda.graph``.  numpy in -> numpy out; tensors come back on the device of ``values``.
+
+    Differentiable with respect to ``values`` and ``weight`` (not twice, and not with respect to the graph): the gradient
+    of ``values`` is the sum of the incoming rows at the same end of the edges (``ops.segment_reduce``, K55: fixed order, no
+    atomics), that of ``weight`` ``ops.edge_dot`` (K57)."""
+    parsed = _message_graph(graph)
+    _, _, B, Q, edge_shape = parsed
+    if not isinstance(values, (torch.Tensor, np.ndarray)):
+        raise TypeError("values must be a tensor or an ndarray")
+    if at not in ("source", "target"):
+        raise ValueError(f"at must be 'source' or 'target', got {at!r}")
+    shape = tuple(values.shape)
+    floating = np.issubdtype(values.dtype, np.floating) if isinstance(values, np.ndarray) else values.dtype.is_floating_point
+    if len(shape) not in (3, 4) or shape[0] != B or (at == "source" and shape[1] != Q) or not floating:
+        raise ValueError(f"values must be a floating-point tensor of shape ({B}, {'M' if at == 'target' else Q}, C) or "
+                         f"(.., H, D) to match the graph, got {values.dtype} {shape}")
+    if at == "target":
+        n_targets = shape[1]
+    tail = shape[2:]
+    if weight is not None:
+        wtail = _edge_tail(weight, edge_shape, "weight", "() or (H,)", 1)
+        if not _weight_tail_fits(wtail, tail):
+            raise ValueError(f"weight must hold one number per edge or per head, got {wtail} for values {tail}")
+    args, finish, lists, wants = _edge_setup((("values", values), ("weight", weight)), dict(values=values, weight=weight),
+                                             parsed, at, n_targets)
+    E = lists.col.shape[0]
+    H, D = tail if len(tail) == 2 else (1, tail[0])
+    v3 = args["values"].reshape(B * lists.nodes(at), H, D)
+    w2 = _edge_weight(args.get("weight"), E, H)
+    if wants:
+        out = _EdgeGather.apply(v3, w2, lists.row_ptr, lists.col, (lists.B, lists.Q, lists.M), at)
+    else:
+        out = ops.segment_gather(v3, lists.index(at), w2)
+    return finish((out.reshape(tuple(edge_shape) + tuple(tail)),))[0]
+
+
+def edge_softmax(logits, graph, *, at="source", n_targets=None, return_lse=False):
+    """The softmax of attention ``logits`` over the edges of every node of a graph -- over every row (``at="source"``) or over
+    the edges that arrive at every target (``at="target"``; ``n_targets`` as in ``edge_aggregate``): the weights, of the
+    shape of ``logits`` -- (E,) or (E, H) for a ``RadiusGraph``, (B,Q,k) or (B,Q,k,H) for a padded list, each head on its own
+    -- or, with ``return_lse``, ``(w, lse)`` with ``lse`` (B, nodes) or (B, nodes, H), the logarithm of every node's sum.  One
+    HIP kernel (``ops.segment_softmax``, K58): the maximum is subtracted, the exponentials are evaluated and summed in
+    double in ascending order and each weight is rounded once; no temporaries, no atomics, repeatable bit for bit.  A node
+    with one edge gives exactly 1; a logit of -inf gives 0; a node without edges, or with -inf on all of them, gives zeros
+    and ``lse`` -inf; the weights are exactly 0 at the padding and nothing is read there.  No host read, so it runs inside
+    ``torch.cuda.graph``.  numpy in -> numpy out; tensors come back on the device of ``logits``.
+
+    Differentiable with respect to ``logits`` (``ops.segment_softmax_backward``, K59; not twice); ``lse`` carries no graph."""
+    parsed = _message_graph(graph)
+    edge_shape = parsed[4]
+    tail = _edge_tail(logits, edge_shape, "logits", "() or (H,)", 1)
+    args, finish, lists, _ = _edge_setup((("logits", logits),), dict(logits=logits), parsed, at, n_targets)
+    E = lists.col.shape[0]
+    x2 = args["logits"].reshape(E, tail[0] if tail else 1)
+    out = _run_softmax(x2, lists, *lists.grouping(at), return_lse)
+    if return_lse:
+        return finish((out[0].reshape(tuple(edge_shape) + tail), out[1].reshape((lists.B, lists.nodes(at)) + tail)))
+    return finish((out.reshape(tuple(edge_shape) + tail),))[0]
+
+
+def edge_attention(logits, values, graph, *, at="source", n_targets=None):
+    """One attention step over a graph: every node's softmax-weighted sum of the ``values`` on its edges,
+    ``edge_aggregate(values, graph, weight=edge_softmax(logits, graph))`` -- (B, nodes, C) or (B, nodes, H, D) from ``logits``
+    (E,) or (E, H) and ``values`` (E, C) or (E, H, D) (for a padded list the edge axis is (B,Q,k)).  It is COMPOSED of the two
+    functions, on one set of lists (at the targets the incoming list is built once): two HIP kernels forwards (K58, K55),
+    K56, K57 and K59 backwards, and no (E,H,D) product of weights and values is built; a single fused kernel is not part of
+    this version.  Differentiable with respect to ``logits`` and
+    ``values``; everything ``edge_softmax`` and ``edge_aggregate`` say about order, padding and running inside
+    ``torch.cuda.graph`` holds::
+
+        g = radius_graph(x, 10.0, mask, max_edges=n)
+        rbf = radius_edge_distance_features(xyz, g)                    # (E, P*R)
+        out = edge_attention(rbf @ w_logit, (rbf @ w_value).reshape(-1, H, D), g)   # (B, N, H, D); backward() reaches the weights and xyz
+    """
+    parsed = _message_graph(graph)
+    edge_shape = parsed[4]
+    ltail = _edge_tail(logits, edge_shape, "logits", "() or (H,)", 1)
+    tail = _edge_tail(values, edge_shape, "values", "(C,) or (H, D)", 2)
+    if not _weight_tail_fits(ltail, tail):
+        raise ValueError(f"logits must hold one number per edge or per head, got {ltail} for values {tail}")
+    args, finish, lists, _ = _edge_setup((("logits", logits), ("values", values)), dict(logits=logits, values=values), parsed, at,
+                                         n_targets)
+    E = lists.col.shape[0]
+    H, D = tail if len(tail) == 2 else (1, tail[0])
+    ptr, perm = lists.grouping(at)
+    w = _edge_weight(_run_softmax(args["logits"].reshape(E, ltail[0] if ltail else 1), lists, ptr, perm), E, H)
+    out = _run_aggregate(args["values"].reshape(E, H, D), w, lists, ptr, perm, at)
+    return finish((out.reshape((lists.B, lists.nodes(at)) + tuple(tail)),))[0]
 
 
 class SideChainTorsions(NamedTuple):

@@ -16,7 +16,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _csredge, _edgegrad, _lib
+from . import _aggregate, _csredge, _edgegrad, _lib
 
 
 RNG_STATE_WORDS = 528  # PS_RNG_STATE_WORDS of include/protstruc_hip.h
@@ -2793,6 +2793,228 @@ def csr_edge_frames_backward(rot: torch.Tensor, trans: torch.Tensor, row_ptr: to
                              _ptr(cl), E, _ptr(ip), _ptr(ie), ie.shape[0], _ptr(gp), _ptr(gr), *(_ptr(o) for o in out),
                              *(() if bipartite else (None, None)), B, M, Q, _stream(r))
     return out
+
+
+# ---- message passing on graphs (K55 - K59, include/protstruc_aggregate.h) ------------------------------------------------------
+AGGREGATE_MAX_HEADS = 64  # PS_AGGREGATE_MAX_HEADS of include/protstruc_aggregate.h
+AGGREGATE_MAX_ROW = 4096  # PS_AGGREGATE_MAX_ROW: H * D, the floats of one row
+AGGREGATE_MODES = ("sum", "mean", "max", "min")   # by position, the modes PS_AGGREGATE_SUM .. PS_AGGREGATE_MIN
+
+
+def _launch_aggregate(name: str, *args) -> None:
+    """Call entry point ``name`` of libprotstruc_aggregate.so; HipLibraryError if it does not return hipSuccess."""
+    rc = getattr(_aggregate.load(), name)(*args)
+    if rc:
+        _aggregate.check(rc, name)
+
+
+def _check_rows(t, name: str, E: Optional[int] = None) -> Tuple[int, int, int]:
+    """(rows, H, D) of per-edge or per-node data ``t`` (rows, H, D), floating-point, within the limits; ValueError otherwise"""
+    shape = tuple(t.shape)
+    if len(shape) != 3 or (E is not None and shape[0] != E):
+        raise ValueError(f"{name} must have shape ({'rows' if E is None else E}, heads, floats), got {shape}")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor, got {t.dtype}")
+    _check_count(shape[1], 1, AGGREGATE_MAX_HEADS, f"heads in {name}")
+    if shape[2] < 1 or shape[1] * shape[2] > AGGREGATE_MAX_ROW:
+        raise ValueError(f"a row of {name} holds 1 .. {AGGREGATE_MAX_ROW} floats, got {shape[1]} x {shape[2]}")
+    return shape
+
+
+def _check_grouping(ptr, perm, row_ptr, col, B, Q, M, E: int) -> int:
+    """S of a grouping over ``E`` edge positions (include/protstruc_aggregate.h): ``ptr`` (S+1,) int64 with ``perm`` None
+    (the source grouping, S = B*Q) or ``perm`` (n,) int64 (the target grouping, S = B*M); ``col`` (E,) integers with
+    ``row_ptr`` (B*Q+1,), or neither; ValueError otherwise."""
+    _check_sizes(B=B, Q=Q, M=M)
+    B, Q, M = int(B), int(Q), int(M)
+    _check_batch(B)
+    _check_count(Q, 0, 2 ** 24, "queries per structure")
+    _check_count(M, 0, 2 ** 24, "points per structure")
+    S = B * (Q if perm is None else M)
+    if tuple(ptr.shape) != (S + 1,) or ptr.dtype != torch.int64:
+        raise ValueError(f"ptr must be an int64 tensor of shape ({S + 1},), the {S} segments and one, got {ptr.dtype} "
+                         f"{tuple(ptr.shape)}")
+    if perm is not None and (perm.ndim != 1 or perm.dtype != torch.int64):
+        raise ValueError(f"perm must be an int64 tensor of shape (members,), got {perm.dtype} {tuple(perm.shape)}")
+    if (col is None) != (row_ptr is None):
+        raise ValueError("row_ptr and col come together: the edge list the members are checked against")
+    if col is not None and _check_csr_graph(row_ptr, col, B, Q, f"{B} structures") != E:
+        raise ValueError(f"col must have shape ({E},), one entry per edge position, got {tuple(col.shape)}")
+    _same_device(ptr, perm=perm, row_ptr=row_ptr, col=col)
+    return S
+
+
+def _grouping_args(ptr, perm, row_ptr, col, M: int):
+    """the grouping's tensors as the kernels take them, and their six arguments (ptr, perm, n_perm, row_ptr, col)"""
+    keep = (ptr.contiguous(), None if perm is None else perm.contiguous(), None if row_ptr is None else _row_ptr64(row_ptr),
+            None if col is None else _col32(col, M))
+    pm = keep[1] if keep[1] is not None and keep[1].shape[0] else None   # an empty tensor has no device pointer
+    return keep, (_ptr(keep[0]), _ptr(pm), 0 if pm is None else pm.shape[0], _ptr(keep[2]), _ptr(keep[3]))
+
+
+def check_segment_reduce_shapes(values, ptr, perm=None, weight=None, row_ptr=None, col=None, B=0, Q=0, M=0, reduce="sum",
+                                return_arg=False) -> Tuple[int, int, int, int]:
+    """Shape rules of ``segment_reduce`` (no launch): ValueError; returns (E, H, D, S)."""
+    E, H, D = _check_rows(values, "values")
+    if reduce not in AGGREGATE_MODES:
+        raise ValueError(f"reduce must be one of {', '.join(AGGREGATE_MODES)}, got {reduce!r}")
+    if reduce in ("max", "min") and weight is not None:
+        raise ValueError(f"reduce={reduce!r} takes no weight")
+    if return_arg and reduce in ("sum", "mean"):
+        raise ValueError(f"reduce={reduce!r} has no arg: return_arg goes with max and min")
+    _check_optional(weight, (E, H), "weight", "the edges and heads of values", floating=True)
+    S = _check_grouping(ptr, perm, row_ptr, col, B, Q, M, E)
+    _same_device(values, ptr=ptr, weight=weight)
+    return E, H, D, S
+
+
+def segment_reduce(values: torch.Tensor, ptr: torch.Tensor, perm: Optional[torch.Tensor] = None, *, B: int, Q: int, M: int,
+                   reduce: str = "sum", weight: Optional[torch.Tensor] = None, row_ptr: Optional[torch.Tensor] = None,
+                   col: Optional[torch.Tensor] = None, return_arg: bool = False):
+    """K55.  The sum, mean, max or min of the per-edge rows ``values`` (E,H,D) over every segment of a grouping: ``out``
+    (S,H,D) fp32 or, with ``return_arg`` (max, min), ``(out, arg (S,H,D) int64)``, the winning edge positions.  The source
+    grouping is ``ptr = row_ptr`` with ``perm`` None (S = B*Q); the target grouping ``ptr, perm = csr_incoming_edges(...)``
+    (S = B*M).  With ``row_ptr`` and ``col`` the members at the padding are skipped and nothing is read there.  Sums are in
+    double from +0, members ascending, each term the exact product with ``weight`` (E,H), rounded once: defined bit for
+    bit; ties of max / min go to the lower position; an empty segment gives +0 and -1.  No atomics, no host read, every
+    element written (include/protstruc_aggregate.h)."""
+    E, H, D, S = check_segment_reduce_shapes(values, ptr, perm, weight, row_ptr, col, B, Q, M, reduce, return_arg)
+    v, wt = _f32c(values, "values"), _f32c_opt(weight, "weight")
+    keep, lists = _grouping_args(ptr, perm, row_ptr, col, int(M))
+    _require_device(keep[0], "ptr")
+    with _on(v.device):
+        if not (S and E):   # nothing to launch (an empty tensor has no device pointer): every segment is empty
+            out = torch.zeros(S, H, D, dtype=torch.float32, device=v.device)
+            return (out, torch.full((S, H, D), -1, dtype=torch.int64, device=v.device)) if return_arg else out
+        out = torch.empty(S, H, D, dtype=torch.float32, device=v.device)   # every element is written
+        arg = torch.empty(S, H, D, dtype=torch.int64, device=v.device) if return_arg else None
+        _launch_aggregate("ps_segment_reduce_f32", _ptr(v), _ptr(wt), *lists, E, AGGREGATE_MODES.index(reduce), _ptr(out),
+                          _ptr(arg), int(B), int(Q), int(M), H, D, _stream(v))
+    return (out, arg) if return_arg else out
+
+
+def _check_index(index, E: Optional[int] = None) -> int:
+    if index.ndim != 1 or index.dtype != torch.int64 or (E is not None and index.shape[0] != E):
+        raise ValueError(f"index must be an int64 tensor of shape ({'edges' if E is None else E},), got {index.dtype} "
+                         f"{tuple(index.shape)}")
+    return index.shape[0]
+
+
+def check_segment_gather_shapes(node, index, weight=None) -> Tuple[int, int, int, int]:
+    """Shape rules of ``segment_gather`` (no launch): ValueError; returns (E, S, H, D)."""
+    S, H, D = _check_rows(node, "node")
+    E = _check_index(index)
+    _check_optional(weight, (E, H), "weight", "the edges of index and the heads of node", floating=True)
+    _same_device(node, index=index, weight=weight)
+    return E, S, H, D
+
+
+def segment_gather(node: torch.Tensor, index: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K56.  The node rows ``node`` (S,H,D) on every edge, the adjoint of the segment sum: ``out`` (E,H,D) fp32,
+    ``out[e] = weight[e] * node[index[e]]`` per head (the exact product rounded once), or a copy without ``weight`` (E,H).
+    ``index`` (E,) int64 is a flat node index; outside [0, S) -- the caller's mark for the padding -- the row is exactly
+    +0 and nothing is read, the weight included.  No host read; every element written (include/protstruc_aggregate.h)."""
+    E, S, H, D = check_segment_gather_shapes(node, index, weight)
+    nd, wt, ix = _f32c(node, "node"), _f32c_opt(weight, "weight"), index.contiguous()
+    _require_device(ix, "index")
+    with _on(nd.device):
+        if not (E and S):
+            return torch.zeros(E, H, D, dtype=torch.float32, device=nd.device)
+        out = torch.empty(E, H, D, dtype=torch.float32, device=nd.device)
+        _launch_aggregate("ps_segment_gather_f32", _ptr(nd), _ptr(wt), _ptr(ix), E, S, H, D, _ptr(out), _stream(nd))
+    return out
+
+
+def check_edge_dot_shapes(node, values, index) -> Tuple[int, int, int, int]:
+    """Shape rules of ``edge_dot`` (no launch): ValueError; returns (E, S, H, D)."""
+    S, H, D = _check_rows(node, "node")
+    E = _check_index(index)
+    if tuple(values.shape) != (E, H, D) or not values.dtype.is_floating_point:
+        raise ValueError(f"values must be a floating-point tensor of shape {(E, H, D)} to match index and node, got "
+                         f"{values.dtype} {tuple(values.shape)}")
+    _same_device(node, index=index, values=values)
+    return E, S, H, D
+
+
+def edge_dot(node: torch.Tensor, values: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """K57.  ``out[e, h] = sum_d node[index[e], h, d] * values[e, h, d]``, (E,H) fp32: the gradient of a weight.  Exact
+    products, summed in double in the fixed order of the header (fours ascending, then a tree) and rounded once, whatever
+    the alignment; exactly +0 where ``index`` is outside [0, S), and nothing is read there (include/protstruc_aggregate.h)."""
+    E, S, H, D = check_edge_dot_shapes(node, values, index)
+    nd, v, ix = _f32c(node, "node"), _f32c(values, "values"), index.contiguous()
+    _require_device(ix, "index")
+    with _on(nd.device):
+        if not (E and S):
+            return torch.zeros(E, H, dtype=torch.float32, device=nd.device)
+        out = torch.empty(E, H, dtype=torch.float32, device=nd.device)
+        _launch_aggregate("ps_edge_dot_f32", _ptr(nd), _ptr(v), _ptr(ix), E, S, H, D, _ptr(out), _stream(nd))
+    return out
+
+
+def _check_heads(t, name: str) -> Tuple[int, int]:
+    if t.ndim != 2 or not t.dtype.is_floating_point:
+        raise ValueError(f"{name} must be a floating-point tensor of shape (edges, heads), got {t.dtype} {tuple(t.shape)}")
+    _check_count(t.shape[1], 1, AGGREGATE_MAX_HEADS, f"heads in {name}")
+    return tuple(t.shape)
+
+
+def check_segment_softmax_shapes(logits, ptr, perm=None, row_ptr=None, col=None, B=0, Q=0, M=0) -> Tuple[int, int, int]:
+    """Shape rules of ``segment_softmax`` (no launch): ValueError; returns (E, H, S)."""
+    E, H = _check_heads(logits, "logits")
+    S = _check_grouping(ptr, perm, row_ptr, col, B, Q, M, E)
+    _same_device(logits, ptr=ptr)
+    return E, H, S
+
+
+def segment_softmax(logits: torch.Tensor, ptr: torch.Tensor, perm: Optional[torch.Tensor] = None, *, B: int, Q: int, M: int,
+                    row_ptr: Optional[torch.Tensor] = None, col: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """K58.  The softmax of ``logits`` (E,H) over every segment of a grouping (see ``segment_reduce``), per head: ``w`` (E,H)
+    fp32 or, with ``return_lse``, ``(w, lse (S,H))``.  The maximum is subtracted, the exponentials are evaluated and summed
+    in double, members ascending, and each weight is rounded once.  A segment of one member gives exactly 1; a logit of
+    -inf gives +0; an empty segment, or one whose maximum is -inf, gives weights +0 and ``lse`` -inf; ``w`` is +0 at the
+    padding and nothing is read there.  No atomics, no host read (include/protstruc_aggregate.h)."""
+    E, H, S = check_segment_softmax_shapes(logits, ptr, perm, row_ptr, col, B, Q, M)
+    x = _f32c(logits, "logits")
+    keep, lists = _grouping_args(ptr, perm, row_ptr, col, int(M))
+    _require_device(keep[0], "ptr")
+    with _on(x.device):
+        if not (S and E):
+            w = torch.zeros(E, H, dtype=torch.float32, device=x.device)
+            return (w, torch.full((S, H), float("-inf"), dtype=torch.float32, device=x.device)) if return_lse else w
+        w = torch.empty(E, H, dtype=torch.float32, device=x.device)   # zeroed by the entry point's first launch
+        lse = torch.empty(S, H, dtype=torch.float32, device=x.device) if return_lse else None
+        _launch_aggregate("ps_segment_softmax_f32", _ptr(x), *lists, E, _ptr(w), _ptr(lse), int(B), int(Q), int(M), H, _stream(x))
+    return (w, lse) if return_lse else w
+
+
+def check_segment_softmax_backward_shapes(w, grad_w, ptr, perm=None, row_ptr=None, col=None, B=0, Q=0, M=0) -> Tuple[int, int, int]:
+    """Shape rules of ``segment_softmax_backward`` (no launch): ValueError; returns (E, H, S)."""
+    E, H = _check_heads(w, "w")
+    if tuple(grad_w.shape) != (E, H) or not grad_w.dtype.is_floating_point:
+        raise ValueError(f"grad_w must be a floating-point tensor of shape {(E, H)} to match w, got {grad_w.dtype} "
+                         f"{tuple(grad_w.shape)}")
+    S = _check_grouping(ptr, perm, row_ptr, col, B, Q, M, E)
+    _same_device(w, grad_w=grad_w, ptr=ptr)
+    return E, H, S
+
+
+def segment_softmax_backward(w: torch.Tensor, grad_w: torch.Tensor, ptr: torch.Tensor, perm: Optional[torch.Tensor] = None, *,
+                             B: int, Q: int, M: int, row_ptr: Optional[torch.Tensor] = None,
+                             col: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K59.  The gradient of ``segment_softmax`` with respect to the logits, (E,H) fp32, given its output ``w`` and the
+    incoming ``grad_w``: per segment and head ``t = sum w * g`` in double, members ascending, and ``w * (g - t)`` rounded
+    once -- defined bit for bit given ``w``; +0 at the padding, where no gradient is read (include/protstruc_aggregate.h)."""
+    E, H, S = check_segment_softmax_backward_shapes(w, grad_w, ptr, perm, row_ptr, col, B, Q, M)
+    ww, g = _f32c(w, "w"), _f32c(grad_w, "grad_w")
+    keep, lists = _grouping_args(ptr, perm, row_ptr, col, int(M))
+    _require_device(keep[0], "ptr")
+    with _on(ww.device):
+        if not (S and E):
+            return torch.zeros(E, H, dtype=torch.float32, device=ww.device)
+        gx = torch.empty(E, H, dtype=torch.float32, device=ww.device)
+        _launch_aggregate("ps_segment_softmax_backward_f32", _ptr(ww), _ptr(g), *lists, E, _ptr(gx), int(B), int(Q), int(M), H,
+                          _stream(ww))
+    return gx
 
 
 CHI_MAX_TYPES = 32  # PS_CHI_MAX_TYPES of include/protstruc_hip.h: the tables travel in the kernel's arguments
